@@ -24,6 +24,9 @@ Output: ONE JSON line on rank 0. `roofline` describes the dominant kernel of the
 MFMA GEMM); `hbm_kernels` lists the HBM-bound hot-path kernels on the headline shape
 [14336, 4096] bf16 per-channel with achieved GB/s vs 8 TB/s; `cpu_baseline` is the reference's
 eager ATen chain (oracle/eager_chain.py, a port) timed on this box's host cores on a bounded sample.
+
+`--dump-outputs DIR` writes the logits of the last timed step to DIR/logits.npy (float32, at most 64 MB: a fixed, seeded
+sample of rows at the Llama-3-8B shapes), so two builds run with the same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -486,6 +489,35 @@ def cpu_baseline(config: llama.LlamaConfig, budget_s: float = 20.0) -> dict:
     }
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs: array bytes written in all (the .npy headers add 128 B per file)
+
+
+def dump_outputs(directory: pathlib.Path, outputs: dict[str, torch.Tensor]) -> dict:
+    """Write each output as directory/<name>.npy in float32 (float64 stays float64). An output over its share of the budget
+    is written as a sample of its rows (the last dimension kept whole): rows drawn by a generator seeded with 0 from the
+    shape alone, in ascending order, so two builds run with the same arguments write the same rows."""
+    import numpy as np
+
+    directory.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(outputs)
+    written = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        rows = t.reshape(-1, t.shape[-1])
+        keep = min(rows.shape[0], max(1, share // (rows.shape[1] * dtype.itemsize)))
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).removeprefix("torch."), "written": str(dtype).removeprefix("torch.")}
+        if keep < rows.shape[0]:
+            index = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            rows = rows.index_select(0, index.to(rows.device))
+            entry["rows_sampled"] = keep
+        else:
+            rows = t
+        np.save(directory / f"{name}.npy", rows.to(dtype).cpu().numpy())
+        written[name] = entry
+    return {"dir": str(directory), "outputs": written}
+
+
 def relaunch_under_torchrun(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (one per GPU) as CHILDREN through
     torch.distributed.run and hand back their exit code. The ranks are NEW child processes — never an exec of this process —
@@ -528,9 +560,13 @@ def main() -> None:
     ap.add_argument("--fuse-rowsums", action="store_true", help="A/B: every weight re-quantized right before its GEMM by the one-pass codes + row sums kernel (no batched launch, no rowsum_i8 launches)")
     ap.add_argument("--force-dist", action="store_true", help="create the process group even for one rank: the range all-reduce and the cross-rank "
                     "check then run through the collective backend (RCCL with one rank executes the same all_reduce(MIN) an 8-GPU run issues)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the logits of the last timed step as DIR/logits.npy "
+                    "(float32; rank 0; a fixed, seeded sample of whole rows when the tensor exceeds the 64 MB budget)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
         raise SystemExit(relaunch_under_torchrun(args.gpus))  # N fresh ranks; never a silent 1-GPU run
     if args.calib_seqs is None:
@@ -600,15 +636,15 @@ def main() -> None:
     def step():
         if graph is not None:
             graph.replay()
-        else:
-            forward()
+            return static_out
+        return forward()
 
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -617,6 +653,9 @@ def main() -> None:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the last timed step's logits, before the side measurements below free the graph's memory
+    dumped = dump_outputs(pathlib.Path(args.dump_outputs), {"logits": out}) if args.dump_outputs and rank == 0 else None
+    del out
 
     # the drop-in path beside the headline: what ff.quantize_model() gives with NO harness — the module graph itself, every
     # quantizer its own module call, the dispatcher's int8 linear; its Llama modules run RMSNorm / SiLU*up / rotary / attention as
@@ -698,6 +737,7 @@ def main() -> None:
         "world_size": torch.distributed.get_world_size() if world > 1 else 1,
         "collective_backend": (torch.distributed.get_backend() + (" (RCCL over xGMI)" if torch.distributed.get_backend() == "nccl" else "")) if torch.distributed.is_initialized() else None,
         "module_graph_drop_in": module_graph,
+        "dumped_outputs": dumped,
         "calibration": {"sequences_per_gpu": calib_steps * args.batch, "sequences_total": calib_steps * args.batch * world, "seconds": round(calib_s, 3),
                         "sequences_per_s_all_gpus": round(calib_steps * args.batch * world / calib_s, 2),
                         "allreduce_floats": payload, "collective": "1 x all_reduce(MIN) over RCCL" if world > 1 else ("1 x all_reduce(MIN) through a one-rank group (--force-dist)" if torch.distributed.is_initialized() else "none (1 GPU)"),
