@@ -178,6 +178,7 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_linear_w8a8_earlier": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _i64, _i64, _vp, _sz, _vp]),
     "ffq_linear_w8a8_gated": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp, _vp, _vp]),
     "ffq_gptq_block": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _vp]),
+    "ffq_gptq_block_grid": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _d, _vp]),
     "ffq_pack_gguf_blocks": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "ffq_quantize_pack_int4": (_i, [_vp, _i, _vp, _i64, _vp, _i64, _tp, _i64, _vp, _vp]),
     "ffq_unpack_dequantize_int4": (_i, [_vp, _vp, _i64, _vp, _i64, _tp, _i64, _vp, _i, _vp]),
@@ -207,6 +208,10 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_attention": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _d, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
 }
 
+# Entry points only the HIP library must export: a host library (the CPU oracle) without one gets the attribute bound to None and
+# callers treat that as "not covered". Whether the symbol is there is the capability check (FFQ_ABI_VERSION does not move for them).
+DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid"})
+
 
 class FFQLibrary:
     """A loaded implementation of the ``ffq_*`` ABI."""
@@ -214,11 +219,15 @@ class FFQLibrary:
     def __init__(self, path: str | os.PathLike[str]):
         self.path = os.fspath(path)
         self._dll = ctypes.CDLL(self.path)
+        missing = []
         for name, (restype, argtypes) in SIGNATURES.items():
             try:
                 fn = getattr(self._dll, name)
             except AttributeError as e:
-                raise ImportError(f"{self.path} does not export {name}") from e
+                if name not in DEVICE_ONLY:
+                    raise ImportError(f"{self.path} does not export {name}") from e
+                missing.append(name)
+                continue
             fn.restype = restype
             fn.argtypes = argtypes
             setattr(self, name, fn)
@@ -226,6 +235,10 @@ class FFQLibrary:
         if version != FFQ_ABI_VERSION:
             raise ImportError(f"{self.path}: ABI version {version}, expected {FFQ_ABI_VERSION}")
         self.backend_name: str = self.ffq_backend_name().decode()  # type: ignore[attr-defined]
+        if missing and self.is_device:
+            raise ImportError(f"{self.path} does not export {missing[0]}")
+        for name in missing:
+            setattr(self, name, None)
 
     @property
     def is_device(self) -> bool:

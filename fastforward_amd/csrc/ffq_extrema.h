@@ -8,8 +8,13 @@
 // estimator step then merges two numbers (ffq_running_minmax_step on a 2-element tensor) instead of reading the tensor again.
 // Same values as ffq_minmax_by_tile on the finished tensor: min and max are exact, the keys order -0.0 below +0.0 as the 16-bit
 // pattern accumulators of ffq_minmax.hip do.
+//
+// Also here: A5 of one tile (range_to_parameters) and its constants (make_range_args), which every kernel that turns a range
+// into parameters shares.
 #pragma once
 #include "ffq_common.h"
+
+#include <math.h>
 
 namespace ffq {
 
@@ -65,6 +70,46 @@ __device__ __forceinline__ void extrema_publish(const ExtremaSink& s, float mn, 
   if (t != arrivals - 1) return;
   asm volatile("" ::: "memory");
   extrema_finish(s);
+}
+
+// ---- A5 (range -> scale / offset) of ONE tile, shared by parameters_for_range_kernel and the one-launch estimator step
+// (ffq_minmax.hip) and by the GPTQ group refit (ffq_gptq.hip): one copy of the arithmetic, the same bits everywhere ------------
+struct RangeArgs {
+  int range_dt, scale_dt, offset_dt;
+  int64_t ntiles;
+  int symmetric, allow_one_sided, round_offset;
+  float abs_int_min, abs_int_max, num_steps, int_min;
+};
+
+__device__ __forceinline__ void range_to_parameters(float lo, float hi, int one_sided, const RangeArgs& a, float& scale, float& offset) {
+  if (a.symmetric && one_sided) lo = 0.0f;                               // (range.py:104-105)
+  if (a.symmetric && !one_sided) {
+    const float neg = __builtin_fabsf(lo) / a.abs_int_min;               // (:108)
+    const float pos = __builtin_fabsf(hi) / a.abs_int_max;               // (:109)
+    scale = (neg != neg || pos != pos) ? NAN : __builtin_fmaxf(neg, pos);  // torch.max  (:110)
+    offset = 0.0f;  // reference returns None; the setter fills the buffer with 0
+  } else {
+    const float interval = hi - lo;                                      // (:118)
+    scale = interval / a.num_steps;                                      // (:119)
+    scale = scale != scale ? scale : __builtin_fmaxf(scale, 1.1920928955078125e-07f);  // clamp(eps) (:120)
+    const float q = lo / scale;
+    offset = q - a.int_min;                                              // (:121)
+    if (a.round_offset) offset = rne(offset);                            // dynamic path, _quantizer_impl.py:275
+  }
+}
+
+inline RangeArgs make_range_args(int range_dt, int64_t ntiles, double num_bits, int symmetric, int allow_one_sided, int scale_dt, int offset_dt,
+                                int round_offset) {
+  RangeArgs a;
+  a.range_dt = range_dt; a.scale_dt = scale_dt; a.offset_dt = offset_dt;
+  a.ntiles = ntiles;
+  a.symmetric = symmetric; a.allow_one_sided = allow_one_sided; a.round_offset = round_offset;
+  const double int_min = -pow(2.0, num_bits - 1.0), int_max = -int_min - 1.0;
+  a.abs_int_min = (float)fabs(int_min);
+  a.abs_int_max = (float)fabs(int_max);
+  a.num_steps = (float)(pow(2.0, num_bits) - 1.0);
+  a.int_min = (float)int_min;
+  return a;
 }
 
 }  // namespace ffq

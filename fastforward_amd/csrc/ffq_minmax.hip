@@ -16,6 +16,7 @@
 // wavefront (64-lane) xor-shuffle butterflies, one LDS hop across the 4 waves of a block.
 #include "ffq_affine.h"
 #include "ffq_common.h"
+#include "ffq_extrema.h"
 #include "ffq_vec.h"
 
 #include <math.h>
@@ -207,31 +208,6 @@ __device__ __forceinline__ void write_result(T* mn_out, T* mx_out, uint32_t t, M
   mn_out[t] = from_f32<T>(mn);
   mx_out[t] = from_f32<T>(mx);
   if (f && flags) atomicOr(flags, f);
-}
-
-// ---- A5 (range -> scale / offset) of ONE tile, shared by parameters_for_range_kernel and the one-launch estimator step ------------
-struct RangeArgs {
-  int range_dt, scale_dt, offset_dt;
-  int64_t ntiles;
-  int symmetric, allow_one_sided, round_offset;
-  float abs_int_min, abs_int_max, num_steps, int_min;
-};
-
-__device__ __forceinline__ void range_to_parameters(float lo, float hi, int one_sided, const RangeArgs& a, float& scale, float& offset) {
-  if (a.symmetric && one_sided) lo = 0.0f;                               // (range.py:104-105)
-  if (a.symmetric && !one_sided) {
-    const float neg = __builtin_fabsf(lo) / a.abs_int_min;               // (:108)
-    const float pos = __builtin_fabsf(hi) / a.abs_int_max;               // (:109)
-    scale = (neg != neg || pos != pos) ? NAN : __builtin_fmaxf(neg, pos);  // torch.max  (:110)
-    offset = 0.0f;  // reference returns None; the setter fills the buffer with 0
-  } else {
-    const float interval = hi - lo;                                      // (:118)
-    scale = interval / a.num_steps;                                      // (:119)
-    scale = scale != scale ? scale : __builtin_fmaxf(scale, 1.1920928955078125e-07f);  // clamp(eps) (:120)
-    const float q = lo / scale;
-    offset = q - a.int_min;                                              // (:121)
-    if (a.round_offset) offset = rne(offset);                            // dynamic path, _quantizer_impl.py:275
-  }
 }
 
 // ---- stage 1, one tile: grid-stride over chunks, one Partial per block -------------------------
@@ -773,20 +749,6 @@ __global__ __launch_bounds__(kBlock) void parameters_for_range_grid_kernel(const
       if (offset_out) store_any(offset_out, a.offset_dt, t, (double)offset);
     }
   }
-}
-
-static RangeArgs make_range_args(int range_dt, int64_t ntiles, double num_bits, int symmetric, int allow_one_sided, int scale_dt, int offset_dt,
-                                 int round_offset) {
-  RangeArgs a;
-  a.range_dt = range_dt; a.scale_dt = scale_dt; a.offset_dt = offset_dt;
-  a.ntiles = ntiles;
-  a.symmetric = symmetric; a.allow_one_sided = allow_one_sided; a.round_offset = round_offset;
-  const double int_min = -pow(2.0, num_bits - 1.0), int_max = -int_min - 1.0;
-  a.abs_int_min = (float)fabs(int_min);
-  a.abs_int_max = (float)fabs(int_max);
-  a.num_steps = (float)(pow(2.0, num_bits) - 1.0);
-  a.int_min = (float)int_min;
-  return a;
 }
 
 template <typename R>

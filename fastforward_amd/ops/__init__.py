@@ -28,7 +28,7 @@ from fastforward_amd.ops.static import (  # noqa: F401
     _quantize_by_tile_backward_composite, dequantize_by_tile, quantize_by_tile, quantize_by_tile_backward, quantize_by_tile_unless_same, quantize_dynamic_by_tile, quantize_rows_batch, quantize_rows_rowsum,
 )
 from fastforward_amd.ops.packing import (  # noqa: F401
-    _pack_gguf, gptq_block, grid_sqerror_by_tile, pack_int4, pack_q4_0_blocks, pack_q8_0_blocks, quantize_pack_int4, unpack_dequantize_int4, unpack_int4,
+    _pack_gguf, gptq_block, gptq_block_grid, grid_sqerror_by_tile, pack_int4, pack_q4_0_blocks, pack_q8_0_blocks, quantize_pack_int4, unpack_dequantize_int4, unpack_int4,
 )
 from fastforward_amd.ops.reductions import (  # noqa: F401
     _running_minmax_step, minmax_by_tile, parameters_for_range, running_minmax_quantize, running_minmax_step,
@@ -59,6 +59,7 @@ __all__ = [
     "quantize_pack_int4",
     "unpack_dequantize_int4",
     "gptq_block",
+    "gptq_block_grid",
     "grid_sqerror_by_tile",
     "linear_w8a8",
     "linear_w8a8_multi",

@@ -1,5 +1,5 @@
 """A7 and the callers either side of it: int4 packing in the GGUF nibble order (reference export/stages/gguf/_packing.py:23-98) alone and
-fused with A1 / A2, the GGUF block writers, the GPTQ column loop (quantization/gptq.py:101-235) and the grid estimator's error pass
+fused with A1 / A2, the GGUF block writers, the GPTQ column loop (quantization/gptq.py:101-235, per-row and grid parameters) and the grid estimator's error pass
 (range_setting/min_error.py:171-231)."""
 
 from __future__ import annotations
@@ -66,6 +66,57 @@ def gptq_block(
             _ptr(weights), _ptr(quantized), _ptr(errors), rows, weights.shape[1], int(col0), int(block_cols),
             _ptr(hessian_inverse), hessian_inverse.shape[1], _ptr(sc), sc.numel(), _ptr(of), of.numel() if of is not None else 0,
             float(num_bits), stream,
+        )
+    )
+    return True
+
+
+def gptq_block_grid(
+    weights: torch.Tensor,
+    quantized: torch.Tensor,
+    errors: torch.Tensor,
+    col0: int,
+    block_cols: int,
+    hessian_inverse: torch.Tensor,
+    scale: torch.Tensor,
+    offset: torch.Tensor | None,
+    tile: tuple[int, int],
+    num_bits: float,
+    column_order: torch.Tensor | None = None,
+    refit: bool = False,
+    symmetric: bool = True,
+    allow_one_sided: bool = True,
+) -> bool:
+    """:func:`gptq_block` for parameters that change along the columns: `scale` / `offset` are the quantizer's
+    ``[rows / tile[0], columns / tile[1]]`` grid, column ``c`` of `weights` uses grid column ``column_order[c] // tile[1]``
+    (int64 device tensor; None = identity). With `refit` the groups that start in the block are re-estimated first, in place,
+    from `weights` (reference quantization/gptq.py:91-99). Returns False when the kernel does not cover the call (the library
+    lacks the entry point, host tensors, non-fp32 or non-contiguous tensors, more than 128 columns)."""
+    if _base._native.library().ffq_gptq_block_grid is None or _base._host_route(weights):
+        return False
+    params = (scale,) if offset is None else (scale, offset)
+    tensors = (weights, quantized, errors, hessian_inverse, *params)
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors) or block_cols > 128:
+        return False
+    if weights.dim() != 2 or hessian_inverse.dim() != 2 or not (weights.shape == quantized.shape == errors.shape):
+        return False
+    rows, cols = weights.shape
+    if hessian_inverse.shape[0] < col0 + block_cols:
+        return False
+    groups = (rows // tile[0]) * (cols // tile[1])
+    if any(t.numel() != groups for t in params):
+        return False
+    order = None
+    if column_order is not None:
+        if column_order.dtype != torch.int64 or column_order.numel() != cols:
+            return False
+        order = column_order.contiguous()
+    lib, stream = _base._prepare(weights, quantized, errors, hessian_inverse, scale, offset, order)
+    lib.check(
+        lib.ffq_gptq_block_grid(
+            _ptr(weights), _ptr(quantized), _ptr(errors), rows, cols, int(col0), int(block_cols), _ptr(hessian_inverse),
+            hessian_inverse.shape[1], _ptr(scale), _ptr(offset), int(tile[0]), int(tile[1]), _ptr(order), int(refit),
+            int(symmetric), int(allow_one_sided), float(num_bits), stream,
         )
     )
     return True

@@ -12,9 +12,14 @@ organisation below is this package's own:
 * ``_ParameterGrid``    — EVERY granularity as one rule: with ``(tr, tc) = granularity.tile_size(weight.shape)`` the
   parameters form a ``[rows / tr, columns / tc]`` grid, and column ``c`` sees ``grid[:, c // tc]`` repeated ``tr`` times
   (the reference enumerates the granularities one by one, :149-235);
-* ``_Sweep``            — the working matrices and the two ways to process a block of columns: one launch of the HIP
-  kernel when a row's parameters do not depend on the column (per-tensor / per-output-channel: rows are independent, a
-  lane owns a row), else the column-by-column loop built from this package's quantize / dequantize ops.
+* ``_Sweep``            — the working matrices and the three ways to process a block of columns:
+  - one launch of ``ffq_gptq_block`` when a row's parameters do not depend on the column (per-tensor / per-output-channel:
+    rows are independent, a lane owns a row);
+  - else one launch of ``ffq_gptq_block_grid``, which reads each column's parameters from the grid (grouped, per-tile and
+    per-input-channel quantizers, act-order or not) and, for grouped quantizers without act-order, first re-estimates the
+    groups that start in the block (a second launch before it on the stream: no host round trip per column or group);
+  - the column-by-column loop built from this package's quantize / dequantize ops: ``fused=False``, or a call neither
+    kernel covers (e.g. a library without the grid entry point).
 """
 
 from __future__ import annotations
@@ -125,15 +130,29 @@ class _ParameterGrid:
 class _Sweep:
     """Working state of one layer: permuted weights, their snapped values, the scaled errors, the factor ``U``."""
 
-    def __init__(self, weights: torch.Tensor, factor: torch.Tensor, order: torch.Tensor, grid: _ParameterGrid, refit_groups: bool) -> None:
+    def __init__(
+        self, weights: torch.Tensor, factor: torch.Tensor, order: torch.Tensor, grid: _ParameterGrid, refit_groups: bool, permuted: bool
+    ) -> None:
         self.weights, self.factor, self.order, self.grid = weights, factor, order, grid
         self.snapped = torch.zeros_like(weights)
         self.errors = torch.zeros_like(weights)
         self.refit_groups = refit_groups
+        self.permuted = permuted
+        self.refitted_on_device = False  # the grid kernel wrote the parameters through their pointers: _version has not moved
 
     def block_in_one_launch(self, start: int, width: int) -> bool:
         q = self.grid.quantizer
         return ops.gptq_block(self.weights, self.snapped, self.errors, start, width, self.factor, q.scale, q.offset, q.num_bits)
+
+    def block_on_grid(self, start: int, width: int) -> bool:
+        q, grid = self.grid.quantizer, self.grid
+        done = ops.gptq_block_grid(
+            self.weights, self.snapped, self.errors, start, width, self.factor, q.scale.data, None if q.offset is None else q.offset.data,
+            (grid.tile_rows, grid.tile_cols), q.num_bits, column_order=self.order if self.permuted else None, refit=self.refit_groups,
+            symmetric=q.symmetric, allow_one_sided=q.allow_one_sided,
+        )
+        self.refitted_on_device |= done and self.refit_groups
+        return done
 
     def block_column_by_column(self, start: int, stop: int) -> None:
         local = self.weights[:, start:stop].clone()
@@ -161,7 +180,7 @@ def gptq(
     fused: bool = True,
 ) -> None:
     """Replace ``module.weight`` by GPTQ-optimised values on its weight quantizer's grid (reference signature :24-32;
-    ``fused=False`` forces the column loop where the block kernel would apply)."""
+    ``fused=False`` forces the column loop where a kernel would apply)."""
     quantizer = module.weight_quantizer
     if not isinstance(quantizer, ff.nn.LinearQuantizer):
         raise ValueError(f"weight_quantizer must be a LinearQuantizer, got {type(quantizer).__name__}.")
@@ -181,13 +200,21 @@ def gptq(
     factor = _upper_factor_of_inverse(hessian[order][:, order], perc_damp).contiguous()
 
     grouped = isinstance(quantizer.granularity, (granularities.PerBlock, granularities.PerTile))
-    sweep = _Sweep(weights, factor, order, grid, refit_groups=grouped and grid.col_groups > 1 and not actorder)
+    sweep = _Sweep(weights, factor, order, grid, refit_groups=grouped and grid.col_groups > 1 and not actorder, permuted=actorder)
     kernel_applies = fused and grid.column_independent and grid.tile_rows in (1, shape[0]) and block_size <= 128 and quantizer.scale.dtype == torch.float32
     for start in range(0, columns, block_size):
         stop = min(start + block_size, columns)
-        if not (kernel_applies and sweep.block_in_one_launch(start, stop - start)):
+        if kernel_applies:
+            done = sweep.block_in_one_launch(start, stop - start)
+        else:
+            done = fused and sweep.block_on_grid(start, stop - start)
+        if not done:
             sweep.block_column_by_column(start, stop)
         sweep.push_errors_right(start, stop)
+    if sweep.refitted_on_device:  # code caches key on the parameters' version counters (llama.py), as after refit_group's writes
+        for refitted in (quantizer.scale, quantizer.offset):
+            if refitted is not None:
+                torch.autograd.graph.increment_version(refitted)
 
     back = torch.argsort(order)
     with torch.no_grad():  # an in-place write autograd sees (the reference: module.weight.copy_): every cache keyed on

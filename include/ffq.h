@@ -558,6 +558,23 @@ int ffq_gptq_block(float* weights, float* quantized, float* errors, int64_t rows
                    int64_t scale_numel, const float* offset, int64_t offset_numel, double num_bits, void* stream);
 
 /*
+ * The same inner loop for weight quantizers whose parameters change along the columns (PerBlock, PerTile, PerChannel(1)), with
+ * or without act-order. weights / quantized / errors are [rows, cols] fp32; scale / offset (offset nullable) are the parameter
+ * grid [rows / tile_rows, cols / tile_cols]: column c of `weights` is column column_order[c] of the weight the parameters describe
+ * (column_order: int64 [cols] on the device, NULL = identity), and row r of it uses grid entry
+ * [r / tile_rows, column_order[c] / tile_cols]. With `refit` set, every column group whose first column lies in
+ * [col0, col0 + block_cols) is re-estimated first from weights[:, group's columns] as they stand (gptq(), :91-99): min / max of
+ * each grid entry's tile, then parameters_for_range with one one-sided decision per group (symmetric, allow_one_sided,
+ * num_bits as the quantizer's), written into scale and, when given, offset. Results equal the column loop bit for bit.
+ * block_cols <= 128 (else FFQ_ERR_DTYPE); tiles must divide the weight (FFQ_ERR_TILE_DIVIDE); every check runs before the
+ * first launch; rows == 0 or block_cols == 0 is a no-op.
+ */
+int ffq_gptq_block_grid(float* weights, float* quantized, float* errors, int64_t rows, int64_t cols, int64_t col0,
+                        int64_t block_cols, const float* hinv, int64_t hinv_stride, float* scale, float* offset,
+                        int64_t tile_rows, int64_t tile_cols, const int64_t* column_order, int refit, int symmetric,
+                        int allow_one_sided, double num_bits, void* stream);
+
+/*
  * Weight codes and their row sums in one pass (ABI version 3). A6's zero-point term needs sum_k wq[n, k] for every weight row
  * whenever the activation quantizer has an offset; with the reference's semantics the weight is re-quantized on every
  * forward (nn/linear.py:34), so the sums change with it. ffq_quantize_rows_rowsum is A1 for a [rows, cols] weight with one
