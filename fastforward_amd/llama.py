@@ -637,8 +637,9 @@ class QuantizedLlamaModel(QuantizedModule, LlamaModel):
         return self.lm_head(hidden_states) if logits else hidden_states
 
 
-class QuantizedEmbedding(QuantizedModule, torch.nn.Embedding):
-    """Embedding stays float in the Llama recipe (not matched by the quantizer queries)."""
+class QuantizedEmbedding(QuantizedModule, torch.nn.Embedding, include_in_module_map=False):
+    """Embedding stays float in the Llama recipe (not matched by the quantizer queries). Out of the global module map, where
+    ``torch.nn.Embedding`` maps to the generic ``ff.nn.QuantizedEmbedding``; :func:`quantize_llama` asks for this class."""
 
 
 # ---- recipe ------------------------------------------------------------------------------------------
@@ -685,7 +686,7 @@ def quantize_llama(
     """``ff.quantize_model`` + the quick-start W{w_bits}A{a_bits} recipe. Quantizers are created on the
     model's device; ranges are uninitialised until a calibration pass (``ff.estimate_ranges``)."""
     device = next(model.parameters()).device
-    ff.quantize_model(model)
+    ff.quantize_model(model, extra_conversion={torch.nn.Embedding: QuantizedEmbedding})
     for _, linear in decoder_linears(model):
         if w_bits is not None:
             linear.weight_quantizer = ff.nn.LinearQuantizer(

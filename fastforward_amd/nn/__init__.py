@@ -19,3 +19,8 @@ from fastforward_amd.nn.container import QuantizedModuleList as QuantizedModuleL
 from fastforward_amd.nn.container import QuantizedParameterDict as QuantizedParameterDict  # isort: skip
 from fastforward_amd.nn.container import QuantizedParameterList as QuantizedParameterList  # isort: skip
 from fastforward_amd.nn.container import QuantizedSequential as QuantizedSequential  # isort: skip
+from fastforward_amd.nn.normalization import QuantizedLayerNorm as QuantizedLayerNorm  # isort: skip
+from fastforward_amd.nn.embedding import QuantizedEmbedding as QuantizedEmbedding  # isort: skip
+from fastforward_amd.nn.activations import QuantizedActivation as QuantizedActivation  # isort: skip
+from fastforward_amd.nn.activations import QuantizedRelu as QuantizedRelu  # isort: skip
+from fastforward_amd.nn.activations import QuantizedSilu as QuantizedSilu  # isort: skip

@@ -1,11 +1,13 @@
-"""Quantized functional operators on the linear path: ``linear``, ``matmul``, ``mm``, ``bmm``.
+"""Quantized functional operators: the linear path (``linear``, ``matmul``, ``mm``, ``bmm``) and the generic modules' operators
+(``layer_norm``, ``embedding``, ``relu``, ``silu``).
 
 Reference: the generated ``ff.nn.functional.*`` (src/fastforward/_gen/operators.py:79-106 for
 ``linear``; matmul/mm/bmm follow the same template) and their fallbacks
 (src/fastforward/_gen/fallback.py:77-112, 699-798). Each operator is
 ``dispatch(name, **kwargs) or fallback`` — the dispatcher lookup is plug-in seam #2, where
-``fastforward_amd.fused_linear`` registers the int8-MFMA kernel. The other 49 generated operators of
-the reference are pure float fallbacks and are out of scope.
+``fastforward_amd.fused_linear`` registers the int8-MFMA kernel and ``fastforward_amd.fused_modules`` the one-pass LayerNorm /
+Embedding / ReLU / SiLU kernels (fallbacks: _gen/fallback.py:296-317, 616-652, 655-696, 1348-1369). The other generated
+operators of the reference are pure float fallbacks and are out of scope.
 """
 
 from __future__ import annotations
@@ -22,7 +24,7 @@ from fastforward_amd.quantized_tensor import QuantizedTensor
 if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
-__all__ = ["linear", "matmul", "mm", "bmm"]
+__all__ = ["linear", "matmul", "mm", "bmm", "layer_norm", "embedding", "relu", "silu"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -102,3 +104,58 @@ def bmm(input: torch.Tensor, mat2: torch.Tensor, *, output_quantizer: Optional["
     if kernel:
         return kernel(**kwargs)
     return _fallback_bmm(input, mat2, output_quantizer=output_quantizer, strict_quantization=kwargs["strict_quantization"])
+
+
+# ---- the generic modules' operators (reference _gen/operators.py: dispatch(op, **kwargs) or the generated fallback) -------------
+def _fallback_layer_norm(input: torch.Tensor, normalized_shape: tuple[int, ...], weight: torch.Tensor | None = None, bias: torch.Tensor | None = None, eps: float = 1e-5, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.layer_norm, optional output quantizer (reference fallback.py:655-696)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    if weight is not None:
+        weight = _dequantized("weight", weight, strict_quantization)
+    if bias is not None:
+        bias = _dequantized("bias", bias, strict_quantization, required=False)
+    output = torch.nn.functional.layer_norm(input=input, normalized_shape=normalized_shape, weight=weight, bias=bias, eps=eps)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _fallback_embedding(input: torch.Tensor, weight: torch.Tensor, padding_idx: int | None = None, max_norm: float | None = None, norm_type: float = 2.0, scale_grad_by_freq: bool = False, sparse: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize the table, F.embedding, optional output quantizer (reference fallback.py:616-652)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    weight = _dequantized("weight", weight, strict_quantization)
+    output = torch.nn.functional.embedding(input=input, weight=weight, padding_idx=padding_idx, max_norm=max_norm, norm_type=norm_type, scale_grad_by_freq=scale_grad_by_freq, sparse=sparse)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _unary_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., torch.Tensor]:
+    def fallback(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+        _check_output_quantizer(output_quantizer, strict_quantization)
+        input = _dequantized("input", input, strict_quantization)
+        output = torch_op(input=input)
+        return output_quantizer(output) if output_quantizer is not None else output
+
+    return fallback
+
+
+_fallback_relu = _unary_fallback(torch.nn.functional.relu)  # fallback.py:296-317
+_fallback_silu = _unary_fallback(torch.nn.functional.silu)  # fallback.py:1348-1369
+
+
+def layer_norm(input: torch.Tensor, normalized_shape: tuple[int, ...], weight: torch.Tensor | None = None, bias: torch.Tensor | None = None, eps: float = 1e-5, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, normalized_shape=normalized_shape, weight=weight, bias=bias, eps=eps, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("layer_norm", **kwargs) or _fallback_layer_norm)(**kwargs)
+
+
+def embedding(input: torch.Tensor, weight: torch.Tensor, padding_idx: int | None = None, max_norm: float | None = None, norm_type: float = 2.0, scale_grad_by_freq: bool = False, sparse: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, weight=weight, padding_idx=padding_idx, max_norm=max_norm, norm_type=norm_type, scale_grad_by_freq=scale_grad_by_freq, sparse=sparse, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("embedding", **kwargs) or _fallback_embedding)(**kwargs)
+
+
+def relu(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("relu", **kwargs) or _fallback_relu)(**kwargs)
+
+
+def silu(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("silu", **kwargs) or _fallback_silu)(**kwargs)

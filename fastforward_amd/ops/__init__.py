@@ -11,7 +11,8 @@ the library (outputs and scratch are torch allocations), legal under hipGraph ca
 
 The package is split by family (round 6; one 1,700-line module before): ``static`` (the four registry operators and the row-batched
 forms of A1), ``reductions`` (A4 / A5), ``packing`` (A7, GGUF, GPTQ, the grid estimator), ``gemm`` (A6 on int8 codes), ``wq`` (A6 with a
-quantized weight and a plain input), ``producers`` (RMSNorm / SiLU*up / rotary / attention with A1 fused), ``registry`` (the torch operator
+quantized weight and a plain input), ``producers`` (RMSNorm / SiLU*up / rotary / attention with A1 fused), ``modules``
+(LayerNorm / Embedding / ReLU / SiLU with A2 and A1 fused), ``registry`` (the torch operator
 library and the C++ extension), ``_base`` (device check, tags, scratch). Every public name is re-exported here: ``ops.linear_wq`` etc.
 """
 
@@ -41,6 +42,9 @@ from fastforward_amd.ops.wq import (  # noqa: F401
 )
 from fastforward_amd.ops.producers import (  # noqa: F401
     _fan, add_rmsnorm_quantize, attention, rope_, silu_mul_quantize,
+)
+from fastforward_amd.ops.modules import (  # noqa: F401
+    embedding_quantize, layer_norm_quantize, pointwise_quantize,
 )
 from fastforward_amd.ops.registry import NATIVE_DISPATCH, TORCH_EXTENSION_PATH, _LIBRARY  # noqa: F401,E402
 
@@ -73,6 +77,9 @@ __all__ = [
     "quantize_rows_rowsum",
     "quantize_rows_batch",
     "attention",
+    "layer_norm_quantize",
+    "embedding_quantize",
+    "pointwise_quantize",
     "FLAG_INF",
     "FLAG_NAN",
 ]

@@ -414,6 +414,46 @@ int ffq_silu_mul_quantize(const void* gate, const void* up, int dt, int64_t nume
                           const ffq_fanout* fan, void* stream);
 
 /*
+ * LayerNorm + A1 — QuantizedLayerNorm (reference nn/normalization.py) through fallback.layer_norm (_gen/fallback.py:655-696):
+ *   v = x                                     (x_scale == NULL: x is [rows, cols] of `dt`)
+ *   v = dt((q + round(o)) * s)                (x_scale != NULL: codes of x_dt = int8 or `dt`; fp32 parameters, one pair for the
+ *                                              tensor or, x_per_row != 0, one per row: A2 exactly as ffq_dequantize_by_tile)
+ *   mean = sum(v) / cols, var = sum((v - mean)^2) / cols          (fp32, biased)
+ *   z = dt(weight * (rsqrt(var + eps) * (v - mean)) + bias)      (fp32, the multiply-add fused, one rounding to dt, as
+ *                                                                   F.layer_norm; a missing weight / bias drops its step)
+ *   codes_j = A1(z; scale_j, offset_j)                             (ffq_fanout)
+ * dt is bf16 or fp16; weight / bias are nullable [cols] vectors of dt; out ([rows, cols] of dt) is nullable. The summation order
+ * of mean and var is the kernel's own: z can differ from ATen's by a bf16 ulp on rare elements; the codes are exactly A1 of the
+ * z this call produces. cols % 8 == 0, cols <= 16384.
+ */
+int ffq_layer_norm_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int x_per_row,
+                            const void* weight, const void* bias, int dt, int64_t rows, int64_t cols, double eps,
+                            void* out, const ffq_fanout* fan, void* stream);
+
+/*
+ * Embedding gather + A2 + A1 — QuantizedEmbedding (reference nn/embedding.py) through fallback.embedding (_gen/fallback.py:616-652):
+ *   z[t, d] = dt((table[ids[t], d] + round(o)) * s)      codes_j = A1(z; scale_j, offset_j)
+ * ids: n_ids int64 or int32 (ids_dt); table: [V, D] codes of table_dt = int8 or `dt` (bf16 / fp16). fp32 parameters on the
+ * grid [per_row ? V : 1, D / group]: per tensor (0, D), PerChannel(0) (1, D), PerBlock tile (1, G) (1, G; G % 8 == 0) or
+ * PerChannel(1) (0, 1). out ([n_ids, D] of dt) is nullable. Bit for bit the A2 of the whole table followed by F.embedding.
+ * An id outside [0, V) reads nothing: its row of z is zeros and atomicMin(bad_id, t) records the position (the caller sets
+ * *bad_id to INT32_MAX before the call). D % 8 == 0.
+ */
+int ffq_embedding_quantize(const void* ids, int ids_dt, int64_t n_ids, const void* table, int table_dt, int64_t V, int64_t D,
+                           const float* scale, const float* offset, int per_row, int64_t group, int dt,
+                           void* out, const ffq_fanout* fan, int32_t* bad_id, void* stream);
+
+/*
+ * ReLU / SiLU + A1 — QuantizedRelu / QuantizedSilu (reference nn/activations.py) through fallback.relu / fallback.silu
+ * (_gen/fallback.py:296-317, 1348-1369):   z = dt(op(v)),  codes_j = A1(z; scale_j, offset_j)
+ * op 0: relu(v) = NaN ? v : max(v, 0);  op 1: silu(v) = v / (1 + exp(-v)) in fp32 (ffq_silu.h; equal to ATen on all bf16 values).
+ * v as in ffq_layer_norm_quantize: plain `dt`, or codes with one parameter pair (param_run == 0) or one per run of param_run
+ * elements (per-row parameters). out is nullable. numel % 8 == 0 (and param_run % 8 == 0).
+ */
+int ffq_pointwise_quantize(int op, const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_run,
+                           int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
+
+/*
  * Rotary position embedding in place — attention.py:20-41 (apply_rotary_pos_emb):
  *   out = bf16(bf16(v * cos) + bf16(rotate_half(v) * sin)),  rotate_half(v) = cat(-v[D/2:], v[:D/2])
  * q: [tokens, q_heads, head_dim], k: [tokens, k_heads, head_dim] as they leave the projections;
