@@ -33,5 +33,6 @@ from fastforward_amd.overrides import enable_quantization as enable_quantization
 from fastforward_amd.range_setting import estimate_ranges as estimate_ranges  # isort: skip
 import fastforward_amd.fused_linear  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_modules  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_conv  # noqa: E402,F401  isort: skip
 
 __version__ = "0.1.0"

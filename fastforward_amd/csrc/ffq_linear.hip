@@ -24,6 +24,7 @@
 #include "ffq_affine.h"
 #include "ffq_common.h"
 #include "ffq_vec.h"
+#include "ffq_epilogue.h"
 #include "ffq_extrema.h"
 #include "ffq_silu.h"
 
@@ -79,13 +80,6 @@ struct LinearArgs {
   void* seg_out[2];
 };
 
-// The value the linear would have returned in dtype `y_dt` (one rounding), as fp32
-__device__ __forceinline__ float round_to_dt(float y, int y_dt) {
-  if (y_dt == FFQ_BF16) return bf16_bits_to_f32(f32_to_bf16_bits(y));
-  if (y_dt == FFQ_F16) return (float)(_Float16)y;
-  return y;
-}
-
 __device__ __forceinline__ uint32_t swizzled(uint32_t row, uint32_t slot) {
   return row * BK + ((slot ^ ((row >> 2) & 3u)) << 4);
 }
@@ -96,13 +90,6 @@ __device__ __forceinline__ u32x4 load_slot(const int8_t* base, int row, int rows
   if (row < rows && kbyte < K) v = *reinterpret_cast<const u32x4*>(base + (size_t)row * K + kbyte);
   return v;
 }
-
-template <typename TOut>
-__device__ __forceinline__ void store_out(TOut* p, float v);
-template <> __device__ __forceinline__ void store_out<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void store_out<bf16_t>(bf16_t* p, float v) { *p = from_f32<bf16_t>(v); }
-template <> __device__ __forceinline__ void store_out<f16_t>(f16_t* p, float v) { *p = from_f32<f16_t>(v); }
-template <> __device__ __forceinline__ void store_out<int8_t>(int8_t* p, float v) { *p = from_f32<int8_t>(v); }
 
 // -------------------------------------------------------------------------------------------------
 // The tail kernel: block tile 128 x 128 x 64, 4 wavefronts (2 x 2), each owning 64 x 64 = 2 x 2 tiles of

@@ -24,3 +24,6 @@ from fastforward_amd.nn.embedding import QuantizedEmbedding as QuantizedEmbeddin
 from fastforward_amd.nn.activations import QuantizedActivation as QuantizedActivation  # isort: skip
 from fastforward_amd.nn.activations import QuantizedRelu as QuantizedRelu  # isort: skip
 from fastforward_amd.nn.activations import QuantizedSilu as QuantizedSilu  # isort: skip
+from fastforward_amd.nn.conv import QuantizedConv1d as QuantizedConv1d  # isort: skip
+from fastforward_amd.nn.conv import QuantizedConv2d as QuantizedConv2d  # isort: skip
+from fastforward_amd.nn.conv import quantized_conv_modules as quantized_conv_modules  # isort: skip

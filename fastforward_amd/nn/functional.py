@@ -1,12 +1,13 @@
-"""Quantized functional operators: the linear path (``linear``, ``matmul``, ``mm``, ``bmm``) and the generic modules' operators
-(``layer_norm``, ``embedding``, ``relu``, ``silu``).
+"""Quantized functional operators: the linear path (``linear``, ``matmul``, ``mm``, ``bmm``), the convolutions (``conv1d``,
+``conv2d``) and the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``).
 
 Reference: the generated ``ff.nn.functional.*`` (src/fastforward/_gen/operators.py:79-106 for
 ``linear``; matmul/mm/bmm follow the same template) and their fallbacks
 (src/fastforward/_gen/fallback.py:77-112, 699-798). Each operator is
 ``dispatch(name, **kwargs) or fallback`` — the dispatcher lookup is plug-in seam #2, where
 ``fastforward_amd.fused_linear`` registers the int8-MFMA kernel and ``fastforward_amd.fused_modules`` the one-pass LayerNorm /
-Embedding / ReLU / SiLU kernels (fallbacks: _gen/fallback.py:296-317, 616-652, 655-696, 1348-1369). The other generated
+Embedding / ReLU / SiLU kernels (fallbacks: _gen/fallback.py:296-317, 616-652, 655-696, 1348-1369), and ``fastforward_amd.fused_conv``
+the int8 implicit-GEMM convolution (fallbacks: _gen/fallback.py:116-214). The other generated
 operators of the reference are pure float fallbacks and are out of scope.
 """
 
@@ -24,7 +25,7 @@ from fastforward_amd.quantized_tensor import QuantizedTensor
 if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
-__all__ = ["linear", "matmul", "mm", "bmm", "layer_norm", "embedding", "relu", "silu"]
+__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -159,3 +160,32 @@ def relu(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None,
 def silu(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("silu", **kwargs) or _fallback_silu)(**kwargs)
+
+
+# ---- the convolutions (reference _gen/operators.py:110-193: dispatch(op, **kwargs) or the generated fallback) ------------------
+def _conv_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., torch.Tensor]:
+    def fallback(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+        """Dequantize input / weight / bias, the float convolution, optional output quantizer (reference fallback.py:116-214)."""
+        _check_output_quantizer(output_quantizer, strict_quantization)
+        input = _dequantized("input", input, strict_quantization)
+        weight = _dequantized("weight", weight, strict_quantization)
+        if bias is not None:
+            bias = _dequantized("bias", bias, strict_quantization, required=False)
+        output = torch_op(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups)
+        return output_quantizer(output) if output_quantizer is not None else output
+
+    return fallback
+
+
+_fallback_conv1d = _conv_fallback(torch.nn.functional.conv1d)  # fallback.py:116-164
+_fallback_conv2d = _conv_fallback(torch.nn.functional.conv2d)  # fallback.py:167-214
+
+
+def conv1d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("conv1d", **kwargs) or _fallback_conv1d)(**kwargs)
+
+
+def conv2d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("conv2d", **kwargs) or _fallback_conv2d)(**kwargs)

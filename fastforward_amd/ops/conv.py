@@ -1,0 +1,95 @@
+"""The W8A8 convolution on int8 codes (csrc/ffq_conv.hip): what QuantizedConv2d / QuantizedConv1d run on the device instead of the
+reference's fallback.conv2d / fallback.conv1d (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer)."""
+
+from __future__ import annotations
+
+from typing import Sequence
+
+import torch
+
+from fastforward_amd.exceptions import BackendError
+from fastforward_amd.ops import _base
+from fastforward_amd.ops._base import _ptr, _tag, _workspace
+
+_REAL = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _pair(v: int | Sequence[int], what: str) -> tuple[int, int]:
+    if isinstance(v, int):
+        return v, v
+    t = tuple(int(e) for e in v)
+    if len(t) != 2:
+        raise RuntimeError(f"conv2d_w8a8: {what} is an int or a pair, got {v!r}")
+    return t  # type: ignore[return-value]
+
+
+def conv2d_w8a8(
+    x_codes: torch.Tensor,
+    w_codes: torch.Tensor,
+    x_scale: torch.Tensor,
+    x_offset: torch.Tensor | None,
+    w_scale: torch.Tensor,
+    w_offset: torch.Tensor | None,
+    bias: torch.Tensor | None = None,
+    stride: int | Sequence[int] = 1,
+    padding: int | Sequence[int] = 0,
+    dilation: int | Sequence[int] = 1,
+    out_dtype: torch.dtype = torch.bfloat16,
+    out_scale: torch.Tensor | None = None,
+    out_offset: torch.Tensor | None = None,
+    out_num_bits: float = 8.0,
+    requant_from: torch.dtype | None = None,
+) -> torch.Tensor:
+    """``F.conv2d`` (groups = 1) on int8 codes: `x_codes` [B, C, H, W] (contiguous, or channels-last with C % 16 == 0, which skips
+    the layout pass's input half), `w_codes` [OC, C, KH, KW]; fp32 parameters, one pair for the input and one for the weight or one
+    per output channel; integer `padding` (a pair, symmetric per side). Returns the contiguous NCHW [B, OC, OH, OW] result in
+    `out_dtype`: the exact integer contraction with the affine terms over the taps inside the image (include/ffq.h,
+    ffq_conv2d_w8a8). With `out_scale` (and optionally `out_offset`) the per-tensor output quantizer runs in the epilogue: the
+    result is rounded to `requant_from` (default bf16) and A1 writes int8 codes — exactly ``quantize_by_tile(conv2d_w8a8(...,
+    out_dtype=requant_from), out_scale, shape, bits, torch.int8, out_offset)``."""
+    if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
+        raise TypeError("conv2d_w8a8 expects int8 codes")
+    if x_codes.dim() != 4 or w_codes.dim() != 4:
+        raise RuntimeError(f"conv2d_w8a8: input [B, C, H, W] and weight [OC, C, KH, KW], got {tuple(x_codes.shape)} and {tuple(w_codes.shape)}")
+    B, C, H, W = x_codes.shape
+    OC, Cw, KH, KW = w_codes.shape
+    if Cw != C:
+        raise RuntimeError(f"conv2d_w8a8: the weight has {Cw} input channels, the input {C} (groups > 1 is not built)")
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride, "stride"), _pair(padding, "padding"), _pair(dilation, "dilation")
+    nhwc = (not x_codes.is_contiguous()) and C % 16 == 0 and x_codes.is_contiguous(memory_format=torch.channels_last)
+    xc = x_codes.detach() if nhwc else x_codes.detach().contiguous()
+    wc = w_codes.detach().contiguous()
+
+    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
+        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
+
+    xs, xo, ws_, wo, os_, oo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(out_scale), f32(out_offset)
+    if xs.numel() != 1 or (xo is not None and xo.numel() != 1):
+        raise RuntimeError("conv2d_w8a8: the input has one parameter pair (per-tensor)")
+    if ws_.numel() not in (1, OC) or (wo is not None and wo.numel() != ws_.numel()):
+        raise RuntimeError(f"conv2d_w8a8: the weight has 1 or {OC} parameter pairs, got {ws_.numel()}")
+    if os_ is not None and (os_.numel() != 1 or (oo is not None and oo.numel() != 1)):
+        raise RuntimeError("conv2d_w8a8: the output quantizer is per tensor")
+    if os_ is None and out_dtype not in _REAL:
+        raise RuntimeError(f"conv2d_w8a8: a real-valued output is f32, bf16 or f16, got {out_dtype}")
+    bias_c = None if bias is None else bias.detach().reshape(-1).contiguous()
+    if bias_c is not None and (bias_c.numel() != OC or bias_c.dtype not in _REAL):
+        raise RuntimeError(f"conv2d_w8a8: the bias is [{OC}] of f32, bf16 or f16")
+    lib, stream = _base._prepare(xc, wc, xs, xo, ws_, wo, bias_c, os_, oo)
+    entry = getattr(lib, "ffq_conv2d_w8a8", None)
+    if entry is None:
+        raise BackendError("the loaded library does not export ffq_conv2d_w8a8 (a host library has no convolution kernel)")
+    OH = (H + 2 * ph - dh * (KH - 1) - 1) // sh + 1
+    OW = (W + 2 * pw - dw * (KW - 1) - 1) // sw + 1
+    out = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=torch.int8 if os_ is not None else out_dtype, device=xc.device)
+    nbytes = lib.ffq_conv2d_w8a8_workspace_bytes(B, C, H, W, OC, KH, KW, int(nhwc))
+    ws = _workspace(nbytes, xc.device)
+    y_dt = _tag(requant_from or torch.bfloat16) if os_ is not None else 0
+    lib.check(
+        entry(
+            _ptr(xc), int(nhwc), _ptr(wc), _ptr(xs), _ptr(xo), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
+            _ptr(bias_c), _tag(bias_c.dtype) if bias_c is not None else 0, _ptr(out), _tag(out.dtype), _ptr(os_), _ptr(oo),
+            float(out_num_bits), y_dt, B, C, H, W, OC, KH, KW, sh, sw, ph, pw, dh, dw, _ptr(ws), nbytes, stream,
+        )
+    )
+    return out

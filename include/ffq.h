@@ -454,6 +454,42 @@ int ffq_pointwise_quantize(int op, const void* x, int x_dt, const float* x_scale
                            int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
 
 /*
+ * W8A8 convolution — QuantizedConv2d / QuantizedConv1d (reference nn/conv.py) through fallback.conv2d / fallback.conv1d
+ * (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer). Integer codes in, an implicit GEMM on the
+ * int8 matrix cores, one fp32 epilogue per output element. For output (b, n, p), p = (oh, ow), V(p) = the taps (kh, kw) whose
+ * input pixel (oh * stride_h - pad_h + kh * dil_h, ow * stride_w - pad_w + kw * dil_w) lies inside the H x W image:
+ *   acc = sum_{t in V(p), c < C} xq[b,c,ih,iw] * wq[n,c,t]                                  (int32, exact)
+ *   rsx = sum_{t in V(p), c < C} xq[b,c,ih,iw]                                              (only with w_offset)
+ *   rsw = sum_{t in V(p)} sum_c wq[n,c,t]                                                    (only when rne(x_offset) != 0)
+ *   v = float(acc); v = v + ox * rsw; v = v + ow * rsx; v = v + (C * |V(p)|) * ox * ow      (fp32, left to right, no FMA)
+ *   y = (sx * sw[n']) * v  (+ bias[n])
+ * with ox / ow = rne(offset) as in A2 and n' = n if w_per_channel else 0. Padding: the reference pads the DEQUANTIZED input with
+ * 0.0, whose code -ox need not fit the container (after a ReLU it does not); out-of-image taps read code 0 and leave V(p), which is
+ * the same real-valued sum. Channels are padded to a multiple of 16 with code 0 internally (C = 3 stems are covered).
+ * Layout: xq is [B, C, H, W] contiguous, or (x_nhwc != 0, C % 16 == 0, 16-byte aligned) [B, H, W, C] — a channels-last tensor;
+ * wq is [OC, C, KH, KW] contiguous; out is [B, OC, OH, OW] contiguous (NCHW), OH = (H + 2 pad_h - dil_h (KH - 1) - 1) / stride_h + 1.
+ * Conv1d is this call with H = KH = 1. Parameters: x per tensor; w per tensor or per output channel; fp32; bias nullable
+ * (f32 / bf16 / f16, [OC]).
+ * If out_scale != NULL the output quantizer (per tensor) runs in the epilogue as in ffq_linear_w8a8: y rounded once to y_dt, then
+ * codes = clamp(rne(y / out_scale - rne(out_offset))) into out (out_dt must be int8) — bit-identical to ffq_quantize_by_tile on the
+ * tensor the call without out_scale writes in y_dt. Else out holds y in out_dt (f32 / bf16 / f16).
+ * Coverage: groups == 1 (the caller's), C * KH * KW <= 131072 (else FFQ_ERR_DTYPE: |acc| stays within int32), stride / dilation
+ * >= 1, padding >= 0, extents <= 2^24, B * OH * OW < 2^31. Every argument check runs before any launch.
+ * Workspace: ffq_conv2d_w8a8_workspace_bytes(...) bytes, 16-byte aligned — the NHWC input codes (none with x_nhwc), the reordered
+ * weight [OC, KH, KW, Cp] and the per-tap weight sums; less returns FFQ_ERR_WORKSPACE. Two launches (layout, GEMM) and a memset.
+ * Tolerance vs the reference's float convolution: the contraction is exact, so y differs from the float route only by the
+ * float route's own roundings (tests/test_conv_gpu.py checks within check_linear's tolerance and exactly against a float64
+ * accumulator).
+ */
+size_t ffq_conv2d_w8a8_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int x_nhwc);
+int ffq_conv2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, const float* x_scale, const float* x_offset,
+                    const float* w_scale, const float* w_offset, int w_per_channel, const void* bias, int bias_dt, void* out,
+                    int out_dt, const float* out_scale, const float* out_offset, double out_num_bits, int y_dt, int64_t B,
+                    int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t stride_h, int64_t stride_w,
+                    int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
+/*
  * Rotary position embedding in place — attention.py:20-41 (apply_rotary_pos_emb):
  *   out = bf16(bf16(v * cos) + bf16(rotate_half(v) * sin)),  rotate_half(v) = cat(-v[D/2:], v[:D/2])
  * q: [tokens, q_heads, head_dim], k: [tokens, k_heads, head_dim] as they leave the projections;
