@@ -34,5 +34,6 @@ from fastforward_amd.range_setting import estimate_ranges as estimate_ranges  # 
 import fastforward_amd.fused_linear  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_modules  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_conv  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_elementwise  # noqa: E402,F401  isort: skip
 
 __version__ = "0.1.0"

@@ -198,6 +198,9 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_layer_norm_quantize": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i64, _i64, _d, _vp, _fp, _vp]),
     "ffq_embedding_quantize": (_i, [_vp, _i, _i64, _vp, _i, _i64, _i64, _vp, _vp, _i, _i64, _i, _vp, _fp, _vp, _vp]),
     "ffq_pointwise_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i, _i64, _vp, _fp, _vp]),
+    "ffq_binary_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _i64, _i64, _d, _d, _i, _i64, _vp, _fp, _vp]),
+    "ffq_softmax_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i, _i64, _i64, _vp, _fp, _vp]),
+    "ffq_activation_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i, _i64, _vp, _fp, _vp]),
     "ffq_conv2d_w8a8_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i]),
     "ffq_conv2d_w8a8": (
         _i,
@@ -220,7 +223,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
 # Entry points only the HIP library must export: a host library (the CPU oracle) without one gets the attribute bound to None and
 # callers treat that as "not covered". Whether the symbol is there is the capability check (FFQ_ABI_VERSION does not move for them).
 DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_quantize", "ffq_embedding_quantize", "ffq_pointwise_quantize",
-                                         "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes"})
+                                         "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
+                                         "ffq_activation_quantize"})
 
 
 class FFQLibrary:

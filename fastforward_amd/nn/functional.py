@@ -1,5 +1,6 @@
 """Quantized functional operators: the linear path (``linear``, ``matmul``, ``mm``, ``bmm``), the convolutions (``conv1d``,
-``conv2d``) and the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``).
+``conv2d``), the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``) and the elementwise operators of a
+transformer block outside its linears (``add``, ``sub``, ``mul``, ``div``, ``softmax``, ``sigmoid``, ``gelu``).
 
 Reference: the generated ``ff.nn.functional.*`` (src/fastforward/_gen/operators.py:79-106 for
 ``linear``; matmul/mm/bmm follow the same template) and their fallbacks
@@ -7,8 +8,11 @@ Reference: the generated ``ff.nn.functional.*`` (src/fastforward/_gen/operators.
 ``dispatch(name, **kwargs) or fallback`` — the dispatcher lookup is plug-in seam #2, where
 ``fastforward_amd.fused_linear`` registers the int8-MFMA kernel and ``fastforward_amd.fused_modules`` the one-pass LayerNorm /
 Embedding / ReLU / SiLU kernels (fallbacks: _gen/fallback.py:296-317, 616-652, 655-696, 1348-1369), and ``fastforward_amd.fused_conv``
-the int8 implicit-GEMM convolution (fallbacks: _gen/fallback.py:116-214). The other generated
-operators of the reference are pure float fallbacks and are out of scope.
+the int8 implicit-GEMM convolution (fallbacks: _gen/fallback.py:116-214), and ``fastforward_amd.fused_elementwise`` the one-pass
+add / sub / mul / div, softmax, sigmoid and GELU kernels (fallbacks: _gen/fallback.py:269-293, 321-342, 801-955, 1373-1395).
+``mul`` of a per-tensor affine tensor by a Python number without an output quantizer is the reference's rescale of the scale
+(quantization/_linear_quantized_ops.py:126-171). The other generated operators of the reference are pure float fallbacks and are
+out of scope.
 """
 
 from __future__ import annotations
@@ -25,7 +29,8 @@ from fastforward_amd.quantized_tensor import QuantizedTensor
 if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
-__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu"]
+__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
+           "softmax", "sigmoid", "gelu"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -189,3 +194,74 @@ def conv1d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None 
 def conv2d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("conv2d", **kwargs) or _fallback_conv2d)(**kwargs)
+
+
+# ---- the elementwise operators (reference _gen/operators.py: dispatch(op, **kwargs) or the generated fallback) ---------------------
+def _arith_fallback(torch_op: Callable[..., torch.Tensor], with_alpha: bool) -> Callable[..., torch.Tensor]:
+    def fallback(input: torch.Tensor, other: torch.Tensor | float, alpha: float = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+        """Dequantize input / other, the torch op, optional output quantizer; a number `other` is no strict-mode error."""
+        _check_output_quantizer(output_quantizer, strict_quantization)
+        input = _dequantized("input", input, strict_quantization)
+        other = _dequantized("other", other, strict_quantization, required=isinstance(other, torch.Tensor))
+        output = torch_op(input=input, other=other, alpha=alpha) if with_alpha else torch_op(input=input, other=other)
+        return output_quantizer(output) if output_quantizer is not None else output
+
+    return fallback
+
+
+_fallback_add = _arith_fallback(torch.add, True)  # fallback.py:801-837
+_fallback_sub = _arith_fallback(torch.sub, True)  # fallback.py:840-876
+_fallback_mul = _arith_fallback(torch.mul, False)  # fallback.py:879-914
+_fallback_div = _arith_fallback(torch.div, False)  # fallback.py:917-952
+_fallback_sigmoid = _unary_fallback(torch.nn.functional.sigmoid)  # fallback.py:321-342
+
+
+def _fallback_softmax(input: torch.Tensor, dim: int, dtype: torch.dtype | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.softmax, optional output quantizer (reference fallback.py:269-293)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.softmax(input=input, dim=dim, dtype=dtype)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _fallback_gelu(input: torch.Tensor, approximate: str = "none", *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.gelu, optional output quantizer (reference fallback.py:1373-1395)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.gelu(input=input, approximate=approximate)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def add(input: torch.Tensor, other: torch.Tensor | float, alpha: float = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, other=other, alpha=alpha, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("add", **kwargs) or _fallback_add)(**kwargs)
+
+
+def sub(input: torch.Tensor, other: torch.Tensor | float, alpha: float = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, other=other, alpha=alpha, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("sub", **kwargs) or _fallback_sub)(**kwargs)
+
+
+def mul(input: torch.Tensor, other: torch.Tensor | float, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, other=other, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("mul", **kwargs) or _fallback_mul)(**kwargs)
+
+
+def div(input: torch.Tensor, other: torch.Tensor | float, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, other=other, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("div", **kwargs) or _fallback_div)(**kwargs)
+
+
+def softmax(input: torch.Tensor, dim: int, dtype: torch.dtype | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, dim=dim, dtype=dtype, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("softmax", **kwargs) or _fallback_softmax)(**kwargs)
+
+
+def sigmoid(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("sigmoid", **kwargs) or _fallback_sigmoid)(**kwargs)
+
+
+def gelu(input: torch.Tensor, approximate: str = "none", *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, approximate=approximate, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("gelu", **kwargs) or _fallback_gelu)(**kwargs)

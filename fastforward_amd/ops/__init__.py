@@ -12,7 +12,8 @@ the library (outputs and scratch are torch allocations), legal under hipGraph ca
 The package is split by family (round 6; one 1,700-line module before): ``static`` (the four registry operators and the row-batched
 forms of A1), ``reductions`` (A4 / A5), ``packing`` (A7, GGUF, GPTQ, the grid estimator), ``gemm`` (A6 on int8 codes), ``wq`` (A6 with a
 quantized weight and a plain input), ``producers`` (RMSNorm / SiLU*up / rotary / attention with A1 fused), ``modules``
-(LayerNorm / Embedding / ReLU / SiLU with A2 and A1 fused), ``conv`` (the W8A8 convolution), ``registry`` (the torch operator
+(LayerNorm / Embedding / ReLU / SiLU with A2 and A1 fused), ``conv`` (the W8A8 convolution), ``elementwise`` (add / sub / mul / div,
+softmax, sigmoid, GELU with A2 and A1 fused), ``registry`` (the torch operator
 library and the C++ extension), ``_base`` (device check, tags, scratch). Every public name is re-exported here: ``ops.linear_wq`` etc.
 """
 
@@ -47,6 +48,7 @@ from fastforward_amd.ops.modules import (  # noqa: F401
     embedding_quantize, layer_norm_quantize, pointwise_quantize,
 )
 from fastforward_amd.ops.conv import conv2d_w8a8  # noqa: F401
+from fastforward_amd.ops.elementwise import activation_quantize, binary_quantize, softmax_quantize  # noqa: F401
 from fastforward_amd.ops.registry import NATIVE_DISPATCH, TORCH_EXTENSION_PATH, _LIBRARY  # noqa: F401,E402
 
 __all__ = [
@@ -82,6 +84,9 @@ __all__ = [
     "embedding_quantize",
     "pointwise_quantize",
     "conv2d_w8a8",
+    "binary_quantize",
+    "softmax_quantize",
+    "activation_quantize",
     "FLAG_INF",
     "FLAG_NAN",
 ]

@@ -3,6 +3,7 @@
 Subset of src/fastforward/quantization/_linear_quantized_ops.py needed on the Llama linear path
 (SURVEY §2): ``contiguous`` (:94-96) for any quantized tensor and ``view`` / ``view_as`` /
 ``reshape`` / ``transpose`` for per-tensor affine tensors (:99-123). They only move metadata.
+So does ``mul`` by a Python number (:126-171): the same codes with ``scale * other``.
 """
 
 from __future__ import annotations
@@ -70,3 +71,43 @@ def reshape(input: QuantizedTensor, *args: Any) -> QuantizedTensor:
 @register("transpose", affine_per_tensor_predicate)
 def transpose(input: QuantizedTensor, *args: Any) -> QuantizedTensor:
     return apply_and_reattach(lambda x: x.transpose(*args), input)
+
+
+# ---- mul by a Python number: a rescale of the parameters (reference :126-171) ------------------------------------------------------
+class _ScaleGradient(torch.autograd.Function):
+    """The identity on the raw codes, with the gradient scaled by `scalar` on the way back."""
+
+    @staticmethod
+    def forward(ctx: Any, input: torch.Tensor, scalar: float) -> torch.Tensor:
+        ctx.scalar = scalar
+        return input
+
+    @staticmethod
+    def backward(ctx: Any, grad: torch.Tensor) -> tuple[torch.Tensor, None]:
+        return grad * ctx.scalar, None
+
+
+def _is_scalar_multiply(input: Any = None, other: Any = None, *_args: Any, output_quantizer: Any = None, **kwargs: Any) -> bool:
+    """A per-tensor affine `input` times a Python number, without an output quantizer (or with a stub), as the reference's
+    predicate — but only for calls of ``ff.nn.functional.mul``, which pass ``strict_quantization``: ``qt * 2`` reaches the dispatcher
+    through ``QuantizedTensor.__torch_function__`` and keeps its dequantizing route."""
+    from fastforward_amd.nn.quantizer import QuantizerStub
+
+    if "strict_quantization" not in kwargs:
+        return False
+    if not isinstance(other, (int, float)) or isinstance(other, bool):
+        return False
+    if not _static_affine(input) or not isinstance(_granularity_of(input), granularities.PerTensor):
+        return False
+    return output_quantizer is None or isinstance(output_quantizer, QuantizerStub)
+
+
+scalar_multiply_predicate = Predicate(_is_scalar_multiply)
+
+
+@register("mul", scalar_multiply_predicate)
+def scalar_multiply(input: QuantizedTensor, other: float, *_args: Any, **_kwargs: Any) -> QuantizedTensor:
+    """``input * other`` of an affine quantized tensor: only the scale moves."""
+    params = input.quant_args()
+    scaled = _ScaleGradient.apply(input.raw_data, other)
+    return input.quantization_context.with_changes(scale=params.scale * other).attach(scaled)

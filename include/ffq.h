@@ -454,6 +454,43 @@ int ffq_pointwise_quantize(int op, const void* x, int x_dt, const float* x_scale
                            int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
 
 /*
+ * add / sub / mul / div + A1 — ff.nn.functional.add / sub / mul / div (reference _gen/fallback.py:801-955: A2 of the quantized
+ * operands, torch.add / sub / mul / div, the output quantizer):   z = dt(op(A, B)),  codes_j = A1(z; scale_j, offset_j)
+ * A and B as v in ffq_pointwise_quantize: plain `dt`, or codes (int8 or `dt`) with one parameter pair (param_run == 0) or one per
+ * run of param_run elements, each A2 rounded to dt. a holds numel elements. b holds b_numel elements: b_numel == numel (same
+ * shape), or a divisor of numel whose shape is a suffix of a's (element i reads b[i % b_numel]: a bias [D] against [B, S, D]);
+ * b == NULL takes float(scalar) instead (b_numel 0, no parameters). ATen's formulas in fp32, one rounding to dt:
+ *   op 0 add: fma(B, alpha, A);  op 1 sub: fma(B, -alpha, A)        (ATen's a + b * alpha, contracted as its kernel is);
+ *             a scalar B: A + float(scalar) * (+-alpha), the product rounded to fp32 first (ATen scales the scalar once)
+ *   op 2 mul: A * B;  op 3 div: A / B (IEEE quotient), by a scalar: A * float(1 / scalar) (ATen's reciprocal); alpha must be 1
+ * out is nullable. numel % 8 == 0, b_numel % 8 == 0 (and param_run % 8 == 0).
+ */
+int ffq_binary_quantize(int op, const void* a, int a_dt, const float* a_scale, const float* a_offset, int64_t a_param_run,
+                        const void* b, int b_dt, const float* b_scale, const float* b_offset, int64_t b_param_run, int64_t b_numel,
+                        double scalar, double alpha, int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
+
+/*
+ * softmax over the last dimension + A1 — ff.nn.functional.softmax(x, -1) (reference _gen/fallback.py:269-293):
+ *   v as in ffq_layer_norm_quantize (plain, or codes with per-tensor / per-row parameters);
+ *   m = max(v), e = exp(v - m), z = dt(e / sum(e))         (fp32; a row of -inf, or holding NaN or +inf, gives NaN as ATen)
+ *   codes_j = A1(z; scale_j, offset_j)
+ * The summation order of sum(e) is the kernel's own: z can differ from ATen's by one ulp on rare elements; the codes are exactly
+ * A1 of the z this call produces. out is nullable. cols % 8 == 0, cols <= 16384.
+ */
+int ffq_softmax_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int x_per_row, int dt,
+                         int64_t rows, int64_t cols, void* out, const ffq_fanout* fan, void* stream);
+
+/*
+ * sigmoid / GELU + A1 — ff.nn.functional.sigmoid / gelu (reference _gen/fallback.py:321-342, 1373-1395):  z = dt(op(v)),
+ * codes_j = A1(z; scale_j, offset_j), with ATen's fp32 formulas (expf / erff / tanhf):
+ *   op 0 sigmoid: 1 / (1 + exp(-v));   op 1 gelu: (v * 0.5) * (1 + erf(v * M_SQRT1_2));
+ *   op 2 gelu (approximate="tanh"): (0.5 * v) * (1 + tanh(kBeta * fma(0.044715, v^3, v))), kBeta = sqrt(2 / pi)
+ * v as in ffq_pointwise_quantize. out is nullable. numel % 8 == 0 (and param_run % 8 == 0).
+ */
+int ffq_activation_quantize(int op, const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_run,
+                            int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
+
+/*
  * W8A8 convolution — QuantizedConv2d / QuantizedConv1d (reference nn/conv.py) through fallback.conv2d / fallback.conv1d
  * (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer). Integer codes in, an implicit GEMM on the
  * int8 matrix cores, one fp32 epilogue per output element. For output (b, n, p), p = (oh, ow), V(p) = the taps (kh, kw) whose
