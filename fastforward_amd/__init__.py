@@ -11,8 +11,11 @@ from fastforward_amd import exceptions as exceptions
 from fastforward_amd import flags as flags
 from fastforward_amd.flags import export_mode as export_mode
 from fastforward_amd.flags import get_export_mode as get_export_mode
+from fastforward_amd.flags import get_sdpa_torch_fallback_allowed as get_sdpa_torch_fallback_allowed
 from fastforward_amd.flags import get_strict_quantization as get_strict_quantization
+from fastforward_amd.flags import sdpa_torch_fallback_allowed as sdpa_torch_fallback_allowed
 from fastforward_amd.flags import set_export_mode as set_export_mode
+from fastforward_amd.flags import set_sdpa_torch_fallback_allowed as set_sdpa_torch_fallback_allowed
 from fastforward_amd.flags import set_strict_quantization as set_strict_quantization
 from fastforward_amd.flags import strict_quantization as strict_quantization
 from fastforward_amd.quantized_tensor import QuantizedTensor as QuantizedTensor
@@ -25,6 +28,7 @@ from fastforward_amd.quantization.granularity import PerTensor as PerTensor  # i
 from fastforward_amd.quantization.granularity import PerTile as PerTile  # isort: skip
 import fastforward_amd.quantization._linear_quantized_ops  # noqa: E402,F401  isort: skip
 from fastforward_amd import nn as nn  # isort: skip
+from fastforward_amd.nn.sdpa import sdpa_upcast as sdpa_upcast  # isort: skip
 from fastforward_amd import range_setting as range_setting  # isort: skip
 from fastforward_amd import overrides as overrides  # isort: skip
 from fastforward_amd.nn.quantized_module import quantize_model as quantize_model  # isort: skip
@@ -35,5 +39,6 @@ import fastforward_amd.fused_linear  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_modules  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_conv  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_elementwise  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_sdpa  # noqa: E402,F401  isort: skip
 
 __version__ = "0.1.0"

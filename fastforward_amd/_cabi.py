@@ -136,6 +136,14 @@ class RowsBatch(ctypes.Structure):
     ]
 
 
+class SdpaQuantizer(ctypes.Structure):
+    """``ffq_sdpa_quantizer``: one of the eight quantizer slots of ``ffq_sdpa_quantize`` (scale NULL: inactive)."""
+
+    _fields_ = [("scale", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("num_bits", ctypes.c_double)]
+
+
+SDPA_QUANTIZERS = 8  # FFQ_SDPA_QUANTIZERS
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
@@ -201,6 +209,11 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_binary_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _i64, _i64, _d, _d, _i, _i64, _vp, _fp, _vp]),
     "ffq_softmax_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i, _i64, _i64, _vp, _fp, _vp]),
     "ffq_activation_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i, _i64, _vp, _fp, _vp]),
+    "ffq_sdpa_quantize": (
+        _i,
+        [_vp, _vp, _vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _vp, _i, _i,
+         ctypes.POINTER(_i64), _d, _d, ctypes.POINTER(SdpaQuantizer), _i, _vp, _vp, _vp, _vp],
+    ),
     "ffq_conv2d_w8a8_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i]),
     "ffq_conv2d_w8a8": (
         _i,
@@ -224,7 +237,7 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
 # callers treat that as "not covered". Whether the symbol is there is the capability check (FFQ_ABI_VERSION does not move for them).
 DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_quantize", "ffq_embedding_quantize", "ffq_pointwise_quantize",
                                          "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
-                                         "ffq_activation_quantize"})
+                                         "ffq_activation_quantize", "ffq_sdpa_quantize"})
 
 
 class FFQLibrary:

@@ -55,6 +55,11 @@ strict_quantization = set_strict_quantization
 set_export_mode, get_export_mode = _define("export_mode", False)
 export_mode = set_export_mode
 
+# reference flags.py:102-106: scaled_dot_product_attention may call torch's own SDPA when no quantizer is active (the value it
+# returns is the math path's either way: nn/sdpa.py)
+set_sdpa_torch_fallback_allowed, get_sdpa_torch_fallback_allowed = _define("sdpa_torch_fallback_allowed", False)
+sdpa_torch_fallback_allowed = set_sdpa_torch_fallback_allowed
+
 
 def context(flag: Callable[[bool], _Restore], value: bool) -> Callable[[Callable[_P, _T]], Callable[_P, _T]]:
     """Decorator: run the function with `flag` set to `value` (reference flags.py:61-81)."""

@@ -11,7 +11,9 @@ Embedding / ReLU / SiLU kernels (fallbacks: _gen/fallback.py:296-317, 616-652, 6
 the int8 implicit-GEMM convolution (fallbacks: _gen/fallback.py:116-214), and ``fastforward_amd.fused_elementwise`` the one-pass
 add / sub / mul / div, softmax, sigmoid and GELU kernels (fallbacks: _gen/fallback.py:269-293, 321-342, 801-955, 1373-1395).
 ``mul`` of a per-tensor affine tensor by a Python number without an output quantizer is the reference's rescale of the scale
-(quantization/_linear_quantized_ops.py:126-171). The other generated operators of the reference are pure float fallbacks and are
+(quantization/_linear_quantized_ops.py:126-171). ``dropout`` follows fallback.py:1399-1423 with no kernel of its own, and
+``scaled_dot_product_attention`` is the reference's custom operator (nn/sdpa.py; ``fastforward_amd.fused_sdpa`` registers its
+kernel). The other generated operators of the reference are pure float fallbacks and are
 out of scope.
 """
 
@@ -30,7 +32,7 @@ if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
 __all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
-           "softmax", "sigmoid", "gelu"]
+           "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -265,3 +267,19 @@ def sigmoid(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = No
 def gelu(input: torch.Tensor, approximate: str = "none", *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, approximate=approximate, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("gelu", **kwargs) or _fallback_gelu)(**kwargs)
+
+
+def _fallback_dropout(input: torch.Tensor, p: float = 0.5, training: bool = True, inplace: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.dropout, optional output quantizer (reference fallback.py:1399-1423)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.dropout(input=input, p=p, training=training, inplace=inplace)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def dropout(input: torch.Tensor, p: float = 0.5, training: bool = True, inplace: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, p=p, training=training, inplace=inplace, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("dropout", **kwargs) or _fallback_dropout)(**kwargs)
+
+
+from fastforward_amd.nn.sdpa import scaled_dot_product_attention  # noqa: E402  (nn/sdpa.py calls back into this module)

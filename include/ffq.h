@@ -491,6 +491,41 @@ int ffq_activation_quantize(int op, const void* x, int x_dt, const float* x_scal
                             int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
 
 /*
+ * Quantized scaled_dot_product_attention — ff.nn.functional.scaled_dot_product_attention (reference
+ * nn/functional/custom/sdpa.py:116-285: fp32 upcast, q * sqrt(scale) -> A1, k^T * sqrt(scale) -> A1, matmul -> A1, + bias (mask
+ * -> A1) -> A1, safe softmax -> A1, dropout (p = 0) -> A1, matmul -> A1) in one launch, no [L, S] matrix in memory.
+ * q [B, q_heads, L, E], k [B, kv_heads, S, E], v [B, kv_heads, S, E] in `dt` (bf16 / fp16), last dimension contiguous and
+ * 16-byte aligned rows; strides[9] = the element strides of (batch, head, row) of q, k, v (multiples of 8). Query head h reads
+ * kv head h / (q_heads / kv_heads). deq_scale[3] / deq_offset[3]: per-tensor parameters when q / k / v hold codes (in `dt`,
+ * dequantized to `dt` as A2 does), scale NULL for plain values. E in {64, 128}; any L, S >= 1.
+ * mask_kind 0: none, 1: causal (top-left tril), 2: bool mask, 3: float mask (mask_dt f32 / bf16 / f16) read at
+ * mask[b * ms[0] + h * ms[1] + l * ms[2] + s * ms[3]] (ms = the strides of the mask expanded to [B, q_heads, L, S]).
+ * quantizers[8], in the reference's keyword order: scores, mask, masked scores, weights, scaled query, scaled key, dropout,
+ * output; scale NULL = inactive, else one fp32 scale, nullable fp32 offset, integral num_bits in 1..8. All elementwise steps run
+ * in fp32 with A1 = clamp(rne(x / s - rne(o))) and A2 = (code + rne(o)) * s; the matrix products see codes (q, k) or integers
+ * code + rne(o) split into parts exact in `dt` (probabilities), so no offset is too large for them. The safe softmax gives 0 on a row whose masked
+ * scores are all <= float(neg_inf). `skip_above_diagonal` (causal only): the caller asserts that the masked value of a key above
+ * the diagonal is -inf, so those tiles are not visited. out [B, q_heads, L, E] in `dt` (nullable): the value, or A2 of the output
+ * codes when the output quantizer is active; codes_out (nullable) its int8 codes. key_codes: with an active scaled-key quantizer,
+ * scratch of B * kv_heads * S * E elements of `dt` (16-byte aligned) that a first launch fills with the scaled-K codes; ignored
+ * (nullable) otherwise. Device only.
+ */
+enum {  /* the slots of quantizers[] */
+  FFQ_SDPA_SCORES = 0, FFQ_SDPA_MASK, FFQ_SDPA_MASKED, FFQ_SDPA_WEIGHTS, FFQ_SDPA_QUERY, FFQ_SDPA_KEY, FFQ_SDPA_DROPOUT, FFQ_SDPA_OUTPUT,
+  FFQ_SDPA_QUANTIZERS
+};
+typedef struct {
+  const float* scale;   /* NULL: the quantizer is not active */
+  const float* offset;  /* nullable */
+  double num_bits;
+} ffq_sdpa_quantizer;
+int ffq_sdpa_quantize(const void* q, const void* k, const void* v, int dt, const float* const* deq_scale,
+                      const float* const* deq_offset, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L, int64_t S,
+                      int64_t E, const int64_t* strides, const void* mask, int mask_kind, int mask_dt, const int64_t* mask_strides,
+                      double sqrt_scale, double neg_inf, const ffq_sdpa_quantizer* quantizers, int skip_above_diagonal, void* out,
+                      int8_t* codes_out, void* key_codes, void* stream);
+
+/*
  * W8A8 convolution — QuantizedConv2d / QuantizedConv1d (reference nn/conv.py) through fallback.conv2d / fallback.conv1d
  * (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer). Integer codes in, an implicit GEMM on the
  * int8 matrix cores, one fp32 epilogue per output element. For output (b, n, p), p = (oh, ow), V(p) = the taps (kh, kw) whose
