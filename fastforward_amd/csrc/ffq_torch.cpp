@@ -21,6 +21,7 @@
 #include <torch/csrc/Exceptions.h>
 #include <torch/library.h>
 
+#include <cstdint>
 #include <map>
 #include <mutex>
 #include <optional>
@@ -130,6 +131,11 @@ void same_device(const at::Tensor& data, const at::Tensor& other) {
 }
 
 at::Tensor flat(const at::Tensor& t) { return t.is_contiguous() ? t : t.reshape({-1}).contiguous(); }  // (pointer + numel() are what is read)
+// An operand of an entry point that reads with 16-byte vector loads and refuses other pointers: `t` itself when it is contiguous and
+// 16-byte aligned, else an aligned copy (.contiguous() keeps the pointer of a contiguous slice at an element offset)
+at::Tensor dense(const at::Tensor& t) {
+  return t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 ? t : t.clone(at::MemoryFormat::Contiguous);
+}
 
 void* stream_on(const at::Tensor& data) { return c10::hip::getCurrentHIPStream(data.device().index()).stream(); }
 
@@ -277,7 +283,7 @@ std::vector<at::Tensor> quantize_by_tile_backward(const at::Tensor& data, const 
   const bool fast = dt == output_grad.scalar_type() && (dt == at::kFloat || dt == at::kBFloat16 || dt == at::kHalf) && scale.scalar_type() == at::kFloat &&
                     (!has_offset || offset->scalar_type() == at::kFloat) && data.sizes() == output_grad.sizes();
   if (fast) {
-    at::Tensor data_c = data.contiguous(), grad_c = output_grad.contiguous();
+    at::Tensor data_c = dense(data), grad_c = dense(output_grad);  // (misaligned: the kernel on a copy, not the composite's sum order)
     at::Tensor scale_c = flat(scale), offset_c = has_offset ? flat(*offset) : at::Tensor();
     ffq_tiling tiling = tiling_of(data_c, tile_size);
     const int64_t ntiles = num_tiles(tiling);
@@ -344,7 +350,7 @@ at::Tensor linear_w8a8(const at::Tensor& x_codes, const at::Tensor& w_codes, con
                        double out_num_bits, const std::optional<at::Tensor>& w_rowsum, std::optional<at::ScalarType> requant_from) {
   TORCH_CHECK_TYPE(x_codes.scalar_type() == at::kChar && w_codes.scalar_type() == at::kChar, "linear_w8a8 expects int8 codes");
   c10::DeviceGuard guard(x_codes.device());
-  at::Tensor xc = x_codes.contiguous(), wc = w_codes.contiguous();
+  at::Tensor xc = dense(x_codes), wc = dense(w_codes);
   const int64_t K = xc.dim() ? xc.size(-1) : 0, N = wc.dim() ? wc.size(0) : 0, M = K ? xc.numel() / K : 0;
   TORCH_CHECK(wc.dim() == 2 && wc.size(1) == K, "mat1 and mat2 shapes cannot be multiplied (", M, "x", K, " and ", wc.sizes(), "^T)");
   at::Tensor xs = f32_flat(x_scale), xo = f32_flat(opt(x_offset)), ws_ = f32_flat(w_scale), wo = f32_flat(opt(w_offset));
@@ -382,7 +388,7 @@ at::Tensor bmm_w8a8(const at::Tensor& x_codes, const at::Tensor& w_codes, const 
   TORCH_CHECK_TYPE(x_codes.scalar_type() == at::kChar && w_codes.scalar_type() == at::kChar && x_codes.dim() == 3 && w_codes.dim() == 3,
                    "bmm_w8a8 expects int8 codes of shape [B, M, K] and [B, N, K]");
   c10::DeviceGuard guard(x_codes.device());
-  at::Tensor xc = x_codes.contiguous(), wc = w_codes.contiguous();
+  at::Tensor xc = dense(x_codes), wc = dense(w_codes);
   const int64_t B = xc.size(0), M = xc.size(1), K = xc.size(2), N = wc.size(1);
   TORCH_CHECK(wc.size(0) == B && wc.size(2) == K, "batch1 and batch2 shapes cannot be multiplied (", xc.sizes(), " and ", wc.sizes(), "^T)");
   at::Tensor xs = f32_flat(x_scale), xo = f32_flat(opt(x_offset)), ws_ = f32_flat(w_scale), wo = f32_flat(opt(w_offset));
@@ -406,7 +412,7 @@ at::Tensor bmm_w8a8(const at::Tensor& x_codes, const at::Tensor& w_codes, const 
 at::Tensor linear_wq(const at::Tensor& x, const at::Tensor& w_codes, const at::Tensor& w_scale, const std::optional<at::Tensor>& w_offset, int64_t group,
                      const std::optional<at::Tensor>& bias, at::ScalarType out_dtype, int64_t pack_block, int64_t two_pass, int64_t split) {
   c10::DeviceGuard guard(x.device());
-  at::Tensor xc = x.contiguous(), wc = w_codes.contiguous();
+  at::Tensor xc = dense(x), wc = dense(w_codes);
   const int64_t K = xc.dim() ? xc.size(-1) : 0;
   TORCH_CHECK(K > 0, "linear_wq: empty contraction");
   const int64_t N = pack_block > 0 ? wc.numel() * 2 / K : wc.size(0), M = xc.numel() / K;

@@ -18,6 +18,8 @@ the reference chain (the fallbacks in :mod:`fastforward_amd.nn.functional`) runs
   rescale (``scalar_multiply``) and is left to it;
 * softmax over the last dimension, ``dtype`` None or the value dtype, 8 | cols <= 16384; ``gelu`` with approximate "none" / "tanh";
 * sizes: 8 | numel (and 8 | the row of per-row parameters);
+* any layout: a strided view, or a contiguous one at a misaligned address (``x[1:]``, a split of a flat buffer), reaches the
+  kernel as an aligned copy (``ops._base._dense``; the kernels read 16-byte aligned buffers only), a dense aligned operand as it is;
 * no operand or parameter that needs a gradient while grad mode is on (the launches have no autograd formula);
 * under strict quantization, only calls the fallback would accept (an output quantizer, quantized tensor operands).
 

@@ -10,6 +10,8 @@ fallbacks in :mod:`fastforward_amd.nn.functional`) runs unchanged there:
 * bf16 / fp16 values: a plain tensor, or static-affine codes (int8 or value-dtype container, <= 8 bits, fp32 parameters) with
   per-tensor or per-row parameters; an embedding table per tensor, per row, per column or in groups of G % 8 == 0 along D;
 * sizes: 8 | the row (LayerNorm: 8 | cols <= 16384; Embedding: 8 | D; ReLU / SiLU: 8 | numel); ``max_norm is None``;
+* any layout: a strided view, or a contiguous one at a misaligned address (``x[1:]``, a split of a flat buffer), reaches the
+  kernel as an aligned copy (``ops._base._dense``; the kernels read 16-byte aligned buffers only), a dense aligned operand as it is;
 * no operand or parameter that needs a gradient while grad mode is on (the launches have no autograd formula).
 
 The output quantizer runs inside the launch under the rules that decide it for the int8 GEMM (``DispatcherKernels._requant``:

@@ -110,6 +110,16 @@ def _tile_of(data: torch.Tensor, tile_size: Sequence[int]) -> Tiling:
     return Tiling.make(tuple(data.shape), tuple(int(v) for v in tile_size))
 
 
+def _dense(t: torch.Tensor | None, memory_format: torch.memory_format = torch.contiguous_format) -> torch.Tensor | None:
+    """An operand for an entry point that reads with 16-byte vector loads and refuses other pointers (include/ffq.h): `t` itself
+    when it is dense in `memory_format` and 16-byte aligned, else a fresh copy in that format (the caching allocator aligns it).
+    ``.contiguous()`` is not enough: a slice at an element offset (``x[1:]``, a split of a flat buffer) is contiguous and keeps
+    its misaligned pointer. The copy holds the same values, so the result is bit for bit the aligned call's."""
+    if t is None or (t.is_contiguous(memory_format=memory_format) and t.data_ptr() % 16 == 0):
+        return t
+    return t.clone(memory_format=memory_format)
+
+
 def _flat(t: torch.Tensor | None) -> torch.Tensor | None:
     if t is None:
         return None

@@ -9,7 +9,7 @@ import torch
 
 from fastforward_amd.exceptions import BackendError
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _ptr, _tag, _workspace
+from fastforward_amd.ops._base import _dense, _ptr, _tag, _workspace
 
 _REAL = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -57,8 +57,8 @@ def conv2d_w8a8(
         raise RuntimeError(f"conv2d_w8a8: the weight has {Cw} input channels, the input {C} (groups > 1 is not built)")
     (sh, sw), (ph, pw), (dh, dw) = _pair(stride, "stride"), _pair(padding, "padding"), _pair(dilation, "dilation")
     nhwc = (not x_codes.is_contiguous()) and C % 16 == 0 and x_codes.is_contiguous(memory_format=torch.channels_last)
-    xc = x_codes.detach() if nhwc else x_codes.detach().contiguous()
-    wc = w_codes.detach().contiguous()
+    xc = _dense(x_codes.detach(), torch.channels_last if nhwc else torch.contiguous_format)
+    wc = _dense(w_codes.detach())
 
     def f32(t: torch.Tensor | None) -> torch.Tensor | None:
         return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()

@@ -9,7 +9,7 @@ import torch
 
 from fastforward_amd import _native
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _extrema_words, _native_route, _ptr, _tag, _workspace
+from fastforward_amd.ops._base import _dense, _extrema_words, _native_route, _ptr, _tag, _workspace
 
 
 def linear_w8a8(
@@ -49,8 +49,8 @@ def _linear_w8a8(x_codes, w_codes, x_scale, x_offset, w_scale, w_offset, bias, o
     """Python implementation of the ``linear_w8a8`` operator (Python -> ctypes -> C ABI); arguments in schema order."""
     if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
         raise TypeError("linear_w8a8 expects int8 codes")
-    xc = x_codes.detach().contiguous()
-    wc = w_codes.detach().contiguous()
+    xc = _dense(x_codes.detach())
+    wc = _dense(w_codes.detach())
     K = xc.shape[-1]
     N = wc.shape[0]
     M = xc.numel() // K if K else 0
@@ -106,7 +106,7 @@ def linear_w8a8_multi(
     count = len(rows)
     if not 2 <= count <= 3 or out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return None
-    xc, wc = x_codes.detach().contiguous(), w_codes.detach().contiguous()
+    xc, wc = _dense(x_codes.detach()), _dense(w_codes.detach())
     K, N = xc.shape[-1], int(sum(rows))
     M = xc.numel() // K if K else 0
     if wc.dim() != 2 or wc.shape != (N, K) or any(int(r) <= 0 for r in rows) or any(int(r) % 256 for r in rows[:-1]):
@@ -157,7 +157,7 @@ def linear_w8a8_earlier(
     codes are in force before anything reads `x_codes`."""
     if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8 or earlier[0].dtype != torch.int8:
         raise TypeError("linear_w8a8_earlier expects int8 codes")
-    xc, wc, ec = x_codes.detach().contiguous(), w_codes.detach().contiguous(), earlier[0].detach().contiguous()
+    xc, wc, ec = _dense(x_codes.detach()), _dense(w_codes.detach()), _dense(earlier[0].detach())
     K, N = xc.shape[-1], wc.shape[0]
     M = xc.numel() // K if K else 0
     if wc.dim() != 2 or wc.shape[1] != K:
@@ -208,7 +208,7 @@ def linear_w8a8_gated(
     would start with."""
     if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
         raise TypeError("linear_w8a8_gated expects int8 codes")
-    xc, wc, gc = x_codes.detach().contiguous(), w_codes.detach().contiguous(), gate.detach().contiguous()
+    xc, wc, gc = _dense(x_codes.detach()), _dense(w_codes.detach()), _dense(gate.detach())
     K, N = xc.shape[-1], wc.shape[0]
     M = xc.numel() // K if K else 0
     if wc.dim() != 2 or wc.shape[1] != K:
@@ -265,7 +265,7 @@ def _bmm_w8a8(x_codes, w_codes, x_scale, x_offset, w_scale, w_offset, out_dtype,
     """Python implementation of the ``bmm_w8a8`` operator; arguments in schema order."""
     if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8 or x_codes.dim() != 3 or w_codes.dim() != 3:
         raise TypeError("bmm_w8a8 expects int8 codes of shape [B, M, K] and [B, N, K]")
-    xc, wc = x_codes.detach().contiguous(), w_codes.detach().contiguous()
+    xc, wc = _dense(x_codes.detach()), _dense(w_codes.detach())
     B, M, K = xc.shape
     if wc.shape[0] != B or wc.shape[2] != K:
         raise RuntimeError(f"batch1 and batch2 shapes cannot be multiplied ({tuple(xc.shape)} and {tuple(wc.shape)}^T)")
@@ -306,7 +306,7 @@ def mlp_gate_up_w8a8(
     quantized_llama/mlp.py:30-40): int8 codes of the product, equal to
     ``silu_mul_quantize(linear_w8a8(x, gate), linear_w8a8(x, up))`` exactly. Per-tensor activation parameters,
     per-output-channel symmetric weights. Returns None when the shapes are outside the kernel's range."""
-    xc, gc, uc = x_codes.detach().contiguous(), gate_codes.detach().contiguous(), up_codes.detach().contiguous()
+    xc, gc, uc = _dense(x_codes.detach()), _dense(gate_codes.detach()), _dense(up_codes.detach())
     if not (xc.dtype == gc.dtype == uc.dtype == torch.int8) or gc.shape != uc.shape or gc.dim() != 2:
         raise TypeError("mlp_gate_up_w8a8 expects int8 codes and equally shaped gate / up weights")
     K, N = xc.shape[-1], gc.shape[0]
@@ -359,8 +359,8 @@ def mlp_gate_up_w8a8_estimating(
     one-launch gate + up + SiLU * up kernel runs on one of the code tensors — is decided on the device; otherwise the two linears
     run, the second with the gated epilogue. Same values either way: ``silu_mul_quantize(linear_w8a8(xg, ...), linear_w8a8(xu, ...),
     (), want_product=True)[0]``. ``want_extrema``: also ``[min, max]`` of the product. None outside the kernels' shapes."""
-    xg, xu = x_codes_gate.detach().contiguous(), x_codes_up.detach().contiguous()
-    gc, uc = gate_codes.detach().contiguous(), up_codes.detach().contiguous()
+    xg, xu = _dense(x_codes_gate.detach()), _dense(x_codes_up.detach())
+    gc, uc = _dense(gate_codes.detach()), _dense(up_codes.detach())
     if not (xg.dtype == xu.dtype == gc.dtype == uc.dtype == torch.int8) or gc.shape != uc.shape or gc.dim() != 2 or xg.shape != xu.shape:
         raise TypeError("mlp_gate_up_w8a8_estimating expects int8 codes, equally shaped gate / up weights and equally shaped activations")
     K, N = xg.shape[-1], gc.shape[0]

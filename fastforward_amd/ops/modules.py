@@ -16,7 +16,7 @@ import torch
 
 from fastforward_amd.exceptions import BackendError
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _ptr, _tag
+from fastforward_amd.ops._base import _dense, _ptr, _tag
 from fastforward_amd.ops.producers import _fan
 
 Quantizers = Sequence[tuple[torch.Tensor, torch.Tensor | None]]
@@ -41,8 +41,8 @@ def _params(scale: torch.Tensor, offset: torch.Tensor | None, count: int, what: 
 
 
 def _operand(x: torch.Tensor, dtype: torch.dtype, rows: int, dequant: tuple[torch.Tensor, torch.Tensor | None] | None, what: str):
-    """(contiguous data, data dtype tag, scale, offset, per_row) of a plain or quantized operand."""
-    xc = x.detach().contiguous()
+    """(contiguous, 16-byte aligned data, scale, offset, per_row) of a plain or quantized operand."""
+    xc = _dense(x.detach())
     if dequant is None:
         if xc.dtype != dtype:
             raise RuntimeError(f"{what}: a plain input must have the value dtype {dtype}, got {xc.dtype}")
@@ -71,8 +71,8 @@ def layer_norm_quantize(
     cols = int(normalized_numel)
     rows = x.numel() // cols if cols else 0
     xc, s, o, per_row = _operand(x, dtype, rows, dequant, "layer_norm_quantize")
-    wc = None if weight is None else weight.detach().contiguous()
-    bc = None if bias is None else bias.detach().contiguous()
+    wc = None if weight is None else _dense(weight.detach())
+    bc = None if bias is None else _dense(bias.detach())
     for name, t in (("weight", wc), ("bias", bc)):
         if t is not None and (t.numel() != cols or t.dtype != dtype):
             raise RuntimeError(f"layer_norm_quantize: {name} must hold {cols} elements of {dtype}")
@@ -110,7 +110,7 @@ def embedding_quantize(
         raise RuntimeError(f"embedding_quantize: ids must be int64 or int32, got {ids.dtype}")
     if table.dim() != 2:
         raise RuntimeError("embedding_quantize: the table is [V, D]")
-    ic, tc = ids.detach().contiguous(), table.detach().contiguous()
+    ic, tc = ids.detach().contiguous(), _dense(table.detach())
     V, D = tc.shape
     s = scale.detach().reshape(-1).to(torch.float32).contiguous()
     o = None if offset is None else offset.detach().reshape(-1).to(torch.float32).contiguous()

@@ -11,7 +11,7 @@ from typing import Sequence
 import torch
 
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _flat, _ptr, _tag, _tile_of, _workspace
+from fastforward_amd.ops._base import _dense, _flat, _ptr, _tag, _tile_of, _workspace
 from fastforward_amd.ops.static import dequantize_by_tile, quantize_by_tile
 
 
@@ -134,7 +134,7 @@ def grid_sqerror_by_tile(
     (``scales`` / ``offsets``: ``[candidates, tiles]`` fp32), all candidates in ONE pass over `data` — the inner loop
     of the min-error grid estimator (reference range_setting/min_error.py:218-231). With `out` given the sums are
     added to it. Returns None when the tiling is outside the kernel's range (the caller loops over A1 / A2)."""
-    data_c = data.detach().contiguous()
+    data_c = _dense(data.detach())  # (misaligned: the streaming kernel on a copy, not the by-tile kernel's sum order)
     sc = scales.detach().to(torch.float32).contiguous()
     of = None if offsets is None else offsets.detach().to(torch.float32).contiguous()
     if data_c.dtype not in (torch.float32, torch.bfloat16, torch.float16) or sc.dim() != 2:
@@ -165,7 +165,7 @@ def grid_sqerror_by_tile(
 
 
 def _pack_gguf(int_codes: torch.Tensor, scales: torch.Tensor, fmt: int) -> torch.Tensor:
-    codes = int_codes.detach().to(torch.int8).contiguous()
+    codes = _dense(int_codes.detach().to(torch.int8))
     if codes.dim() != 2 or codes.shape[1] != 32:
         raise ValueError(f"GGUF block-32 formats expect codes of shape (n_blocks, 32), got {tuple(codes.shape)}")
     sc = scales.detach().reshape(-1).to(torch.float32).contiguous()

@@ -11,7 +11,7 @@ import torch
 
 from fastforward_amd._cabi import FanOut
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _ptr, _tag
+from fastforward_amd.ops._base import _dense, _ptr, _tag
 
 
 def _fan(quantizers: Sequence[tuple[torch.Tensor, torch.Tensor | None]], num_bits: float, shape: Sequence[int], device: torch.device):
@@ -47,9 +47,9 @@ def add_rmsnorm_quantize(
     Returns ``(x + delta, normalised or None, [codes per quantizer])``; with ``delta is None`` the first
     element is `x` itself. ``sum_inplace`` writes the sum over `x` (the residual stream of a decoder).
     """
-    xc = x.detach().contiguous()
-    dc = None if delta is None else delta.detach().contiguous()
-    wc = weight.detach().contiguous()
+    xc = x.detach().contiguous() if sum_inplace else _dense(x.detach())
+    dc = None if delta is None else _dense(delta.detach())
+    wc = _dense(weight.detach())
     if dc is not None and dc.shape != xc.shape:
         raise RuntimeError(f"residual shapes differ: {tuple(xc.shape)} vs {tuple(dc.shape)}")
     if wc.dim() != 1 or wc.shape[0] != xc.shape[-1] or wc.dtype != xc.dtype or (dc is not None and dc.dtype != xc.dtype):
@@ -57,8 +57,8 @@ def add_rmsnorm_quantize(
     lib, stream = _base._prepare(xc, dc, wc, *[t for q in quantizers for t in q])
     cols = xc.shape[-1]
     rows = xc.numel() // cols if cols else 0
-    if sum_inplace and xc.data_ptr() != x.data_ptr():
-        raise RuntimeError("sum_inplace needs a contiguous residual tensor")
+    if sum_inplace and (xc.data_ptr() != x.data_ptr() or xc.data_ptr() % 16):
+        raise RuntimeError("sum_inplace needs a contiguous, 16-byte aligned residual tensor")
     total = xc if dc is None or sum_inplace else (torch.empty_like(xc) if want_sum else None)
     norm = torch.empty_like(xc) if want_norm else None
     fan, codes, keep = _fan(quantizers, num_bits, xc.shape, xc.device)
@@ -82,7 +82,7 @@ def silu_mul_quantize(
     want_product: bool = False,
 ) -> tuple[torch.Tensor | None, list[torch.Tensor]]:
     """``silu(gate) * up`` + A1, one pass (reference quantized_llama/mlp.py:30-40)."""
-    gc, uc = gate.detach().contiguous(), up.detach().contiguous()
+    gc, uc = _dense(gate.detach()), _dense(up.detach())
     if gc.shape != uc.shape or gc.dtype != uc.dtype:
         raise RuntimeError(f"gate and up differ: {tuple(gc.shape)} {gc.dtype} vs {tuple(uc.shape)} {uc.dtype}")
     lib, stream = _base._prepare(gc, uc, *[t for q in quantizers for t in q])

@@ -13,7 +13,7 @@ import torch
 from fastforward_amd import _host
 from fastforward_amd._cabi import FFQ_MAX_BATCH, DType, RowsBatch
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _DTYPES, _flat, _host_route, _ptr, _tag, _tickets, _tile_of, _workspace
+from fastforward_amd.ops._base import _dense, _DTYPES, _flat, _host_route, _ptr, _tag, _tickets, _tile_of, _workspace
 
 
 def quantize_by_tile(
@@ -142,7 +142,7 @@ def quantize_by_tile_backward(
         and data.shape == output_grad.shape
     )
     if fast:
-        data_c, grad_c = data.detach().contiguous(), output_grad.detach().contiguous()
+        data_c, grad_c = _dense(data.detach()), _dense(output_grad.detach())  # (misaligned: the kernel on a copy, not the composite's sum order)
         scale_c, offset_c = _flat(scale), _flat(offset)
         lib, stream = _base._prepare(data_c, grad_c, scale_c, offset_c)
         tiling = _tile_of(data_c, tile_size)
@@ -247,7 +247,7 @@ def quantize_rows_rowsum(
     of = None if offset is None else offset.detach().reshape(-1).to(torch.float32).contiguous()
     if sc.numel() != rows or (of is not None and of.numel() != rows):
         raise RuntimeError(f"expected one scale (and offset) per row ({rows}), got {sc.numel()}")
-    wd = weight.detach()
+    wd = _dense(weight.detach())  # (a contiguous slice at an element offset: an aligned copy)
     lib, stream = _base._prepare(wd, sc, of)
     codes = torch.empty((rows, cols), dtype=torch.int8, device=wd.device)
     if rowsum_out is None:

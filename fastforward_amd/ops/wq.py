@@ -12,7 +12,7 @@ import torch
 
 from fastforward_amd import _native
 from fastforward_amd.ops import _base
-from fastforward_amd.ops._base import _TAGS, _native_route, _ptr, _tag, _tickets, _workspace
+from fastforward_amd.ops._base import _TAGS, _dense, _native_route, _ptr, _tag, _tickets, _workspace
 
 
 def linear_wq(
@@ -74,7 +74,7 @@ def _linear_wq(x, w_codes, w_scale, w_offset, group, bias, out_dtype, pack_block
     N = w_codes.numel() * 2 // K if pack_block > 0 else w_codes.shape[0]
     M = x.numel() // K
     two_pass = None if two_pass < 0 else bool(two_pass)
-    xc, wc = x.detach().contiguous(), w_codes.detach().contiguous()
+    xc, wc = _dense(x.detach()), _dense(w_codes.detach())
     sc = w_scale.detach().reshape(-1).to(torch.float32).contiguous()
     of = None if w_offset is None else w_offset.detach().reshape(-1).to(torch.float32).contiguous()
     if of is not None and of.numel() != sc.numel():
@@ -147,8 +147,8 @@ def linear_wq_multi(
             return None
     if not per_row and group != K:
         return None
-    xc = x.detach().contiguous()
-    codes = [c.detach().contiguous() for c in w_codes]
+    xc = _dense(x.detach())
+    codes = [_dense(c.detach()) for c in w_codes]
     lib, stream = _base._prepare(xc, *codes, *scales, *[o for o in offsets if o is not None])
     outs = [torch.empty((*xc.shape[:-1], n), dtype=out_dtype, device=xc.device) for n in rows]
     nbytes, tickets = _wq_scratch(lib, M, N, K, False, two_pass, split, xc.device, stream)
@@ -216,7 +216,7 @@ def mlp_gate_up_wq(
     lib = _native.library()
     if not lib.ffq_linear_wq_supported(_tag(x.dtype), _tag(gate_codes.dtype), _tag(torch.bfloat16), M, N, K, group, int(pack_block)):
         return None
-    xc, gc, uc = x.detach().contiguous(), gate_codes.detach().contiguous(), up_codes.detach().contiguous()
+    xc, gc, uc = _dense(x.detach()), _dense(gate_codes.detach()), _dense(up_codes.detach())
     flat = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
     gs, go, us, uo = flat(gate_scale), flat(gate_offset), flat(up_scale), flat(up_offset)
     if gs.numel() != us.numel() or (go is not None and (go.numel() != gs.numel() or uo.numel() != gs.numel())):

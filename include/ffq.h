@@ -329,7 +329,8 @@ int ffq_bmm_w8a8(const int8_t* xq, const int8_t* wq, const float* x_scale, const
  * kernel): bit-reproducible launch to launch, equal across the storage forms that share a kernel, NOT equal across batch sizes or
  * across the kernels (every route stays within one output rounding of the float64 product of the same operands).
  * ffq_linear_wq_supported() == 0 (K % 64 != 0, K < 128, other dtypes, group % 64 != 0): the caller dequantizes (A2) and
- * runs a float GEMM, as the reference does.
+ * runs a float GEMM, as the reference does. It sees no pointer: x, the codes and out must also be 16-byte aligned (else
+ * FFQ_ERR_DTYPE), and the package's wrappers (Python and C++) pass an aligned copy of an operand that is not.
  */
 int ffq_linear_wq_supported(int x_dt, int w_dt, int out_dt, int64_t M, int64_t N, int64_t K, int64_t group, int64_t pack_block);
 int64_t ffq_linear_wq_split(int64_t M, int64_t N, int64_t K, int mlp);   /* mlp != 0: the plan of ffq_mlp_gate_up_wq */
@@ -425,6 +426,8 @@ int ffq_silu_mul_quantize(const void* gate, const void* up, int dt, int64_t nume
  * dt is bf16 or fp16; weight / bias are nullable [cols] vectors of dt; out ([rows, cols] of dt) is nullable. The summation order
  * of mean and var is the kernel's own: z can differ from ATen's by a bf16 ulp on rare elements; the codes are exactly A1 of the
  * z this call produces. cols % 8 == 0, cols <= 16384.
+ * This and the module / elementwise entry points below take 16-byte aligned buffers only (else FFQ_ERR_ARG): the package hands a
+ * strided operand, or a contiguous one at a misaligned address, over as an aligned copy (fastforward_amd/ops/_base.py, _dense).
  */
 int ffq_layer_norm_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int x_per_row,
                             const void* weight, const void* bias, int dt, int64_t rows, int64_t cols, double eps,
