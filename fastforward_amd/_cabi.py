@@ -209,6 +209,11 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_binary_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _i64, _i64, _d, _d, _i, _i64, _vp, _fp, _vp]),
     "ffq_softmax_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i, _i64, _i64, _vp, _fp, _vp]),
     "ffq_activation_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i, _i64, _vp, _fp, _vp]),
+    "ffq_rms_norm_quantize": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i64, _i64, _d, _vp, _fp, _vp]),
+    "ffq_unary_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _d, _i, _i64, _vp, _fp, _vp]),
+    "ffq_sum_quantize_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "ffq_sum_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _vp, _fp, _vp, _sz, _vp]),
+    "ffq_cumsum_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _vp, _fp, _vp]),
     "ffq_sdpa_quantize": (
         _i,
         [_vp, _vp, _vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _vp, _i, _i,
@@ -237,7 +242,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
 # callers treat that as "not covered". Whether the symbol is there is the capability check (FFQ_ABI_VERSION does not move for them).
 DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_quantize", "ffq_embedding_quantize", "ffq_pointwise_quantize",
                                          "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
-                                         "ffq_activation_quantize", "ffq_sdpa_quantize"})
+                                         "ffq_activation_quantize", "ffq_sdpa_quantize", "ffq_rms_norm_quantize", "ffq_unary_quantize",
+                                         "ffq_sum_quantize_workspace_bytes", "ffq_sum_quantize", "ffq_cumsum_quantize"})
 
 
 class FFQLibrary:

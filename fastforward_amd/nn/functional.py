@@ -13,8 +13,9 @@ add / sub / mul / div, softmax, sigmoid and GELU kernels (fallbacks: _gen/fallba
 ``mul`` of a per-tensor affine tensor by a Python number without an output quantizer is the reference's rescale of the scale
 (quantization/_linear_quantized_ops.py:126-171). ``dropout`` follows fallback.py:1399-1423 with no kernel of its own, and
 ``scaled_dot_product_attention`` is the reference's custom operator (nn/sdpa.py; ``fastforward_amd.fused_sdpa`` registers its
-kernel). The other generated operators of the reference are pure float fallbacks and are
-out of scope.
+kernel). ``rms_norm``, ``pow``, ``exp``, ``sin``, ``cos``, ``sum`` and ``cumsum`` follow their fallbacks (_gen/fallback.py:955-1014,
+1520-1541, 1831-1941), and ``fastforward_amd.fused_math`` registers their one-pass kernels. The other generated operators of the
+reference are pure float fallbacks and are out of scope.
 """
 
 from __future__ import annotations
@@ -32,7 +33,8 @@ if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
 __all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
-           "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention"]
+           "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
+           "cumsum"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -280,6 +282,80 @@ def _fallback_dropout(input: torch.Tensor, p: float = 0.5, training: bool = True
 def dropout(input: torch.Tensor, p: float = 0.5, training: bool = True, inplace: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, p=p, training=training, inplace=inplace, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("dropout", **kwargs) or _fallback_dropout)(**kwargs)
+
+
+# ---- rms_norm, pow, exp / sin / cos, sum, cumsum (reference _gen/operators.py: dispatch(op, **kwargs) or the generated fallback) --
+def _fallback_rms_norm(input: torch.Tensor, normalized_shape: tuple[int, ...], weight: torch.Tensor | None = None, eps: float | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize input / weight, F.rms_norm, optional output quantizer (reference fallback.py:1906-1941)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    if weight is not None:
+        weight = _dequantized("weight", weight, strict_quantization)
+    output = torch.nn.functional.rms_norm(input=input, normalized_shape=normalized_shape, weight=weight, eps=eps)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _fallback_pow(input: torch.Tensor, exponent: torch.Tensor | float, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize input / a tensor exponent, torch.pow, optional output quantizer (reference fallback.py:955-990); a number
+    exponent is no strict-mode error."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    exponent = _dequantized("exponent", exponent, strict_quantization, required=isinstance(exponent, torch.Tensor))
+    output = torch.pow(input=input, exponent=exponent)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _reduction_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., torch.Tensor]:
+    def fallback(input: torch.Tensor, dim: int | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+        """Dequantize, the torch reduction / scan over `dim`, optional output quantizer."""
+        _check_output_quantizer(output_quantizer, strict_quantization)
+        input = _dequantized("input", input, strict_quantization)
+        output = torch_op(input=input, dim=dim)
+        return output_quantizer(output) if output_quantizer is not None else output
+
+    return fallback
+
+
+_fallback_exp = _unary_fallback(torch.exp)  # fallback.py:1831-1853
+_fallback_sin = _unary_fallback(torch.sin)  # fallback.py:1856-1878
+_fallback_cos = _unary_fallback(torch.cos)  # fallback.py:1881-1903
+_fallback_sum = _reduction_fallback(torch.sum)  # fallback.py:993-1014
+_fallback_cumsum = _reduction_fallback(torch.cumsum)  # fallback.py:1520-1541
+
+
+def rms_norm(input: torch.Tensor, normalized_shape: tuple[int, ...], weight: torch.Tensor | None = None, eps: float | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, normalized_shape=normalized_shape, weight=weight, eps=eps, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("rms_norm", **kwargs) or _fallback_rms_norm)(**kwargs)
+
+
+def pow(input: torch.Tensor, exponent: torch.Tensor | float, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, exponent=exponent, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("pow", **kwargs) or _fallback_pow)(**kwargs)
+
+
+def exp(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("exp", **kwargs) or _fallback_exp)(**kwargs)
+
+
+def sin(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("sin", **kwargs) or _fallback_sin)(**kwargs)
+
+
+def cos(input: torch.Tensor, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("cos", **kwargs) or _fallback_cos)(**kwargs)
+
+
+def sum(input: torch.Tensor, dim: int | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, dim=dim, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("sum", **kwargs) or _fallback_sum)(**kwargs)
+
+
+def cumsum(input: torch.Tensor, dim: int, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, dim=dim, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("cumsum", **kwargs) or _fallback_cumsum)(**kwargs)
 
 
 from fastforward_amd.nn.sdpa import scaled_dot_product_attention  # noqa: E402  (nn/sdpa.py calls back into this module)

@@ -494,6 +494,58 @@ int ffq_activation_quantize(int op, const void* x, int x_dt, const float* x_scal
                             int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
 
 /*
+ * rms_norm over the last dimension + A1 — ff.nn.functional.rms_norm (reference _gen/fallback.py:1906-1941: A2 of the input,
+ * F.rms_norm, the output quantizer):   v as in ffq_layer_norm_quantize (plain, or codes with per-tensor / per-row parameters);
+ *   r = rsqrt(sum(v^2) / cols + eps)  (fp32),   z = dt((v * r) * w), or dt(v * r) without a weight   (ONE rounding, as ATen's
+ *   fused kernel; not the add_rmsnorm epilogue, which rounds before the weight),   codes_j = A1(z; scale_j, offset_j)
+ * weight is nullable, `cols` elements of dt (the caller dequantizes a quantized weight). eps is the caller's: F.rms_norm with
+ * eps=None uses the fp32 epsilon for bf16 / fp16. The summation order of sum(v^2) is the kernel's own: z can differ from ATen's
+ * by one ulp on rare elements; the codes are exactly A1 of the z this call produces. out is nullable.
+ * cols % 8 == 0, cols <= 16384.
+ */
+int ffq_rms_norm_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int x_per_row, const void* weight,
+                          int dt, int64_t rows, int64_t cols, double eps, void* out, const ffq_fanout* fan, void* stream);
+
+/*
+ * exp / sin / cos / pow by a number + A1 — ff.nn.functional.exp / sin / cos / pow (reference _gen/fallback.py:955-990,
+ * 1831-1903):  z = dt(op(v)),  codes_j = A1(z; scale_j, offset_j), with ATen's device formulas in fp32:
+ *   op 0 exp: expf(v);  op 1 sin: sinf(v);  op 2 cos: cosf(v)      (never the fast-math forms; exponent must be 0)
+ *   op 3 pow(v, exponent): 0: 1;  1: v;  0.5: sqrtf(v);  -0.5: rsqrtf(v);  -1: 1 / v;  else with e = dt(exponent) (ATen converts
+ *        the exponent to the data dtype):  e == 2: v * v;  e == 3: dt(v * v) * v;  e == -2: 1 / dt(v * v);  else powf(v, e)
+ * v as in ffq_pointwise_quantize. Bit for bit ATen's value on every bf16 / fp16 input. out is nullable.
+ * numel % 8 == 0 (and param_run % 8 == 0); a pow exponent is finite and |exponent| <= 65504.
+ */
+int ffq_unary_quantize(int op, const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_run,
+                       double exponent, int dt, int64_t numel, void* out, const ffq_fanout* fan, void* stream);
+
+/*
+ * sum over one axis + A1 — ff.nn.functional.sum (reference _gen/fallback.py:993-1014): x viewed as [outer, len, inner] (row-major),
+ * z[o, i] = dt(sum over l of v[o, l, i]) with an fp32 accumulator,  codes_j = A1(z; scale_j, offset_j). sum(dim=None) is
+ * outer = inner = 1. v as in ffq_pointwise_quantize (param_run: per-row parameters of the last dimension of x).
+ * The summation order is the kernel's own and fixed by the shape (no atomics: the result is deterministic): sequential per lane,
+ * then a butterfly over the wave and the block's waves in order (inner == 1 and the whole tensor), or sequential along len per
+ * segment of rows and the segments in order (inner > 1). z can differ from ATen's by one ulp on rare elements; the codes are
+ * exactly A1 of the z this call produces. out (outer * inner elements) is nullable.
+ * Workspace: ffq_sum_quantize_workspace_bytes(outer, len, inner) bytes, 16-byte aligned (fp32 partials; 0 for row sums); less
+ * returns FFQ_ERR_WORKSPACE. len > 0; 8 | len when inner == 1, else 8 | inner.
+ */
+size_t ffq_sum_quantize_workspace_bytes(int64_t outer, int64_t len, int64_t inner);
+int ffq_sum_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_run, int dt, int64_t outer,
+                     int64_t len, int64_t inner, void* out, const ffq_fanout* fan, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/*
+ * cumsum along one axis + A1 — ff.nn.functional.cumsum (reference _gen/fallback.py:1520-1541): x viewed as [outer, len, inner],
+ * z[o, l, i] = dt(fp32 running sum of v[o, 0..l, i]),  codes_j = A1(z; scale_j, offset_j). Each prefix is rounded once, as ATen's
+ * CPU kernel; ATen's DEVICE kernel keeps its running sum in the data dtype, so it is no reference for the value: z is within one
+ * ulp of the float64 scan rounded to dt. The summation order is the kernel's own: sequential along len (inner > 1), or sequential
+ * per 8 elements, then scanned across the wave and the block's waves with a carried fp32 total (inner == 1).
+ * v as in ffq_sum_quantize. out is nullable. 8 | len when inner == 1, else 8 | inner.
+ */
+int ffq_cumsum_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_run, int dt,
+                        int64_t outer, int64_t len, int64_t inner, void* out, const ffq_fanout* fan, void* stream);
+
+/*
  * Quantized scaled_dot_product_attention — ff.nn.functional.scaled_dot_product_attention (reference
  * nn/functional/custom/sdpa.py:116-285: fp32 upcast, q * sqrt(scale) -> A1, k^T * sqrt(scale) -> A1, matmul -> A1, + bias (mask
  * -> A1) -> A1, safe softmax -> A1, dropout (p = 0) -> A1, matmul -> A1) in one launch, no [L, S] matrix in memory.
