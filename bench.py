@@ -20,10 +20,15 @@ timed region holds no Python.
 Multi-GPU: inference shards over the batch with no data-path collective (replicas; "weak"
 scaling: per-GPU batch fixed). value = total tokens of all ranks / max-over-ranks time.
 
-Output: ONE JSON line on rank 0. `roofline` describes the dominant kernel of the step (the int8
-MFMA GEMM); `hbm_kernels` lists the HBM-bound hot-path kernels on the headline shape
-[14336, 4096] bf16 per-channel with achieved GB/s vs 8 TB/s; `cpu_baseline` is the reference's
-eager ATen chain (oracle/eager_chain.py, a port) timed on this box's host cores on a bounded sample.
+Output: ONE JSON line on rank 0. A plain run sets up, calibrates, warms up, times the steps and
+prints the headline (tokens/s, ms_per_step) with the calibration it ran; nothing else.
+
+`--full` adds the side measurements, on rank 0 after the timed region: `module_graph_drop_in` (the
+reference-shaped module graph timed on the same batch); `roofline`, the dominant kernel of the step
+(the int8 MFMA GEMM), with a same-box MFMA probe; `hbm_kernels`, the HBM-bound hot-path kernels on
+the headline shape [14336, 4096] bf16 per-channel with achieved GB/s vs 8 TB/s; `attention_kernel`;
+`host_us_per_op`; `cpu_baseline`, the reference's eager ATen chain (oracle/eager_chain.py, a port)
+timed on the host cores on a bounded sample; and a compact `summary` at the end of the line.
 
 `--dump-outputs DIR` writes the logits of the last timed step to DIR/logits.npy (float32, at most 64 MB: a fixed, seeded
 sample of rows at the Llama-3-8B shapes), so two builds run with the same arguments can be compared output for output.
@@ -553,7 +558,10 @@ def main() -> None:
     ap.add_argument("--module-graph", action="store_true", help="run the reference-shaped module graph (one quantizer call per linear input, "
                     "eager RMSNorm / rotary / SiLU) instead of llama.FusedForward (A1 fused into those producers)")
     ap.add_argument("--cache-weight-codes", action="store_true", help="keep int8 weight codes across steps (NOT the headline: the reference re-quantizes)")
-    ap.add_argument("--no-side-measurements", action="store_true", help="skip roofline / cpu_baseline legs")
+    side_legs = ap.add_mutually_exclusive_group()
+    side_legs.add_argument("--full", action="store_true", help="after the headline, run the side measurements on rank 0: module graph, roofline, "
+                           "HBM kernels, attention kernel, host cost per op, CPU baseline")
+    side_legs.add_argument("--no-side-measurements", action="store_true", help="no side measurements: what a run without --full does (kept for existing commands)")
     ap.add_argument("--qkv-three-launches", action="store_true", help="A/B arm: q_proj / k_proj / v_proj as three launches of the int8 GEMM (round 5) instead of one")
     ap.add_argument("--batch-rowsums", action="store_true", help="A/B: weight row sums from the batched weight-quantization launch instead of one rowsum_i8 launch per linear (measured slower: llama.FusedForward)")
     ap.add_argument("--layer-batched-weights", action="store_true", help="A/B: all seven weights of a layer re-quantized by one launch at the top of the layer (round 4's schedule) instead of group by group right before their GEMMs")
@@ -662,7 +670,7 @@ def main() -> None:
     # one-pass kernels wherever the slots between them are untouched stubs (llama.py), or, inside llama.eager_modules(), as the
     # reference helpers' eager ATen chains. Same arithmetic, same batch, hipGraph-replayed; rank 0 only, after the headline region
     module_graph = None
-    if fused is not None and rank == 0 and not args.no_side_measurements:
+    if fused is not None and rank == 0 and args.full:
         mg_steps = max(2, min(args.steps, 5))
 
         def replayed(fn) -> float:
@@ -747,7 +755,7 @@ def main() -> None:
                         "all_reduce_us": round(float(exchange["seconds"]) * 1e6, 1) if exchange else None,
                         "all_reduce_backend": exchange.get("backend") if exchange else None},
     }
-    if rank == 0 and not args.no_side_measurements:
+    if rank == 0 and args.full:
         del graph
         torch.cuda.empty_cache()
         result["roofline"] = gemm_roofline(config, args.batch * args.seq_len, device, fused, batch)
