@@ -214,6 +214,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_sum_quantize_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "ffq_sum_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _vp, _fp, _vp, _sz, _vp]),
     "ffq_cumsum_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _vp, _fp, _vp]),
+    "ffq_pool2d_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i] + [_i64] * 11 + [_i, _i64, _i64, _vp, _fp, _vp]),
+    "ffq_upsample_nearest_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _i64, _i64, _d, _d, _i, _vp, _fp, _vp]),
     "ffq_sdpa_quantize": (
         _i,
         [_vp, _vp, _vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _vp, _i, _i,
@@ -243,7 +245,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
 DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_quantize", "ffq_embedding_quantize", "ffq_pointwise_quantize",
                                          "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
                                          "ffq_activation_quantize", "ffq_sdpa_quantize", "ffq_rms_norm_quantize", "ffq_unary_quantize",
-                                         "ffq_sum_quantize_workspace_bytes", "ffq_sum_quantize", "ffq_cumsum_quantize"})
+                                         "ffq_sum_quantize_workspace_bytes", "ffq_sum_quantize", "ffq_cumsum_quantize",
+                                         "ffq_pool2d_quantize", "ffq_upsample_nearest_quantize"})
 
 
 class FFQLibrary:

@@ -14,8 +14,10 @@ add / sub / mul / div, softmax, sigmoid and GELU kernels (fallbacks: _gen/fallba
 (quantization/_linear_quantized_ops.py:126-171). ``dropout`` follows fallback.py:1399-1423 with no kernel of its own, and
 ``scaled_dot_product_attention`` is the reference's custom operator (nn/sdpa.py; ``fastforward_amd.fused_sdpa`` registers its
 kernel). ``rms_norm``, ``pow``, ``exp``, ``sin``, ``cos``, ``sum`` and ``cumsum`` follow their fallbacks (_gen/fallback.py:955-1014,
-1520-1541, 1831-1941), and ``fastforward_amd.fused_math`` registers their one-pass kernels. The other generated operators of the
-reference are pure float fallbacks and are out of scope.
+1520-1541, 1831-1941), and ``fastforward_amd.fused_math`` registers their one-pass kernels. ``avg_pool1d``, ``avg_pool2d``,
+``max_pool2d`` and ``interpolate`` follow theirs (_gen/fallback.py:505-575, 1574-1646) with the reference's signatures, and
+``fastforward_amd.fused_pool`` registers the one-pass kernels of the pools and of nearest interpolation. The other generated
+operators of the reference are pure float fallbacks and are out of scope.
 """
 
 from __future__ import annotations
@@ -34,7 +36,7 @@ if TYPE_CHECKING:
 
 __all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
            "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
-           "cumsum"]
+           "cumsum", "avg_pool1d", "avg_pool2d", "max_pool2d", "interpolate"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -356,6 +358,58 @@ def sum(input: torch.Tensor, dim: int | None = None, *, output_quantizer: Option
 def cumsum(input: torch.Tensor, dim: int, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, dim=dim, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("cumsum", **kwargs) or _fallback_cumsum)(**kwargs)
+
+
+# ---- avg_pool1d / avg_pool2d, max_pool2d, interpolate (reference _gen/operators.py: dispatch(op, **kwargs) or the generated fallback) --
+def _avg_pool_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., torch.Tensor]:
+    def fallback(input: torch.Tensor, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+        """Dequantize, the torch average pool, optional output quantizer."""
+        _check_output_quantizer(output_quantizer, strict_quantization)
+        input = _dequantized("input", input, strict_quantization)
+        output = torch_op(input=input, kernel_size=kernel_size, stride=stride, padding=padding, ceil_mode=ceil_mode, count_include_pad=count_include_pad)
+        return output_quantizer(output) if output_quantizer is not None else output
+
+    return fallback
+
+
+_fallback_avg_pool1d = _avg_pool_fallback(torch.nn.functional.avg_pool1d)  # fallback.py:505-538
+_fallback_avg_pool2d = _avg_pool_fallback(torch.nn.functional.avg_pool2d)  # fallback.py:542-575
+
+
+def _fallback_max_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any = None, padding: Any = 0, dilation: Any = 1, ceil_mode: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.max_pool2d, optional output quantizer (reference fallback.py:1574-1607)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.max_pool2d(input=input, kernel_size=kernel_size, stride=stride, padding=padding, dilation=dilation, ceil_mode=ceil_mode)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _fallback_interpolate(input: torch.Tensor, size: Any = None, scale_factor: Any = None, mode: str = "nearest", align_corners: bool | None = None, recompute_scale_factor: bool | None = None, antialias: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.interpolate, optional output quantizer (reference fallback.py:1611-1646)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.interpolate(input=input, size=size, scale_factor=scale_factor, mode=mode, align_corners=align_corners, recompute_scale_factor=recompute_scale_factor, antialias=antialias)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def avg_pool1d(input: torch.Tensor, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, kernel_size=kernel_size, stride=stride, padding=padding, ceil_mode=ceil_mode, count_include_pad=count_include_pad, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("avg_pool1d", **kwargs) or _fallback_avg_pool1d)(**kwargs)
+
+
+def avg_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, kernel_size=kernel_size, stride=stride, padding=padding, ceil_mode=ceil_mode, count_include_pad=count_include_pad, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("avg_pool2d", **kwargs) or _fallback_avg_pool2d)(**kwargs)
+
+
+def max_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any = None, padding: Any = 0, dilation: Any = 1, ceil_mode: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, kernel_size=kernel_size, stride=stride, padding=padding, dilation=dilation, ceil_mode=ceil_mode, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("max_pool2d", **kwargs) or _fallback_max_pool2d)(**kwargs)
+
+
+def interpolate(input: torch.Tensor, size: Any = None, scale_factor: Any = None, mode: str = "nearest", align_corners: bool | None = None, recompute_scale_factor: bool | None = None, antialias: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, size=size, scale_factor=scale_factor, mode=mode, align_corners=align_corners, recompute_scale_factor=recompute_scale_factor, antialias=antialias, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("interpolate", **kwargs) or _fallback_interpolate)(**kwargs)
 
 
 from fastforward_amd.nn.sdpa import scaled_dot_product_attention  # noqa: E402  (nn/sdpa.py calls back into this module)

@@ -546,6 +546,36 @@ int ffq_cumsum_quantize(const void* x, int x_dt, const float* x_scale, const flo
                         int64_t outer, int64_t len, int64_t inner, void* out, const ffq_fanout* fan, void* stream);
 
 /*
+ * avg_pool1d / avg_pool2d / max_pool2d + A1 — ff.nn.functional.avg_pool1d / avg_pool2d / max_pool2d (reference _gen/fallback.py:
+ * 505-575, 1574-1607): x is [planes, H, W] (planes = B * C; avg_pool1d is H = kh = 1, as in ATen), z [planes, OH, OW] = dt(op(v)),
+ * codes_j = A1(z; scale_j, offset_j), with ATen's device formulas:
+ *   mode 0 avg (count_include_pad): one fp32 accumulator over the part of the window inside the input, rows outer / columns inner,
+ *          divided once by the window's size clipped to the input plus its padding;   mode 1 avg: divided by its size inside the input;
+ *   mode 2 max: `val > max || isnan(val)` from -inf over the dilated window inside the input (NaN wins; the padding is -inf).
+ * v: plain dt, or A2 of int8 / dt codes with one fp32 parameter pair for the tensor (param_channels 0) or one per channel
+ * (param_channels = C > 0 pairs, plane p reads pair p % C; C divides planes). Bit for bit the chain's value. out is nullable.
+ * [OH, OW] must be ATen's pooling_output_shape(H / W, kernel, pad, stride, dilation, ceil_mode) — the last window starts inside the
+ * input or its left padding; kernel, stride, dilation >= 1 (dilation 1 for the averages), 0 <= pad <= kernel / 2, H, W >= 1:
+ * otherwise FFQ_ERR_ARG, as ATen refuses them. Any plane size (no multiple of 8 is asked); fewer than 2^31 input and output elements.
+ * FFQ_ERR_DTYPE for dt other than bf16 / fp16 or an input that is neither dt nor codes with a scale, before any buffer is looked at.
+ */
+int ffq_pool2d_quantize(int mode, const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_channels, int dt,
+                        int64_t planes, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                        int64_t dh, int64_t dw, int ceil_mode, int64_t OH, int64_t OW, void* out, const ffq_fanout* fan, void* stream);
+
+/*
+ * interpolate(mode="nearest" / "nearest-exact") + A1 — ff.nn.functional.interpolate (reference _gen/fallback.py:1611-1646):
+ * x [planes, H, W] -> z [planes, OH, OW] (a 3-D input is H = OH = 1), z[p, i, j] = v[p, src(i), src(j)], codes_j = A1(z; ...), with
+ * ATen's source index in fp32:  src(d) = min(floor(d * scale), in - 1), for exact != 0 min(floor((d + 0.5) * scale), in - 1), where
+ * scale = (float)(1 / scale_factor) when scale_factor > 0 (the caller passed one and did not ask to recompute it), else
+ * (float)in / (float)out. v and param_channels as in ffq_pool2d_quantize. Bit for bit the chain's value. out is nullable.
+ * OH, OW >= 1 are the caller's (ATen: `size`, or floor(in * scale_factor)); scale factors are finite and >= 0.
+ */
+int ffq_upsample_nearest_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_channels, int dt,
+                                  int64_t planes, int64_t H, int64_t W, int64_t OH, int64_t OW, double scale_factor_h,
+                                  double scale_factor_w, int exact, void* out, const ffq_fanout* fan, void* stream);
+
+/*
  * Quantized scaled_dot_product_attention — ff.nn.functional.scaled_dot_product_attention (reference
  * nn/functional/custom/sdpa.py:116-285: fp32 upcast, q * sqrt(scale) -> A1, k^T * sqrt(scale) -> A1, matmul -> A1, + bias (mask
  * -> A1) -> A1, safe softmax -> A1, dropout (p = 0) -> A1, matmul -> A1) in one launch, no [L, S] matrix in memory.
