@@ -4,10 +4,7 @@
 // ff.nn.functional.{add, sub, mul, div, softmax, sigmoid, gelu} run their generated fallbacks in the reference
 // (_gen/fallback.py: softmax :269, sigmoid :321, add :801, sub :840, mul :879, div :917, gelu :1373): A2 of each quantized
 // operand into a data-dtype tensor, the ATen op, A1 of the output quantizer — up to four launches with a full-size temporary
-// between each. Here each is one pass, with the arithmetic of ffq_modules.hip: an operand's codes are dequantized in registers as
-// ffq_dequantize.hip does ((q + round(o)) * s in fp32, rounded to the data dtype, exactly the chain's intermediate tensor), the op
-// runs in fp32 with ATen's formula and rounds once to the data dtype, and the value goes through the A1 arithmetic of ffq_affine.h
-// for up to FFQ_MAX_FANOUT static per-tensor quantizers (ffq_fanout.h). The value itself is stored only when the caller asks.
+// between each. Here each is one pass under the A2 / op / A1 contract of ffq_onepass.h.
 // ATen's device formulas, as its kernels evaluate them (the library's contraction of a * b + c into one fma included):
 //   add / sub:  a + b * alpha  ->  fma(b, +-alpha, a)           (sub is add with -alpha); a scalar b: a + float(b) * (+-alpha)
 //   mul / div:  a * b,  a / b (the IEEE quotient);  div by a scalar s: a * float(1 / s), the reciprocal taken of the double s
@@ -15,68 +12,15 @@
 //   sigmoid:    1 / (1 + exp(-v))
 //   gelu:       (v * 0.5) * (1 + erf(v * M_SQRT1_2));  tanh form: (0.5 * v) * (1 + tanh(kBeta * fma(0.044715, v^3, v)))
 //   softmax:    exp(v - max) / sum(exp(v - max))                 (max, sum, quotient in fp32)
-// Chunks are 8 elements: 16 B per lane for bf16 / fp16 values, 8 B for int8 codes. Algorithmic bytes per element are stated at
-// each kernel; all three are HBM-bound streams.
+// Algorithmic bytes per element are stated at each kernel; all three are HBM-bound streams.
 #ifndef FFQ_NT_STREAMS
 #define FFQ_NT_STREAMS 3  // nt loads and stores of the streamed tensors, as ffq_producers.hip
 #endif
-#include "ffq_affine.h"
-#include "ffq_common.h"
-#include "ffq_fanout.h"
-#include "ffq_vec.h"
-
-#include <math.h>
+#include "ffq_onepass.h"
 
 namespace ffq {
 
-constexpr int kE = 8;          // elements per chunk
 constexpr int kEwBlock = 512;  // the streaming kernels' block (as ffq_modules.hip's pointwise kernel)
-
-template <typename T>
-__device__ __forceinline__ void unpack8(const Chunk<T, kE>& h, float (&v)[kE]) {
-#pragma unroll
-  for (int i = 0; i < kE; ++i) v[i] = h.get(i);
-}
-
-// One chunk of an operand as values of the data dtype T (held in fp32): plain T, or A2 of codes TIn — (q + round(o)) * s in fp32
-// (two roundings, no FMA), rounded once to T. `o` is already rounded. NT: a streamed operand (nt hint); a broadcast one is re-read
-// by every row and stays in the caches.
-template <typename T, typename TIn, bool DEQ, bool NT = true>
-__device__ __forceinline__ void operand_chunk(const TIn* p, float s, float o, float (&v)[kE]) {
-  if constexpr (DEQ) {
-    Chunk<TIn, kE> q;
-    if constexpr (NT) q.FFQ_SLOAD(p); else q.load(p);
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-      const float a = q.get(i) + o;
-      v[i] = a * s;
-    }
-    Chunk<T, kE> h;
-    h.pack(v);
-    unpack8(h, v);
-  } else {
-    Chunk<T, kE> h;
-    if constexpr (NT) h.FFQ_SLOAD(reinterpret_cast<const T*>(p)); else h.load(reinterpret_cast<const T*>(p));
-    unpack8(h, v);
-  }
-}
-
-// Parameters of an operand: one pair, or one per run of `by_run.div` chunks (a row of the last dimension).
-struct OperandParams {
-  const float* scale;
-  const float* offset;
-  uint32_t per_row;
-  FastDiv by_run;
-};
-
-template <bool DEQ>
-__device__ __forceinline__ void params_at(const OperandParams& p, uint32_t chunk, float& s, float& o) {
-  if constexpr (DEQ) {
-    const uint32_t r = p.per_row ? fdiv(chunk, p.by_run) : 0u;
-    s = p.scale[r];
-    o = p.offset ? rne(p.offset[r]) : 0.0f;
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------
 // E1: add / sub / mul / div + A1:   z = T(op(A, B)),   codes_j = A1(z; s_j, o_j).
@@ -127,11 +71,7 @@ __global__ __launch_bounds__(kEwBlock) void binary_quantize_kernel(const TA* __r
 #pragma unroll
       for (int i = 0; i < kE; ++i) z[i] = va[i] / vb[i];
     }
-    Chunk<T, kE> y;
-    y.pack(z);  // the one rounding to the data dtype
-    if (out) y.FFQ_SSTORE(out + (size_t)c * kE);
-    unpack8(y, z);
-    fan_store(f, fp, z, (size_t)c * kE);
+    store_chunk<T>(out, f, fp, z, (size_t)c * kE);
   }
 }
 
@@ -153,11 +93,7 @@ __global__ __launch_bounds__(kBlock) void softmax_quantize_kernel(const TIn* __r
   if (row >= rows) return;  // block-uniform when WPR == 4
   const size_t base = (size_t)row * chunks_per_row * kE;
   float s = 1.0f, o = 0.0f;
-  if constexpr (DEQ) {
-    const uint32_t p = per_row ? row : 0u;
-    s = xs[p];
-    o = xo ? rne(xo[p]) : 0.0f;
-  }
+  row_params<DEQ>(xs, xo, per_row, row, s, o);
   float v[CPL][kE];
   float m = -INFINITY;
 #pragma unroll
@@ -189,6 +125,7 @@ __global__ __launch_bounds__(kBlock) void softmax_quantize_kernel(const TIn* __r
     }
     acc = acc + part;
   }
+  // (wave_sum's and store_chunk's steps stay spelled out in this kernel: through the helpers the compiler allocates its registers differently)
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc = acc + __shfl_xor(acc, d, 64);
   if constexpr (WPR > 1) {
@@ -205,9 +142,9 @@ __global__ __launch_bounds__(kBlock) void softmax_quantize_kernel(const TIn* __r
 #pragma unroll
     for (int i = 0; i < kE; ++i) z[i] = v[u][i] / acc;
     Chunk<T, kE> zc;
-    zc.pack(z);  // the one rounding to the data dtype
+    zc.pack(z);
     if (out) zc.FFQ_SSTORE(out + base + (size_t)c * kE);
-    unpack8(zc, z);
+    unpack(zc, z);
     fan_store(f, p, z, base + (size_t)c * kE);
   }
 }
@@ -249,35 +186,12 @@ __global__ __launch_bounds__(kEwBlock) void activation_quantize_kernel(const TIn
     operand_chunk<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
 #pragma unroll
     for (int i = 0; i < kE; ++i) v[i] = activation<OP>(v[i]);
-    Chunk<T, kE> y;
+    Chunk<T, kE> y;  // (store_chunk's steps, spelled out: the helper flips a branch of the GELU forms)
     y.pack(v);
     if (out) y.FFQ_SSTORE(out + (size_t)c * kE);
-    unpack8(y, v);
+    unpack(y, v);
     fan_store(f, fp, v, (size_t)c * kE);
   }
-}
-
-static bool value_dtype(int dt) { return dt == FFQ_BF16 || dt == FFQ_F16; }
-
-// The host checks of one streamed operand: plain `dt`, or codes of int8 / `dt` with a scale and one parameter pair or one per run
-// of `run` elements (run % 8 == 0, run divides numel).
-static int check_operand(const char* what, int x_dt, const float* scale, const float* offset, int64_t run, int dt, int64_t numel) {
-  if (run < 0) return fail(FFQ_ERR_ARG, "%s: negative parameter run", what);
-  const bool deq = scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || offset || run))
-    return fail(FFQ_ERR_DTYPE, "%s: a plain operand of the value dtype, or int8 / value-dtype codes with a scale", what);
-  if (run && (run % kE != 0 || numel % run != 0 || numel / run >= ((int64_t)1 << 31)))
-    return fail(FFQ_ERR_DTYPE, "%s: per-row parameters need a row length that divides numel and is a multiple of 8", what);
-  return FFQ_OK;
-}
-
-static OperandParams operand_params(const float* scale, const float* offset, int64_t run) {
-  OperandParams p;
-  p.scale = scale;
-  p.offset = offset;
-  p.per_row = run ? 1u : 0u;
-  p.by_run = make_fastdiv(run ? (uint32_t)(run / kE) : 1u);
-  return p;
 }
 
 static unsigned stream_grid(uint32_t nchunks) { return (unsigned)((nchunks + kEwBlock - 1) / kEwBlock); }
@@ -296,23 +210,20 @@ extern "C" int ffq_binary_quantize(int op, const void* a, int a_dt, const float*
   if ((op == kMul || op == kDiv) && alpha != 1.0) return fail(FFQ_ERR_ARG, "alpha belongs to add / sub");
   if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused add / sub / mul / div is built for bf16 / fp16 values");
   if (numel % kE != 0 || numel >= ((int64_t)1 << 35)) return fail(FFQ_ERR_DTYPE, "fused add / sub / mul / div needs numel %% 8 == 0 and numel < 2^35");
-  int rc = check_operand("input", a_dt, a_scale, a_offset, a_param_run, dt, numel);
+  int rc = check_operand("input", a_dt, a_scale, a_offset, a_param_run, dt, numel, kRowLimit);
   if (rc) return rc;
   if (b) {
     if (numel && (b_numel == 0 || numel % b_numel != 0))
       return fail(FFQ_ERR_TILE_DIVIDE, "other's numel (%lld) must divide input's (%lld)", (long long)b_numel, (long long)numel);
     if (b_numel % kE != 0) return fail(FFQ_ERR_DTYPE, "fused add / sub / mul / div needs other's numel %% 8 == 0");
-    rc = check_operand("other", b_dt, b_scale, b_offset, b_param_run, dt, b_numel);
+    rc = check_operand("other", b_dt, b_scale, b_offset, b_param_run, dt, b_numel, kRowLimit);
     if (rc) return rc;
   } else if (b_scale || b_offset || b_param_run || b_numel) {
     return fail(FFQ_ERR_ARG, "a scalar other has no parameters and no extent");
   }
   FanOut f;
-  rc = fan_from_abi(fan, numel, &f);
-  if (rc) return rc;
-  if (numel == 0) return FFQ_OK;
-  if (!a) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(a) || (b && !aligned16(b)) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, numel, numel == 0, a, {a, b, out}, &f);
+  if (rc || numel == 0) return rc;
   BinArgs g;
   g.pa = operand_params(a_scale, a_offset, a_param_run);
   g.pb = operand_params(b_scale, b_offset, b_param_run);
@@ -337,21 +248,17 @@ extern "C" int ffq_binary_quantize(int op, const void* a, int a_dt, const float*
     g.scalar = (float)(1.0 / scalar);
   }
   const unsigned grid = stream_grid(g.nchunks);
-#define FFQ_E1(T, TA, DA, TB, DB, SC) \
-  binary_quantize_kernel<T, TA, DA, TB, DB, SC><<<grid, kEwBlock, 0, s>>>(static_cast<const TA*>(a), static_cast<const TB*>(b), g, static_cast<T*>(out), f)
-#define FFQ_E1_B(T, TA, DA)                                           \
-  if (!b) { FFQ_E1(T, TA, DA, T, false, true); }                      \
-  else if (!b_scale) { FFQ_E1(T, TA, DA, T, false, false); }           \
-  else if (b_dt == FFQ_I8) { FFQ_E1(T, TA, DA, int8_t, true, false); } \
-  else { FFQ_E1(T, TA, DA, T, true, false); }
-#define FFQ_E1_A(T)                                       \
-  if (!a_scale) { FFQ_E1_B(T, T, false) }                  \
-  else if (a_dt == FFQ_I8) { FFQ_E1_B(T, int8_t, true) }   \
-  else { FFQ_E1_B(T, T, true) }
-  if (dt == FFQ_BF16) { FFQ_E1_A(bf16_t) } else { FFQ_E1_A(f16_t) }
-#undef FFQ_E1_A
-#undef FFQ_E1_B
-#undef FFQ_E1
+  dispatch_input(dt, a_dt, a_scale != nullptr, [&](auto t, auto ta, auto da) {
+    using T = typename decltype(t)::type;
+    using TA = typename decltype(ta)::type;
+    auto launch = [&](auto tb, auto db, auto scalar_b) {
+      using TB = typename decltype(tb)::type;
+      binary_quantize_kernel<T, TA, decltype(da)::value, TB, decltype(db)::value, decltype(scalar_b)::value><<<grid, kEwBlock, 0, s>>>(
+          static_cast<const TA*>(a), static_cast<const TB*>(b), g, static_cast<T*>(out), f);
+    };
+    if (!b) launch(t, std::false_type{}, std::true_type{});
+    else dispatch_form<T>(b_dt, b_scale != nullptr, [&](auto tb, auto db) { launch(tb, db, std::false_type{}); });
+  });
   return check_launch("binary_quantize_kernel");
 }
 
@@ -360,37 +267,25 @@ extern "C" int ffq_softmax_quantize(const void* x, int x_dt, const float* x_scal
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (rows < 0 || cols < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused softmax is built for bf16 / fp16 values");
-  const bool deq = x_scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || x_offset || x_per_row))
-    return fail(FFQ_ERR_DTYPE, "fused softmax takes a plain input of the value dtype, or int8 / value-dtype codes with a scale");
+  int rc = check_operand_form("fused softmax", x_dt, x_scale, x_offset, x_per_row != 0, dt);
+  if (rc) return rc;
   if (cols % kE != 0 || cols > 16384)
     return fail(FFQ_ERR_DTYPE, "fused softmax needs cols %% 8 == 0 and cols <= 16384 (got %lld)", (long long)cols);
   if (rows >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "too many rows");
   FanOut f;
-  int rc = fan_from_abi(fan, rows * cols, &f);
-  if (rc) return rc;
-  if (rows == 0 || cols == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, rows * cols, rows == 0 || cols == 0, x, {x, out}, &f);
+  if (rc || rows == 0 || cols == 0) return rc;
   const uint32_t cpr = (uint32_t)(cols / kE);
   const uint32_t per_row = x_per_row ? 1u : 0u;
-#define FFQ_E2(T, TIN, DEQ, CPL, WPR)                                                                                     \
-  softmax_quantize_kernel<T, TIN, DEQ, CPL, WPR><<<(unsigned)((rows + 4 / WPR - 1) / (4 / WPR)), kBlock, 0, s>>>(        \
-      static_cast<const TIN*>(x), x_scale, x_offset, per_row, static_cast<T*>(out), f, (uint32_t)rows, cpr)
-#define FFQ_E2_SHAPE(T, TIN, DEQ)                 \
-  if (cpr <= 64) FFQ_E2(T, TIN, DEQ, 1, 1);       \
-  else if (cpr <= 256) FFQ_E2(T, TIN, DEQ, 1, 4); \
-  else if (cpr <= 512) FFQ_E2(T, TIN, DEQ, 2, 4); \
-  else if (cpr <= 1024) FFQ_E2(T, TIN, DEQ, 4, 4); \
-  else FFQ_E2(T, TIN, DEQ, 8, 4)
-#define FFQ_E2_INPUT(T)                                       \
-  if (!deq) { FFQ_E2_SHAPE(T, T, false); }                    \
-  else if (x_dt == FFQ_I8) { FFQ_E2_SHAPE(T, int8_t, true); }  \
-  else { FFQ_E2_SHAPE(T, T, true); }
-  if (dt == FFQ_BF16) { FFQ_E2_INPUT(bf16_t) } else { FFQ_E2_INPUT(f16_t) }
-#undef FFQ_E2_INPUT
-#undef FFQ_E2_SHAPE
-#undef FFQ_E2
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    dispatch_row_shape(cpr, [&](auto cpl, auto wpr) {
+      softmax_quantize_kernel<T, TIn, decltype(deq)::value, decltype(cpl)::value, decltype(wpr)::value>
+          <<<row_grid<decltype(wpr)::value>(rows), kBlock, 0, s>>>(static_cast<const TIn*>(x), x_scale, x_offset, per_row, static_cast<T*>(out), f,
+                                                                   (uint32_t)rows, cpr);
+    });
+  });
   return check_launch("softmax_quantize_kernel");
 }
 
@@ -401,30 +296,24 @@ extern "C" int ffq_activation_quantize(int op, const void* x, int x_dt, const fl
   if (op < kActSigmoid || op > kActGeluTanh) return fail(FFQ_ERR_ARG, "unknown activation %d (0: sigmoid, 1: gelu, 2: gelu tanh)", op);
   if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused sigmoid / GELU is built for bf16 / fp16 values");
   if (numel % kE != 0 || numel >= ((int64_t)1 << 35)) return fail(FFQ_ERR_DTYPE, "fused sigmoid / GELU needs numel %% 8 == 0 and numel < 2^35");
-  int rc = check_operand("input", x_dt, x_scale, x_offset, param_run, dt, numel);
+  int rc = check_operand("input", x_dt, x_scale, x_offset, param_run, dt, numel, kRowLimit);
   if (rc) return rc;
   FanOut f;
-  rc = fan_from_abi(fan, numel, &f);
-  if (rc) return rc;
-  if (numel == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, numel, numel == 0, x, {x, out}, &f);
+  if (rc || numel == 0) return rc;
   const uint32_t nchunks = (uint32_t)(numel / kE);
   const OperandParams px = operand_params(x_scale, x_offset, param_run);
   const unsigned grid = stream_grid(nchunks);
-#define FFQ_E3(T, TIN, DEQ, OP) \
-  activation_quantize_kernel<T, TIN, DEQ, OP><<<grid, kEwBlock, 0, s>>>(static_cast<const TIN*>(x), px, static_cast<T*>(out), f, nchunks)
-#define FFQ_E3_INPUT(T, OP)                              \
-  if (!x_scale) { FFQ_E3(T, T, false, OP); }              \
-  else if (x_dt == FFQ_I8) { FFQ_E3(T, int8_t, true, OP); } \
-  else { FFQ_E3(T, T, true, OP); }
-#define FFQ_E3_OP(T)                                                  \
-  if (op == kActSigmoid) { FFQ_E3_INPUT(T, kActSigmoid) }              \
-  else if (op == kActGeluErf) { FFQ_E3_INPUT(T, kActGeluErf) }         \
-  else { FFQ_E3_INPUT(T, kActGeluTanh) }
-  if (dt == FFQ_BF16) { FFQ_E3_OP(bf16_t) } else { FFQ_E3_OP(f16_t) }
-#undef FFQ_E3_OP
-#undef FFQ_E3_INPUT
-#undef FFQ_E3
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    auto launch = [&](auto form) {
+      activation_quantize_kernel<T, TIn, decltype(deq)::value, decltype(form)::value><<<grid, kEwBlock, 0, s>>>(
+          static_cast<const TIn*>(x), px, static_cast<T*>(out), f, nchunks);
+    };
+    if (op == kActSigmoid) launch(Int<kActSigmoid>{});
+    else if (op == kActGeluErf) launch(Int<kActGeluErf>{});
+    else launch(Int<kActGeluTanh>{});
+  });
   return check_launch("activation_quantize_kernel");
 }

@@ -4,9 +4,7 @@
 // ff.nn.functional.{rms_norm, pow, exp, sin, cos, sum, cumsum} run their generated fallbacks in the reference (_gen/fallback.py:
 // pow :955, sum :993, cumsum :1520, exp :1831, sin :1856, cos :1881, rms_norm :1906): A2 of the quantized input into a data-dtype
 // tensor, the ATen op, A1 of the output quantizer — three launches with a full-size temporary between each. Here each is one pass
-// with the arithmetic of ffq_elementwise.hip: codes are dequantized in registers ((q + round(o)) * s in fp32, rounded to the data
-// dtype, exactly the chain's intermediate tensor), the op runs in fp32 and rounds once to the data dtype, and the value goes through
-// the A1 arithmetic of ffq_affine.h for up to FFQ_MAX_FANOUT static per-tensor quantizers (ffq_fanout.h).
+// under the A2 / op / A1 contract of ffq_onepass.h.
 // ATen's device formulas (torch 2.10, MI355X; each confirmed bit for bit against its kernels on every bf16 / fp16 value):
 //   exp / sin / cos:  expf / sinf / cosf of the fp32 value
 //   pow(v, e):  e == 0: 1;  e == 1: v;  e == 0.5: sqrtf(v);  e == -0.5: rsqrtf(v);  e == -1: 1 / v;  else with e' = dt(e) (ATen
@@ -16,113 +14,26 @@
 //   sum:        an fp32 sum rounded once (ATen accumulates in fp32; the order is the kernel's own here)
 //   cumsum:     ATen's device kernel keeps its running sum in the DATA dtype (up to ~2 of an N(0, 1) row of 4096 bf16 values
 //               away from the exact scan); these kernels keep an fp32 running sum and round each prefix once, as ATen's CPU kernel
-// Chunks are 8 elements: 16 B per lane for bf16 / fp16 values, 8 B for int8 codes. All kernels are HBM-bound streams.
+// All kernels are HBM-bound streams.
 #ifndef FFQ_NT_STREAMS
 #define FFQ_NT_STREAMS 3  // nt loads and stores of the streamed tensors, as ffq_elementwise.hip
 #endif
-#include "ffq_affine.h"
-#include "ffq_common.h"
-#include "ffq_fanout.h"
-#include "ffq_vec.h"
-
-#include <math.h>
+#include "ffq_onepass.h"
 
 namespace ffq {
-namespace math {
 
-constexpr int kE = 8;            // elements per chunk
 constexpr int kStreamBlock = 512;  // the grid-stride kernels' block (as ffq_elementwise.hip)
 constexpr uint32_t kSegmentRows = 64;        // rows a lane of the column reduction walks at least
 constexpr uint32_t kTargetLanes = 256u * 1024u;  // lanes the column reduction aims for (1024 blocks of 256)
 constexpr uint32_t kAllBlocks = 1024;        // first-stage blocks of the full reduction (its workspace: one fp32 each)
 constexpr int kRowsInFlight = 8;             // rows a lane of the column kernels loads before it adds them
 
-template <typename T>
-__device__ __forceinline__ void unpack(const Chunk<T, kE>& h, float (&v)[kE]) {
-#pragma unroll
-  for (int i = 0; i < kE; ++i) v[i] = h.get(i);
-}
-
-// One chunk of the input as values of the data dtype T (held in fp32): plain T, or A2 of codes TIn — (q + round(o)) * s in fp32
-// (two roundings, no FMA), rounded once to T. `o` is already rounded.
-template <typename T, typename TIn, bool DEQ>
-__device__ __forceinline__ void load_values(const TIn* p, float s, float o, float (&v)[kE]) {
-  if constexpr (DEQ) {
-    Chunk<TIn, kE> q;
-    q.FFQ_SLOAD(p);
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-      const float a = q.get(i) + o;
-      v[i] = a * s;
-    }
-    Chunk<T, kE> h;
-    h.pack(v);
-    unpack(h, v);
-  } else {
-    Chunk<T, kE> h;
-    h.FFQ_SLOAD(reinterpret_cast<const T*>(p));
-    unpack(h, v);
-  }
-}
-
-// Parameters of the input: one pair, or one per run of `by_run.div` chunks (a row of the last dimension).
-struct Params {
-  const float* scale;
-  const float* offset;
-  uint32_t per_run;
-  FastDiv by_run;
-};
-
-template <bool DEQ>
-__device__ __forceinline__ void params_at(const Params& p, uint32_t chunk, float& s, float& o) {
-  if constexpr (DEQ) {
-    const uint32_t r = p.per_run ? fdiv(chunk, p.by_run) : 0u;
-    s = p.scale[r];
-    o = p.offset ? rne(p.offset[r]) : 0.0f;
-  }
-}
-
 // chunk `c` of the input as values (its parameters looked up by chunk)
 template <typename T, typename TIn, bool DEQ>
-__device__ __forceinline__ void load_at(const TIn* x, const Params& px, uint32_t c, float (&v)[kE]) {
+__device__ __forceinline__ void load_at(const TIn* x, const OperandParams& px, uint32_t c, float (&v)[kE]) {
   float s = 1.0f, o = 0.0f;
   params_at<DEQ>(px, c, s, o);
-  load_values<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
-}
-
-// The value and the codes of ONE output element (the reductions' results): the arithmetic of quantize_chunk_to_bytes for E = 1.
-template <typename T>
-__device__ __forceinline__ void store_one(T* out, const FanOut& f, const FanParams& p, float acc, size_t at) {
-  const float z[1] = {round_stage(acc, TypeTag<T>::value)};  // the one rounding to the data dtype
-  if (out) out[at] = from_f32<T>(z[0]);
-  const int ilo = (int)f.lo, ihi = (int)f.hi;
-#pragma unroll
-  for (int j = 0; j < FFQ_MAX_FANOUT; ++j) {
-    if (j >= f.n) break;
-    const Divider<1> d(p.s[j]);
-    float r[1];
-    quantize_chunk_with<1, 1>(d, z, p.o[j], r);
-    int v = (int)r[0];
-    v = v < ilo ? ilo : (v > ihi ? ihi : v);
-    f.codes[j][at] = (int8_t)v;
-  }
-}
-
-// 8 fp32 sums -> the data dtype, stored with their codes.
-template <typename T>
-__device__ __forceinline__ void store_chunk(T* out, const FanOut& f, const FanParams& p, float (&z)[kE], size_t at) {
-  Chunk<T, kE> y;
-  y.pack(z);  // the one rounding to the data dtype
-  if (out) y.FFQ_SSTORE(out + at);
-  unpack(y, z);
-  fan_store(f, p, z, at);
-}
-
-// Sum of one value per lane over a wave (butterfly: every lane gets the same, deterministic sum).
-__device__ __forceinline__ float wave_sum(float acc) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc = acc + __shfl_xor(acc, d, 64);
-  return acc;
+  operand_chunk<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -143,18 +54,14 @@ __global__ __launch_bounds__(kBlock) void rms_norm_quantize_kernel(const TIn* __
   if (row >= rows) return;  // block-uniform when WPR == 4
   const size_t base = (size_t)row * chunks_per_row * kE;
   float s = 1.0f, o = 0.0f;
-  if constexpr (DEQ) {
-    const uint32_t p = per_row ? row : 0u;
-    s = xs[p];
-    o = xo ? rne(xo[p]) : 0.0f;
-  }
+  row_params<DEQ>(xs, xo, per_row, row, s, o);
   float v[CPL][kE];
   float acc = 0.0f;
 #pragma unroll
   for (int u = 0; u < CPL; ++u) {
     const uint32_t c = lane + LPR * u;
     if (c >= chunks_per_row) continue;
-    load_values<T, TIn, DEQ>(x + base + (size_t)c * kE, s, o, v[u]);
+    operand_chunk<T, TIn, DEQ>(x + base + (size_t)c * kE, s, o, v[u]);
     float part = 0.0f;
 #pragma unroll
     for (int i = 0; i < kE; ++i) part = part + v[u][i] * v[u][i];
@@ -212,7 +119,7 @@ __device__ __forceinline__ float unary(float v, float e) {
 }
 
 template <typename T, typename TIn, bool DEQ, int FORM>
-__global__ __launch_bounds__(kStreamBlock) void unary_quantize_kernel(const TIn* __restrict__ x, Params px, float exponent,
+__global__ __launch_bounds__(kStreamBlock) void unary_quantize_kernel(const TIn* __restrict__ x, OperandParams px, float exponent,
                                                                       T* __restrict__ out, FanOut f, uint32_t nchunks) {
   const FanParams fp = load_fan(f);
   const uint32_t stride = gridDim.x * (uint32_t)kStreamBlock;
@@ -220,7 +127,7 @@ __global__ __launch_bounds__(kStreamBlock) void unary_quantize_kernel(const TIn*
     float s = 1.0f, o = 0.0f;
     params_at<DEQ>(px, c, s, o);
     float v[kE];
-    load_values<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
+    operand_chunk<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
 #pragma unroll
     for (int i = 0; i < kE; ++i) v[i] = unary<T, FORM>(v[i], exponent);
     store_chunk<T>(out, f, fp, v, (size_t)c * kE);
@@ -238,7 +145,7 @@ __global__ __launch_bounds__(kStreamBlock) void unary_quantize_kernel(const TIn*
 //   Algorithmic bytes / input element: 2 (bf16) or 1 (int8 codes); the output is outer * inner elements.
 // ---------------------------------------------------------------------------------------------------
 template <typename T, typename TIn, bool DEQ, int WPR>
-__global__ __launch_bounds__(kBlock) void reduce_rows_kernel(const TIn* __restrict__ x, Params px, T* __restrict__ out, FanOut f,
+__global__ __launch_bounds__(kBlock) void reduce_rows_kernel(const TIn* __restrict__ x, OperandParams px, T* __restrict__ out, FanOut f,
                                                              uint32_t rows, uint32_t chunks_per_row) {
   constexpr uint32_t LPR = 64u * WPR;
   const uint32_t lane = threadIdx.x % LPR;
@@ -250,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void reduce_rows_kernel(const TIn* __restri
     float s = 1.0f, o = 0.0f;
     params_at<DEQ>(px, first + c, s, o);
     float v[kE];
-    load_values<T, TIn, DEQ>(x + (size_t)(first + c) * kE, s, o, v);
+    operand_chunk<T, TIn, DEQ>(x + (size_t)(first + c) * kE, s, o, v);
     float part = 0.0f;
 #pragma unroll
     for (int i = 0; i < kE; ++i) part = part + v[i];
@@ -274,7 +181,7 @@ struct ColArgs {
 };
 
 template <typename T, typename TIn, bool DEQ, bool FINAL>
-__global__ __launch_bounds__(kBlock) void reduce_cols_kernel(const TIn* __restrict__ x, Params px, ColArgs a, T* __restrict__ out,
+__global__ __launch_bounds__(kBlock) void reduce_cols_kernel(const TIn* __restrict__ x, OperandParams px, ColArgs a, T* __restrict__ out,
                                                              FanOut f, float* __restrict__ partial) {
   const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (t >= a.ncols * a.segments) return;
@@ -343,14 +250,14 @@ __device__ __forceinline__ float block_sum(float acc) {
 }
 
 template <typename T, typename TIn, bool DEQ>
-__global__ __launch_bounds__(kBlock) void reduce_all_kernel(const TIn* __restrict__ x, Params px, uint32_t nchunks, float* __restrict__ partial) {
+__global__ __launch_bounds__(kBlock) void reduce_all_kernel(const TIn* __restrict__ x, OperandParams px, uint32_t nchunks, float* __restrict__ partial) {
   const uint32_t stride = gridDim.x * (uint32_t)kBlock;
   float acc = 0.0f;
   for (uint32_t c = blockIdx.x * (uint32_t)kBlock + threadIdx.x; c < nchunks; c += stride) {
     float s = 1.0f, o = 0.0f;
     params_at<DEQ>(px, c, s, o);
     float v[kE];
-    load_values<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
+    operand_chunk<T, TIn, DEQ>(x + (size_t)c * kE, s, o, v);
     float part = 0.0f;
 #pragma unroll
     for (int i = 0; i < kE; ++i) part = part + v[i];
@@ -377,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void reduce_all_finish_kernel(const float* 
 //   Algorithmic bytes / element: 2 (bf16 input) or 1 (int8 codes) [+ 2 (z)] + 1 per code tensor.
 // ---------------------------------------------------------------------------------------------------
 template <typename T, typename TIn, bool DEQ>
-__global__ __launch_bounds__(kBlock) void scan_rows_kernel(const TIn* __restrict__ x, Params px, T* __restrict__ out, FanOut f,
+__global__ __launch_bounds__(kBlock) void scan_rows_kernel(const TIn* __restrict__ x, OperandParams px, T* __restrict__ out, FanOut f,
                                                            uint32_t chunks_per_row) {
   const uint32_t row = blockIdx.x;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -393,7 +300,7 @@ __global__ __launch_bounds__(kBlock) void scan_rows_kernel(const TIn* __restrict
     if (c < chunks_per_row) {
       float s = 1.0f, o = 0.0f;
       params_at<DEQ>(px, first + c, s, o);
-      load_values<T, TIn, DEQ>(x + (size_t)(first + c) * kE, s, o, v);
+      operand_chunk<T, TIn, DEQ>(x + (size_t)(first + c) * kE, s, o, v);
     }
 #pragma unroll
     for (int i = 1; i < kE; ++i) v[i] = v[i - 1] + v[i];
@@ -422,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void scan_rows_kernel(const TIn* __restrict
 }
 
 template <typename T, typename TIn, bool DEQ>
-__global__ __launch_bounds__(kBlock) void scan_cols_kernel(const TIn* __restrict__ x, Params px, ColArgs a, T* __restrict__ out, FanOut f) {
+__global__ __launch_bounds__(kBlock) void scan_cols_kernel(const TIn* __restrict__ x, OperandParams px, ColArgs a, T* __restrict__ out, FanOut f) {
   const uint32_t col = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (col >= a.ncols) return;
   const uint32_t o_idx = fdiv(col, a.by_inner_chunks);
@@ -457,29 +364,6 @@ __global__ __launch_bounds__(kBlock) void scan_cols_kernel(const TIn* __restrict
     }
     store_chunk<T>(out, f, fp, v, (size_t)c * kE);
   }
-}
-
-static bool value_dtype(int dt) { return dt == FFQ_BF16 || dt == FFQ_F16; }
-
-// The host checks of the input: plain `dt`, or codes of int8 / `dt` with a scale and one parameter pair or one per run of `run`
-// elements (run % 8 == 0, run divides numel).
-static int check_input(const char* what, int x_dt, const float* scale, const float* offset, int64_t run, int dt, int64_t numel) {
-  if (run < 0) return fail(FFQ_ERR_ARG, "%s: negative parameter run", what);
-  const bool deq = scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || offset || run))
-    return fail(FFQ_ERR_DTYPE, "%s takes a plain input of the value dtype, or int8 / value-dtype codes with a scale", what);
-  if (run && (run % kE != 0 || numel % run != 0))
-    return fail(FFQ_ERR_DTYPE, "%s: per-row parameters need a row length that divides numel and is a multiple of 8", what);
-  return FFQ_OK;
-}
-
-static Params make_params(const float* scale, const float* offset, int64_t run) {
-  Params p;
-  p.scale = scale;
-  p.offset = offset;
-  p.per_run = run ? 1u : 0u;
-  p.by_run = make_fastdiv(run ? (uint32_t)(run / kE) : 1u);
-  return p;
 }
 
 static unsigned blocks_for(uint64_t lanes, unsigned block) { return (unsigned)((lanes + block - 1) / block); }
@@ -519,51 +403,36 @@ static int check_axes(const char* what, int64_t outer, int64_t len, int64_t inne
   return FFQ_OK;
 }
 
-}  // namespace math
 }  // namespace ffq
 
 using namespace ffq;
-using namespace ffq::math;
 
 extern "C" int ffq_rms_norm_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int x_per_row,
                                      const void* weight, int dt, int64_t rows, int64_t cols, double eps, void* out,
                                      const ffq_fanout* fan, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (rows < 0 || cols < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (!math::value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused rms_norm is built for bf16 / fp16 values");
-  const bool deq = x_scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || x_offset || x_per_row))
-    return fail(FFQ_ERR_DTYPE, "fused rms_norm takes a plain input of the value dtype, or int8 / value-dtype codes with a scale");
+  if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused rms_norm is built for bf16 / fp16 values");
+  int rc = check_operand_form("fused rms_norm", x_dt, x_scale, x_offset, x_per_row != 0, dt);
+  if (rc) return rc;
   if (cols == 0) return fail(FFQ_ERR_EMPTY, "rms_norm over an empty row");
   if (cols % kE != 0 || cols > 16384)
     return fail(FFQ_ERR_DTYPE, "fused rms_norm needs cols %% 8 == 0 and cols <= 16384 (got %lld)", (long long)cols);
   if (rows >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "too many rows");
   FanOut f;
-  int rc = fan_from_abi(fan, rows * cols, &f);
-  if (rc) return rc;
-  if (rows == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (weight && !aligned16(weight)) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, rows * cols, rows == 0, x, {x, weight, out}, &f);
+  if (rc || rows == 0) return rc;
   const uint32_t cpr = (uint32_t)(cols / kE);
   const uint32_t per_row = x_per_row ? 1u : 0u;
-#define FFQ_R1(T, TIN, DEQ, CPL, WPR)                                                                                   \
-  rms_norm_quantize_kernel<T, TIN, DEQ, CPL, WPR><<<(unsigned)((rows + 4 / WPR - 1) / (4 / WPR)), kBlock, 0, s>>>(     \
-      static_cast<const TIN*>(x), x_scale, x_offset, per_row, static_cast<const T*>(weight), static_cast<T*>(out), f, \
-      (uint32_t)rows, cpr, (float)cols, (float)eps)
-#define FFQ_R1_SHAPE(T, TIN, DEQ)                  \
-  if (cpr <= 64) FFQ_R1(T, TIN, DEQ, 1, 1);        \
-  else if (cpr <= 256) FFQ_R1(T, TIN, DEQ, 1, 4);  \
-  else if (cpr <= 512) FFQ_R1(T, TIN, DEQ, 2, 4);  \
-  else if (cpr <= 1024) FFQ_R1(T, TIN, DEQ, 4, 4); \
-  else FFQ_R1(T, TIN, DEQ, 8, 4)
-#define FFQ_R1_INPUT(T)                                        \
-  if (!deq) { FFQ_R1_SHAPE(T, T, false); }                     \
-  else if (x_dt == FFQ_I8) { FFQ_R1_SHAPE(T, int8_t, true); }  \
-  else { FFQ_R1_SHAPE(T, T, true); }
-  if (dt == FFQ_BF16) { FFQ_R1_INPUT(bf16_t) } else { FFQ_R1_INPUT(f16_t) }
-#undef FFQ_R1_INPUT
-#undef FFQ_R1_SHAPE
-#undef FFQ_R1
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    dispatch_row_shape(cpr, [&](auto cpl, auto wpr) {
+      rms_norm_quantize_kernel<T, TIn, decltype(deq)::value, decltype(cpl)::value, decltype(wpr)::value>
+          <<<row_grid<decltype(wpr)::value>(rows), kBlock, 0, s>>>(static_cast<const TIn*>(x), x_scale, x_offset, per_row, static_cast<const T*>(weight),
+                                                                   static_cast<T*>(out), f, (uint32_t)rows, cpr, (float)cols, (float)eps);
+    });
+  });
   return check_launch("rms_norm_quantize_kernel");
 }
 
@@ -573,9 +442,9 @@ extern "C" int ffq_unary_quantize(int op, const void* x, int x_dt, const float* 
   if (numel < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (op < kOpExp || op > kOpPow) return fail(FFQ_ERR_ARG, "unknown unary op %d (0: exp, 1: sin, 2: cos, 3: pow)", op);
   if (op != kOpPow && exponent != 0.0) return fail(FFQ_ERR_ARG, "the exponent belongs to pow");
-  if (!math::value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused exp / sin / cos / pow is built for bf16 / fp16 values");
+  if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused exp / sin / cos / pow is built for bf16 / fp16 values");
   if (numel % kE != 0 || numel >= ((int64_t)1 << 35)) return fail(FFQ_ERR_DTYPE, "fused exp / sin / cos / pow needs numel %% 8 == 0 and numel < 2^35");
-  int rc = check_input("fused exp / sin / cos / pow", x_dt, x_scale, x_offset, param_run, dt, numel);
+  int rc = check_operand("fused exp / sin / cos / pow", x_dt, x_scale, x_offset, param_run, dt, numel, 0);
   if (rc) return rc;
   // ATen's branches (pow_Tensor_Scalar_out, then its device kernel): the exact exponent first, then the one converted to dt
   int form = op == kOpExp ? kFExp : op == kOpSin ? kFSin : op == kOpCos ? kFCos : kFPow;
@@ -592,39 +461,33 @@ extern "C" int ffq_unary_quantize(int op, const void* x, int x_dt, const float* 
     else if (e == -2.0f) form = kFInvSquare;
   }
   FanOut f;
-  rc = fan_from_abi(fan, numel, &f);
-  if (rc) return rc;
-  if (numel == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, numel, numel == 0, x, {x, out}, &f);
+  if (rc || numel == 0) return rc;
   const uint32_t nchunks = (uint32_t)(numel / kE);
-  const Params px = make_params(x_scale, x_offset, param_run);
+  const OperandParams px = operand_params(x_scale, x_offset, param_run);
   const unsigned grid = blocks_for(nchunks, kStreamBlock);
-#define FFQ_U1(T, TIN, DEQ, FORM) \
-  unary_quantize_kernel<T, TIN, DEQ, FORM><<<grid, kStreamBlock, 0, s>>>(static_cast<const TIN*>(x), px, e, static_cast<T*>(out), f, nchunks)
-#define FFQ_U1_INPUT(T, FORM)                                  \
-  if (!x_scale) { FFQ_U1(T, T, false, FORM); }                 \
-  else if (x_dt == FFQ_I8) { FFQ_U1(T, int8_t, true, FORM); }  \
-  else { FFQ_U1(T, T, true, FORM); }
-#define FFQ_U1_FORM(T)                                       \
-  switch (form) {                                            \
-    case kFExp: FFQ_U1_INPUT(T, kFExp) break;                \
-    case kFSin: FFQ_U1_INPUT(T, kFSin) break;                \
-    case kFCos: FFQ_U1_INPUT(T, kFCos) break;                \
-    case kFOne: FFQ_U1_INPUT(T, kFOne) break;                \
-    case kFCopy: FFQ_U1_INPUT(T, kFCopy) break;              \
-    case kFSquare: FFQ_U1_INPUT(T, kFSquare) break;          \
-    case kFCube: FFQ_U1_INPUT(T, kFCube) break;              \
-    case kFSqrt: FFQ_U1_INPUT(T, kFSqrt) break;              \
-    case kFRsqrt: FFQ_U1_INPUT(T, kFRsqrt) break;            \
-    case kFRecip: FFQ_U1_INPUT(T, kFRecip) break;            \
-    case kFInvSquare: FFQ_U1_INPUT(T, kFInvSquare) break;    \
-    default: FFQ_U1_INPUT(T, kFPow) break;                   \
-  }
-  if (dt == FFQ_BF16) { FFQ_U1_FORM(bf16_t) } else { FFQ_U1_FORM(f16_t) }
-#undef FFQ_U1_FORM
-#undef FFQ_U1_INPUT
-#undef FFQ_U1
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    auto launch = [&](auto f_) {
+      unary_quantize_kernel<T, TIn, decltype(deq)::value, decltype(f_)::value><<<grid, kStreamBlock, 0, s>>>(
+          static_cast<const TIn*>(x), px, e, static_cast<T*>(out), f, nchunks);
+    };
+    switch (form) {
+      case kFExp: launch(Int<kFExp>{}); break;
+      case kFSin: launch(Int<kFSin>{}); break;
+      case kFCos: launch(Int<kFCos>{}); break;
+      case kFOne: launch(Int<kFOne>{}); break;
+      case kFCopy: launch(Int<kFCopy>{}); break;
+      case kFSquare: launch(Int<kFSquare>{}); break;
+      case kFCube: launch(Int<kFCube>{}); break;
+      case kFSqrt: launch(Int<kFSqrt>{}); break;
+      case kFRsqrt: launch(Int<kFRsqrt>{}); break;
+      case kFRecip: launch(Int<kFRecip>{}); break;
+      case kFInvSquare: launch(Int<kFInvSquare>{}); break;
+      default: launch(Int<kFPow>{}); break;
+    }
+  });
   return check_launch("unary_quantize_kernel");
 }
 
@@ -637,51 +500,46 @@ extern "C" int ffq_sum_quantize(const void* x, int x_dt, const float* x_scale, c
                                 int64_t outer, int64_t len, int64_t inner, void* out, const ffq_fanout* fan, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!math::value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused sum is built for bf16 / fp16 values");
+  if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused sum is built for bf16 / fp16 values");
   int rc = check_axes("fused sum", outer, len, inner);
   if (rc) return rc;
   const int64_t numel = outer * len * inner;
-  rc = check_input("fused sum", x_dt, x_scale, x_offset, param_run, dt, numel);
+  rc = check_operand("fused sum", x_dt, x_scale, x_offset, param_run, dt, numel, 0);
   if (rc) return rc;
   FanOut f;
   rc = fan_from_abi(fan, outer * inner, &f);
   if (rc) return rc;
   if (outer == 0 || inner == 0) return FFQ_OK;
   if (len == 0) return fail(FFQ_ERR_EMPTY, "a sum over an empty axis is not built (ATen gives zeros)");
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && inner > 1 && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_buffers(x, {x, inner > 1 ? out : nullptr});  // (inner == 1 stores its results one by one)
+  if (rc) return rc;
   const SumPlan plan = sum_plan(outer, len, inner);
   if (plan.workspace && (!workspace || workspace_bytes < plan.workspace || !aligned16(workspace)))
     return fail(FFQ_ERR_WORKSPACE, "fused sum needs %zu bytes of 16-byte aligned workspace", plan.workspace);
   float* partial = static_cast<float*>(workspace);
-  const Params px = make_params(x_scale, x_offset, param_run);
+  const OperandParams px = operand_params(x_scale, x_offset, param_run);
   if (outer * inner == 1) {  // S4 / S5: the whole tensor
     const uint32_t nchunks = (uint32_t)(numel / kE);
-#define FFQ_S4(T, TIN, DEQ)                                                                                         \
-  reduce_all_kernel<T, TIN, DEQ><<<kAllBlocks, kBlock, 0, s>>>(static_cast<const TIN*>(x), px, nchunks, partial); \
-  reduce_all_finish_kernel<T><<<1, kBlock, 0, s>>>(partial, kAllBlocks, static_cast<T*>(out), f)
-#define FFQ_S4_INPUT(T)                                    \
-    if (!x_scale) { FFQ_S4(T, T, false); }                 \
-    else if (x_dt == FFQ_I8) { FFQ_S4(T, int8_t, true); }  \
-    else { FFQ_S4(T, T, true); }
-    if (dt == FFQ_BF16) { FFQ_S4_INPUT(bf16_t) } else { FFQ_S4_INPUT(f16_t) }
-#undef FFQ_S4_INPUT
-#undef FFQ_S4
+    dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+      using T = typename decltype(t)::type;
+      using TIn = typename decltype(tin)::type;
+      reduce_all_kernel<T, TIn, decltype(deq)::value><<<kAllBlocks, kBlock, 0, s>>>(static_cast<const TIn*>(x), px, nchunks, partial);
+      reduce_all_finish_kernel<T><<<1, kBlock, 0, s>>>(partial, kAllBlocks, static_cast<T*>(out), f);
+    });
     return check_launch("reduce_all_kernel");
   }
   if (inner == 1) {  // S1: rows
     if (outer >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "too many rows");
     const uint32_t cpr = (uint32_t)(len / kE);
-#define FFQ_S1(T, TIN, DEQ, WPR)                                                                                        \
-  reduce_rows_kernel<T, TIN, DEQ, WPR><<<(unsigned)((outer + 4 / WPR - 1) / (4 / WPR)), kBlock, 0, s>>>(               \
-      static_cast<const TIN*>(x), px, static_cast<T*>(out), f, (uint32_t)outer, cpr)
-#define FFQ_S1_INPUT(T)                                                                                    \
-    if (!x_scale) { if (cpr <= 64) FFQ_S1(T, T, false, 1); else FFQ_S1(T, T, false, 4); }                  \
-    else if (x_dt == FFQ_I8) { if (cpr <= 64) FFQ_S1(T, int8_t, true, 1); else FFQ_S1(T, int8_t, true, 4); } \
-    else { if (cpr <= 64) FFQ_S1(T, T, true, 1); else FFQ_S1(T, T, true, 4); }
-    if (dt == FFQ_BF16) { FFQ_S1_INPUT(bf16_t) } else { FFQ_S1_INPUT(f16_t) }
-#undef FFQ_S1_INPUT
-#undef FFQ_S1
+    dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+      using T = typename decltype(t)::type;
+      using TIn = typename decltype(tin)::type;
+      auto launch = [&](auto wpr) {
+        reduce_rows_kernel<T, TIn, decltype(deq)::value, decltype(wpr)::value><<<row_grid<decltype(wpr)::value>(outer), kBlock, 0, s>>>(
+            static_cast<const TIn*>(x), px, static_cast<T*>(out), f, (uint32_t)outer, cpr);
+      };
+      if (cpr <= 64) launch(Int<1>{}); else launch(Int<4>{});
+    });
     return check_launch("reduce_rows_kernel");
   }
   // S2 / S3: columns
@@ -694,51 +552,41 @@ extern "C" int ffq_sum_quantize(const void* x, int x_dt, const float* x_scale, c
   a.by_ncols = make_fastdiv(a.ncols);
   a.by_inner_chunks = make_fastdiv(a.inner_chunks);
   const unsigned grid = blocks_for((uint64_t)a.ncols * a.segments, kBlock);
-#define FFQ_S2(T, TIN, DEQ)                                                                                                     \
-  if (a.segments == 1) {                                                                                                        \
-    reduce_cols_kernel<T, TIN, DEQ, true><<<grid, kBlock, 0, s>>>(static_cast<const TIN*>(x), px, a, static_cast<T*>(out), f, nullptr); \
-  } else {                                                                                                                      \
-    reduce_cols_kernel<T, TIN, DEQ, false><<<grid, kBlock, 0, s>>>(static_cast<const TIN*>(x), px, a, nullptr, f, partial);    \
-    reduce_cols_finish_kernel<T><<<blocks_for(a.ncols, kBlock), kBlock, 0, s>>>(partial, a.ncols, a.segments, static_cast<T*>(out), f); \
-  }
-#define FFQ_S2_INPUT(T)                                  \
-  if (!x_scale) { FFQ_S2(T, T, false) }                  \
-  else if (x_dt == FFQ_I8) { FFQ_S2(T, int8_t, true) }   \
-  else { FFQ_S2(T, T, true) }
-  if (dt == FFQ_BF16) { FFQ_S2_INPUT(bf16_t) } else { FFQ_S2_INPUT(f16_t) }
-#undef FFQ_S2_INPUT
-#undef FFQ_S2
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    constexpr bool DEQ = decltype(deq)::value;
+    if (a.segments == 1) {
+      reduce_cols_kernel<T, TIn, DEQ, true><<<grid, kBlock, 0, s>>>(static_cast<const TIn*>(x), px, a, static_cast<T*>(out), f, nullptr);
+    } else {
+      reduce_cols_kernel<T, TIn, DEQ, false><<<grid, kBlock, 0, s>>>(static_cast<const TIn*>(x), px, a, nullptr, f, partial);
+      reduce_cols_finish_kernel<T><<<blocks_for(a.ncols, kBlock), kBlock, 0, s>>>(partial, a.ncols, a.segments, static_cast<T*>(out), f);
+    }
+  });
   return check_launch("reduce_cols_kernel");
 }
 
 extern "C" int ffq_cumsum_quantize(const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_run, int dt,
                                    int64_t outer, int64_t len, int64_t inner, void* out, const ffq_fanout* fan, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!math::value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused cumsum is built for bf16 / fp16 values");
+  if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused cumsum is built for bf16 / fp16 values");
   int rc = check_axes("fused cumsum", outer, len, inner);
   if (rc) return rc;
   const int64_t numel = outer * len * inner;
-  rc = check_input("fused cumsum", x_dt, x_scale, x_offset, param_run, dt, numel);
+  rc = check_operand("fused cumsum", x_dt, x_scale, x_offset, param_run, dt, numel, 0);
   if (rc) return rc;
   FanOut f;
-  rc = fan_from_abi(fan, numel, &f);
-  if (rc) return rc;
-  if (numel == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
-  const Params px = make_params(x_scale, x_offset, param_run);
+  rc = check_launch_args(fan, numel, numel == 0, x, {x, out}, &f);
+  if (rc || numel == 0) return rc;
+  const OperandParams px = operand_params(x_scale, x_offset, param_run);
   if (inner == 1) {  // C1: rows
     if (outer >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "too many rows");
     const uint32_t cpr = (uint32_t)(len / kE);
-#define FFQ_C1(T, TIN, DEQ) \
-  scan_rows_kernel<T, TIN, DEQ><<<(unsigned)outer, kBlock, 0, s>>>(static_cast<const TIN*>(x), px, static_cast<T*>(out), f, cpr)
-#define FFQ_C1_INPUT(T)                                    \
-    if (!x_scale) { FFQ_C1(T, T, false); }                 \
-    else if (x_dt == FFQ_I8) { FFQ_C1(T, int8_t, true); }  \
-    else { FFQ_C1(T, T, true); }
-    if (dt == FFQ_BF16) { FFQ_C1_INPUT(bf16_t) } else { FFQ_C1_INPUT(f16_t) }
-#undef FFQ_C1_INPUT
-#undef FFQ_C1
+    dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+      using T = typename decltype(t)::type;
+      using TIn = typename decltype(tin)::type;
+      scan_rows_kernel<T, TIn, decltype(deq)::value><<<(unsigned)outer, kBlock, 0, s>>>(static_cast<const TIn*>(x), px, static_cast<T*>(out), f, cpr);
+    });
     return check_launch("scan_rows_kernel");
   }
   ColArgs a;  // C2: columns
@@ -750,14 +598,10 @@ extern "C" int ffq_cumsum_quantize(const void* x, int x_dt, const float* x_scale
   a.by_ncols = make_fastdiv(a.ncols);
   a.by_inner_chunks = make_fastdiv(a.inner_chunks);
   const unsigned grid = blocks_for(a.ncols, kBlock);
-#define FFQ_C2(T, TIN, DEQ) \
-  scan_cols_kernel<T, TIN, DEQ><<<grid, kBlock, 0, s>>>(static_cast<const TIN*>(x), px, a, static_cast<T*>(out), f)
-#define FFQ_C2_INPUT(T)                                  \
-  if (!x_scale) { FFQ_C2(T, T, false); }                 \
-  else if (x_dt == FFQ_I8) { FFQ_C2(T, int8_t, true); }  \
-  else { FFQ_C2(T, T, true); }
-  if (dt == FFQ_BF16) { FFQ_C2_INPUT(bf16_t) } else { FFQ_C2_INPUT(f16_t) }
-#undef FFQ_C2_INPUT
-#undef FFQ_C2
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    scan_cols_kernel<T, TIn, decltype(deq)::value><<<grid, kBlock, 0, s>>>(static_cast<const TIn*>(x), px, a, static_cast<T*>(out), f);
+  });
   return check_launch("scan_cols_kernel");
 }

@@ -3,49 +3,18 @@
 // QuantizedLayerNorm / QuantizedEmbedding / QuantizedRelu / QuantizedSilu (reference nn/normalization.py, nn/embedding.py,
 // nn/activations.py) run their generated fallbacks (_gen/fallback.py: relu :296, embedding :616, layer_norm :655, silu :1348):
 // A2 of the quantized operand into a data-dtype tensor, the ATen op, A1 of the output quantizer — three launches, each a full
-// pass over HBM with a temporary in between. Here each is one pass: the operand's codes are dequantized in registers with the
-// arithmetic of ffq_dequantize.hip ((q + round(o)) * s in fp32, rounded to the data dtype), the op rounds to the data dtype as
-// ATen does, and the value goes through the A1 arithmetic of ffq_affine.h for up to FFQ_MAX_FANOUT static per-tensor
-// quantizers (ffq_fanout.h). The value itself is stored only when the caller asks for it.
-// Chunks are 8 elements: 16 B per lane for bf16 / fp16 values, 8 B for int8 codes. Algorithmic bytes per element are stated at
-// each kernel; all three are HBM-bound streams.
+// pass over HBM with a temporary in between. Here each is one pass under the A2 / op / A1 contract of ffq_onepass.h.
+// Algorithmic bytes per element are stated at each kernel; all three are HBM-bound streams.
 #ifndef FFQ_NT_STREAMS
 #define FFQ_NT_STREAMS 3  // nt loads and stores of the streamed tensors, as ffq_producers.hip
 #endif
 #ifndef FFQ_MODULES_GRID
 #define FFQ_MODULES_GRID 1024  // blocks of the table-driven SiLU kernel: two 512-thread blocks per CU, twice over
 #endif
-#include "ffq_affine.h"
-#include "ffq_common.h"
-#include "ffq_fanout.h"
+#include "ffq_onepass.h"
 #include "ffq_silu.h"
-#include "ffq_vec.h"
-
-#include <math.h>
 
 namespace ffq {
-
-constexpr int kE = 8;  // elements per chunk
-
-// A2 of one chunk into the data dtype T: (q + round(o)) * s in fp32 (two roundings, no FMA), rounded once to T. `o` is rounded.
-template <typename T, typename TIn>
-__device__ __forceinline__ Chunk<T, kE> dequantize_chunk(const Chunk<TIn, kE>& q, float s, float o) {
-  float v[kE];
-#pragma unroll
-  for (int i = 0; i < kE; ++i) {
-    const float a = q.get(i) + o;
-    v[i] = a * s;
-  }
-  Chunk<T, kE> h;
-  h.pack(v);
-  return h;
-}
-
-template <typename T>
-__device__ __forceinline__ void unpack(const Chunk<T, kE>& h, float (&v)[kE]) {
-#pragma unroll
-  for (int i = 0; i < kE; ++i) v[i] = h.get(i);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // M1: LayerNorm (F.layer_norm over the last `cols` elements) + A1.
@@ -69,20 +38,18 @@ __global__ __launch_bounds__(kBlock) void layer_norm_quantize_kernel(const TIn* 
   if (row >= rows) return;  // block-uniform when WPR == 4
   const size_t base = (size_t)row * chunks_per_row * kE;
   float s = 1.0f, o = 0.0f;
-  if constexpr (DEQ) {
-    const uint32_t p = per_row ? row : 0u;
-    s = xs[p];
-    o = xo ? rne(xo[p]) : 0.0f;
-  }
+  row_params<DEQ>(xs, xo, per_row, row, s, o);
   Chunk<T, kE> h[CPL];
 #pragma unroll
   for (int u = 0; u < CPL; ++u) {
     const uint32_t c = lane + LPR * u;
     if (c >= chunks_per_row) continue;
-    if constexpr (DEQ) {
+    if constexpr (DEQ) {  // (operand_packed's steps, spelled out: through the helper some of this loop's loads lose their nt hint)
       Chunk<TIn, kE> q;
       q.FFQ_SLOAD(x + base + (size_t)c * kE);
-      h[u] = dequantize_chunk<T>(q, s, o);
+      float v[kE];
+      a2_chunk(q, s, o, v);
+      h[u].pack(v);
     } else {
       h[u].FFQ_SLOAD(reinterpret_cast<const T*>(x) + base + (size_t)c * kE);
     }
@@ -205,7 +172,10 @@ __global__ __launch_bounds__(kBlock) void embedding_quantize_kernel(const TId* _
       const size_t pidx = (a.per_row ? (size_t)id * a.groups_per_row : 0) + (a.groups_per_row > 1 ? fdiv(j, a.by_group_chunks) : 0u);
       const float s = scale[pidx];
       const float o = offset ? rne(offset[pidx]) : 0.0f;
-      unpack(dequantize_chunk<T>(q, s, o), z);
+      a2_chunk(q, s, o, z);
+      Chunk<T, kE> h;
+      h.pack(z);
+      unpack(h, z);
     }
   }
   const size_t at = (size_t)c * kE;
@@ -246,19 +216,14 @@ __global__ __launch_bounds__(kPwBlock) void pointwise_quantize_kernel(const TIn*
   }
   const uint32_t stride = gridDim.x * (uint32_t)kPwBlock;
   for (uint32_t c = blockIdx.x * (uint32_t)kPwBlock + threadIdx.x; c < nchunks; c += stride) {
-    Chunk<T, kE> h;
     if constexpr (DEQ) {
       if (per_row) {
         const uint32_t r = fdiv(c, by_run);
         s = xs[r];
         o = xo ? rne(xo[r]) : 0.0f;
       }
-      Chunk<TIn, kE> q;
-      q.FFQ_SLOAD(x + (size_t)c * kE);
-      h = dequantize_chunk<T>(q, s, o);
-    } else {
-      h.FFQ_SLOAD(reinterpret_cast<const T*>(x) + (size_t)c * kE);
     }
+    const Chunk<T, kE> h = operand_packed<T, TIn, DEQ>(x + (size_t)c * kE, s, o);
     Chunk<T, kE> y;
     if constexpr (TABLE) {
       uint32_t bad = 0;
@@ -288,8 +253,6 @@ __global__ __launch_bounds__(kPwBlock) void pointwise_quantize_kernel(const TIn*
   }
 }
 
-static bool value_dtype(int dt) { return dt == FFQ_BF16 || dt == FFQ_F16; }
-
 }  // namespace ffq
 
 using namespace ffq;
@@ -300,40 +263,27 @@ extern "C" int ffq_layer_norm_quantize(const void* x, int x_dt, const float* x_s
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (rows < 0 || cols < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused LayerNorm is built for bf16 / fp16 values");
-  const bool deq = x_scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || x_offset || x_per_row))
-    return fail(FFQ_ERR_DTYPE, "fused LayerNorm takes a plain input of the value dtype, or int8 / value-dtype codes with a scale");
+  int rc = check_operand_form("fused LayerNorm", x_dt, x_scale, x_offset, x_per_row != 0, dt);
+  if (rc) return rc;
   if (cols == 0) return fail(FFQ_ERR_EMPTY, "LayerNorm over an empty row");
   if (cols % kE != 0 || cols > 16384)
     return fail(FFQ_ERR_DTYPE, "fused LayerNorm needs cols %% 8 == 0 and cols <= 16384 (got %lld)", (long long)cols);
   if (rows >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "too many rows");
   FanOut f;
-  int rc = fan_from_abi(fan, rows * cols, &f);
-  if (rc) return rc;
-  if (rows == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (weight && !aligned16(weight)) || (bias && !aligned16(bias)) || (out && !aligned16(out)))
-    return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, rows * cols, rows == 0, x, {x, weight, bias, out}, &f);
+  if (rc || rows == 0) return rc;
   const uint32_t cpr = (uint32_t)(cols / kE);
   const uint32_t per_row = x_per_row ? 1u : 0u;
-#define FFQ_M1(T, TIN, DEQ, CPL, WPR)                                                                                   \
-  layer_norm_quantize_kernel<T, TIN, DEQ, CPL, WPR><<<(unsigned)((rows + 4 / WPR - 1) / (4 / WPR)), kBlock, 0, s>>>( \
-      static_cast<const TIN*>(x), x_scale, x_offset, per_row, static_cast<const T*>(weight), static_cast<const T*>(bias), \
-      static_cast<T*>(out), f, (uint32_t)rows, cpr, (float)cols, (float)eps)
-#define FFQ_M1_SHAPE(T, TIN, DEQ)               \
-  if (cpr <= 64) FFQ_M1(T, TIN, DEQ, 1, 1);     \
-  else if (cpr <= 256) FFQ_M1(T, TIN, DEQ, 1, 4); \
-  else if (cpr <= 512) FFQ_M1(T, TIN, DEQ, 2, 4); \
-  else if (cpr <= 1024) FFQ_M1(T, TIN, DEQ, 4, 4); \
-  else FFQ_M1(T, TIN, DEQ, 8, 4)
-#define FFQ_M1_INPUT(T)                                      \
-  if (!deq) { FFQ_M1_SHAPE(T, T, false); }                   \
-  else if (x_dt == FFQ_I8) { FFQ_M1_SHAPE(T, int8_t, true); } \
-  else { FFQ_M1_SHAPE(T, T, true); }
-  if (dt == FFQ_BF16) { FFQ_M1_INPUT(bf16_t) } else { FFQ_M1_INPUT(f16_t) }
-#undef FFQ_M1_INPUT
-#undef FFQ_M1_SHAPE
-#undef FFQ_M1
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    dispatch_row_shape(cpr, [&](auto cpl, auto wpr) {
+      layer_norm_quantize_kernel<T, TIn, decltype(deq)::value, decltype(cpl)::value, decltype(wpr)::value>
+          <<<row_grid<decltype(wpr)::value>(rows), kBlock, 0, s>>>(static_cast<const TIn*>(x), x_scale, x_offset, per_row, static_cast<const T*>(weight),
+                                                                   static_cast<const T*>(bias), static_cast<T*>(out), f, (uint32_t)rows, cpr,
+                                                                   (float)cols, (float)eps);
+    });
+  });
   return check_launch("layer_norm_quantize_kernel");
 }
 
@@ -369,19 +319,21 @@ extern "C" int ffq_embedding_quantize(const void* ids, int ids_dt, int64_t n_ids
   a.by_dchunks = make_fastdiv(a.dchunks);
   a.by_group_chunks = make_fastdiv(group == 1 ? 1u : (uint32_t)(group / kE));
   const unsigned grid = (unsigned)((nchunks + kBlock - 1) / kBlock);
-#define FFQ_M2(T, TIN, TID, PC) \
-  embedding_quantize_kernel<T, TIN, TID, PC><<<grid, kBlock, 0, s>>>(static_cast<const TID*>(ids), static_cast<const TIN*>(table), scale, offset, a, static_cast<T*>(out), f, bad_id)
-#define FFQ_M2_IDS(T, TIN, PC) \
-  if (ids_dt == FFQ_I64) FFQ_M2(T, TIN, int64_t, PC); else FFQ_M2(T, TIN, int32_t, PC)
-#define FFQ_M2_PARAMS(T, TIN) \
-  if (group == 1) { FFQ_M2_IDS(T, TIN, true); } else { FFQ_M2_IDS(T, TIN, false); }
-#define FFQ_M2_TABLE(T) \
-  if (table_dt == FFQ_I8) { FFQ_M2_PARAMS(T, int8_t) } else { FFQ_M2_PARAMS(T, T) }
-  if (dt == FFQ_BF16) { FFQ_M2_TABLE(bf16_t) } else { FFQ_M2_TABLE(f16_t) }
-#undef FFQ_M2_TABLE
-#undef FFQ_M2_PARAMS
-#undef FFQ_M2_IDS
-#undef FFQ_M2
+  dispatch_dtype(dt, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_form<T>(table_dt, true, [&](auto tin, auto) {  // (the table is always codes)
+      using TIn = typename decltype(tin)::type;
+      auto launch = [&](auto tid, auto per_column) {
+        using TId = typename decltype(tid)::type;
+        embedding_quantize_kernel<T, TIn, TId, decltype(per_column)::value><<<grid, kBlock, 0, s>>>(
+            static_cast<const TId*>(ids), static_cast<const TIn*>(table), scale, offset, a, static_cast<T*>(out), f, bad_id);
+      };
+      auto by_ids = [&](auto per_column) {
+        if (ids_dt == FFQ_I64) launch(Tag<int64_t>{}, per_column); else launch(Tag<int32_t>{}, per_column);
+      };
+      if (group == 1) by_ids(std::true_type{}); else by_ids(std::false_type{});
+    });
+  });
   return check_launch("embedding_quantize_kernel");
 }
 
@@ -391,39 +343,30 @@ extern "C" int ffq_pointwise_quantize(int op, const void* x, int x_dt, const flo
   if (numel < 0 || param_run < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (op != kOpRelu && op != kOpSilu) return fail(FFQ_ERR_ARG, "unknown pointwise op %d (0: relu, 1: silu)", op);
   if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "fused ReLU / SiLU is built for bf16 / fp16 values");
-  const bool deq = x_scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || x_offset || param_run))
-    return fail(FFQ_ERR_DTYPE, "fused ReLU / SiLU takes a plain input of the value dtype, or int8 / value-dtype codes with a scale");
   if (numel % kE != 0 || numel >= ((int64_t)1 << 35)) return fail(FFQ_ERR_DTYPE, "fused ReLU / SiLU needs numel %% 8 == 0 and numel < 2^35");
-  if (param_run && (param_run % kE != 0 || numel % param_run != 0 || numel / param_run >= ((int64_t)1 << 31)))
-    return fail(FFQ_ERR_DTYPE, "per-row parameters need a row length that divides numel and is a multiple of 8");
-  FanOut f;
-  int rc = fan_from_abi(fan, numel, &f);
+  int rc = check_operand("fused ReLU / SiLU", x_dt, x_scale, x_offset, param_run, dt, numel, kRowLimit);
   if (rc) return rc;
-  if (numel == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  FanOut f;
+  rc = check_launch_args(fan, numel, numel == 0, x, {x, out}, &f);
+  if (rc || numel == 0) return rc;
   const uint32_t nchunks = (uint32_t)(numel / kE);
   const uint32_t per_row = param_run ? 1u : 0u;
   const FastDiv by_run = make_fastdiv(param_run ? (uint32_t)(param_run / kE) : 1u);
   // the table pays from ~4 chunks per thread of a two-blocks-per-CU grid on (as in ffq_producers.hip)
   const bool table = op == kOpSilu && dt == FFQ_BF16 && nchunks >= 4u * kPwBlock * 512u;
   const unsigned grid = table ? FFQ_MODULES_GRID : (unsigned)((nchunks + kPwBlock - 1) / kPwBlock);
-#define FFQ_M3(T, TIN, DEQ, OP, TAB) \
-  pointwise_quantize_kernel<T, TIN, DEQ, OP, TAB><<<grid, kPwBlock, 0, s>>>(static_cast<const TIN*>(x), x_scale, x_offset, per_row, by_run, static_cast<T*>(out), f, nchunks)
-#define FFQ_M3_INPUT(T, OP, TAB)                                  \
-  if (!deq) { FFQ_M3(T, T, false, OP, TAB); }                     \
-  else if (x_dt == FFQ_I8) { FFQ_M3(T, int8_t, true, OP, TAB); }  \
-  else { FFQ_M3(T, T, true, OP, TAB); }
-  if (dt == FFQ_BF16) {
-    if (op == kOpRelu) { FFQ_M3_INPUT(bf16_t, kOpRelu, false) }
-    else if (table) { FFQ_M3_INPUT(bf16_t, kOpSilu, true) }
-    else { FFQ_M3_INPUT(bf16_t, kOpSilu, false) }
-  } else {
-    if (op == kOpRelu) { FFQ_M3_INPUT(f16_t, kOpRelu, false) }
-    else { FFQ_M3_INPUT(f16_t, kOpSilu, false) }
-  }
-#undef FFQ_M3_INPUT
-#undef FFQ_M3
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    auto launch = [&](auto op_, auto tab) {
+      pointwise_quantize_kernel<T, TIn, decltype(deq)::value, decltype(op_)::value, decltype(tab)::value><<<grid, kPwBlock, 0, s>>>(
+          static_cast<const TIn*>(x), x_scale, x_offset, per_row, by_run, static_cast<T*>(out), f, nchunks);
+    };
+    if (op == kOpRelu) return launch(Int<kOpRelu>{}, std::false_type{});
+    if constexpr (std::is_same_v<T, bf16_t>) {  // (the table holds bf16 silu)
+      if (table) return launch(Int<kOpSilu>{}, std::true_type{});
+    }
+    launch(Int<kOpSilu>{}, std::false_type{});
+  });
   return check_launch("pointwise_quantize_kernel");
 }

@@ -4,10 +4,8 @@
 // ff.nn.functional.{avg_pool1d, avg_pool2d, max_pool2d, interpolate} run their generated fallbacks in the reference
 // (_gen/fallback.py: avg_pool1d :505, avg_pool2d :542, max_pool2d :1574, interpolate :1611): A2 of the quantized input into a
 // data-dtype tensor, the ATen op, A1 of the output quantizer — three launches with a full-size temporary between each. Here each is
-// one pass: codes are dequantized in registers ((q + round(o)) * s in fp32, rounded to the data dtype, exactly the chain's
-// intermediate tensor) with the parameters of the element's plane (one pair for the tensor, or one per channel of [B, C, H, W]),
-// the operator runs with ATen's device formula and rounds once to the data dtype, and the value goes through the A1 arithmetic of
-// ffq_affine.h for up to FFQ_MAX_FANOUT static per-tensor quantizers (ffq_fanout.h).
+// one pass under the A2 / op / A1 contract of ffq_onepass.h, with the parameters of the element's plane (one pair for the tensor, or
+// one per channel of [B, C, H, W]).
 // ATen's device formulas (torch 2.10; what the MI355X showed against them is in docs/kernels.md):
 //   avg:      one fp32 accumulator per output, the window walked rows outer / columns inner over the part inside the input, divided
 //             once by the window's size — (hend - hstart) * (wend - wstart) clipped to the input PLUS its padding when
@@ -19,17 +17,10 @@
 // neighbours in memory: the overlap of a 3x3 stride-2 window is served by the caches), so maps of any width keep the lanes busy. The
 // block's results meet in LDS and leave in 8-element groups — 16 B of values, 8 B of codes per lane through ffq_fanout.h; the last
 // group of a result whose size is no multiple of 8 leaves element by element.
-#include "ffq_affine.h"
-#include "ffq_common.h"
-#include "ffq_fanout.h"
-#include "ffq_vec.h"
-
-#include <math.h>
+#include "ffq_onepass.h"
 
 namespace ffq {
 namespace pool {
-
-constexpr int kE = 8;  // elements per stored group
 
 enum { kAvg = 0, kAvgExcludePad = 1, kMax = 2 };  // the ABI's modes (include/ffq.h)
 
@@ -43,21 +34,10 @@ struct Geometry {
   FastDiv by_ow, by_oh, by_channels;
 };
 
-// A2 of one code: (q + round(o)) * s in fp32 (two roundings, no FMA), rounded once to T. `o` is already rounded.
-template <typename T>
-__device__ __forceinline__ float dequantized(float q, float s, float o) {
-  const float a = q + o;
-  float m = a * s;
-  // (the product in a register of its own: hipcc otherwise folds the multiply and the fp16 conversion into v_fma_mixlo_f16 with a
-  // +0 addend, which turns the -0.0 of a code -0.0 under an offset -0.0 into +0.0; seen on the MI355X against the chain's A2)
-  asm volatile("" : "+v"(m));
-  return round_stage(m, TypeTag<T>::value);
-}
-
 template <typename T, typename TIn, bool DEQ>
 __device__ __forceinline__ float value_at(const TIn* p, float s, float o) {
   const float q = to_f32(*p);
-  if constexpr (DEQ) return dequantized<T>(q, s, o);
+  if constexpr (DEQ) return a2_value<T>(q, s, o);
   return q;
 }
 
@@ -106,7 +86,7 @@ __device__ __forceinline__ float pool_one(const TIn* __restrict__ x, const float
           if (q > best || q != q) best = q;
         }
       // (a window inside the input is never empty under ATen's padding rule; -inf stays -inf for one that is)
-      return best == -INFINITY ? best : dequantized<T>(best, p.s, p.o);
+      return best == -INFINITY ? best : a2_value<T>(best, p.s, p.o);
     }
     for (int32_t h = hstart; h < hend; h += g.dh)
       for (int32_t w = wstart; w < wend; w += g.dw) {
@@ -152,7 +132,7 @@ __device__ __forceinline__ void store_tile(const float* z, uint32_t base, uint32
     float v[kE];
 #pragma unroll
     for (int i = 0; i < kE; ++i) v[i] = z[c * kE + i];
-    if (at + kE <= total) {
+    if (at + kE <= total) {  // (store_chunk's and, below, store_one's steps, spelled out: the helpers change this loop's registers)
       Chunk<T, kE> y;
       y.pack(v);  // the one rounding to the data dtype
       if (out) y.store(out + at);
@@ -162,7 +142,7 @@ __device__ __forceinline__ void store_tile(const float* z, uint32_t base, uint32
       continue;
     }
     const int ilo = (int)f.lo, ihi = (int)f.hi;
-    for (uint32_t i = 0; at + i < total; ++i) {  // the arithmetic of quantize_chunk_to_bytes for E = 1
+    for (uint32_t i = 0; at + i < total; ++i) {
       const float one[1] = {round_stage(z[c * kE + i], TypeTag<T>::value)};
       if (out) out[at + i] = from_f32<T>(one[0]);
 #pragma unroll
@@ -216,8 +196,6 @@ __global__ __launch_bounds__(kBlock) void upsample_nearest_quantize_kernel(const
   store_tile<T, J>(z, base, g.total, out, f);
 }
 
-static bool value_dtype(int dt) { return dt == FFQ_BF16 || dt == FFQ_F16; }
-
 // ATen's pooling_output_shape: the last window starts inside the input or its left padding.
 static int64_t pooled(int64_t in, int64_t k, int64_t pad, int64_t stride, int64_t dil, bool ceil_mode) {
   const int64_t num = in + 2 * pad - dil * (k - 1) - 1 + (ceil_mode ? stride - 1 : 0);
@@ -229,10 +207,7 @@ static int64_t pooled(int64_t in, int64_t k, int64_t pad, int64_t stride, int64_
 // The checks both entry points share: dtypes first (before any buffer is looked at), then extents and buffers.
 static int check_dtypes(const char* what, int x_dt, const float* scale, const float* offset, int64_t channels, int dt) {
   if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "%s is built for bf16 / fp16 values", what);
-  const bool deq = scale != nullptr;
-  if (deq ? (x_dt != FFQ_I8 && x_dt != dt) : (x_dt != dt || offset || channels))
-    return fail(FFQ_ERR_DTYPE, "%s takes a plain input of the value dtype, or int8 / value-dtype codes with a scale", what);
-  return FFQ_OK;
+  return check_operand_form(what, x_dt, scale, offset, channels != 0, dt);
 }
 
 static int check_extents(const char* what, int64_t channels, int64_t planes, int64_t H, int64_t W, int64_t OH, int64_t OW) {
@@ -290,36 +265,30 @@ extern "C" int ffq_pool2d_quantize(int mode, const void* x, int x_dt, const floa
   rc = check_extents("fused pooling", param_channels, planes, H, W, OH, OW);
   if (rc) return rc;
   FanOut f;
-  rc = fan_from_abi(fan, planes * OH * OW, &f);
-  if (rc) return rc;
-  if (planes == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, planes * OH * OW, planes == 0, x, {x, out}, &f);
+  if (rc || planes == 0) return rc;
   Geometry g;
   fill(&g, param_channels, planes, H, W, OH, OW);
   g.kh = (int32_t)kh; g.kw = (int32_t)kw; g.sh = (int32_t)sh; g.sw = (int32_t)sw;
   g.ph = (int32_t)ph; g.pw = (int32_t)pw; g.dh = (int32_t)dh; g.dw = (int32_t)dw;
   const int j = per_lane(g.total);
   const unsigned grid = (unsigned)(((uint64_t)g.total + (uint64_t)(kBlock * j) - 1) / (uint64_t)(kBlock * j));
-#define FFQ_P1(T, TIN, DEQ, MODE, J) \
-  pool2d_quantize_kernel<T, TIN, DEQ, MODE, J><<<grid, kBlock, 0, s>>>(static_cast<const TIN*>(x), x_scale, x_offset, g, static_cast<T*>(out), f)
-#define FFQ_P1_J(T, TIN, DEQ, MODE) \
-  if (j == 8) FFQ_P1(T, TIN, DEQ, MODE, 8); else FFQ_P1(T, TIN, DEQ, MODE, 1)
-#define FFQ_P1_MODE(T, TIN, DEQ)                             \
-  switch (mode) {                                            \
-    case kAvg: FFQ_P1_J(T, TIN, DEQ, kAvg); break;           \
-    case kAvgExcludePad: FFQ_P1_J(T, TIN, DEQ, kAvgExcludePad); break; \
-    default: FFQ_P1_J(T, TIN, DEQ, kMax); break;             \
-  }
-#define FFQ_P1_INPUT(T)                                        \
-  if (!x_scale) { FFQ_P1_MODE(T, T, false) }                   \
-  else if (x_dt == FFQ_I8) { FFQ_P1_MODE(T, int8_t, true) }    \
-  else { FFQ_P1_MODE(T, T, true) }
-  if (dt == FFQ_BF16) { FFQ_P1_INPUT(bf16_t) } else { FFQ_P1_INPUT(f16_t) }
-#undef FFQ_P1_INPUT
-#undef FFQ_P1_MODE
-#undef FFQ_P1_J
-#undef FFQ_P1
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    auto launch = [&](auto mode_, auto j_) {
+      pool2d_quantize_kernel<T, TIn, decltype(deq)::value, decltype(mode_)::value, decltype(j_)::value><<<grid, kBlock, 0, s>>>(
+          static_cast<const TIn*>(x), x_scale, x_offset, g, static_cast<T*>(out), f);
+    };
+    auto by_lane = [&](auto mode_) {
+      if (j == 8) launch(mode_, Int<8>{}); else launch(mode_, Int<1>{});
+    };
+    switch (mode) {
+      case kAvg: by_lane(Int<kAvg>{}); break;
+      case kAvgExcludePad: by_lane(Int<kAvgExcludePad>{}); break;
+      default: by_lane(Int<kMax>{}); break;
+    }
+  });
   return check_launch("pool2d_quantize_kernel");
 }
 
@@ -334,11 +303,8 @@ extern "C" int ffq_upsample_nearest_quantize(const void* x, int x_dt, const floa
   rc = check_extents("fused nearest interpolation", param_channels, planes, H, W, OH, OW);
   if (rc) return rc;
   FanOut f;
-  rc = fan_from_abi(fan, planes * OH * OW, &f);
-  if (rc) return rc;
-  if (planes == 0) return FFQ_OK;
-  if (!x) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(x) || (out && !aligned16(out))) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  rc = check_launch_args(fan, planes * OH * OW, planes == 0, x, {x, out}, &f);
+  if (rc || planes == 0) return rc;
   Geometry g;
   fill(&g, param_channels, planes, H, W, OH, OW);
   // ATen's compute_scales_value<float>: 1 / scale_factor when one is given, else in / out
@@ -347,17 +313,14 @@ extern "C" int ffq_upsample_nearest_quantize(const void* x, int x_dt, const floa
   g.exact = exact ? 1 : 0;
   const int j = per_lane(g.total);
   const unsigned grid = (unsigned)(((uint64_t)g.total + (uint64_t)(kBlock * j) - 1) / (uint64_t)(kBlock * j));
-#define FFQ_N1(T, TIN, DEQ, J) \
-  upsample_nearest_quantize_kernel<T, TIN, DEQ, J><<<grid, kBlock, 0, s>>>(static_cast<const TIN*>(x), x_scale, x_offset, g, static_cast<T*>(out), f)
-#define FFQ_N1_J(T, TIN, DEQ) \
-  if (j == 8) FFQ_N1(T, TIN, DEQ, 8); else FFQ_N1(T, TIN, DEQ, 1)
-#define FFQ_N1_INPUT(T)                                     \
-  if (!x_scale) { FFQ_N1_J(T, T, false); }                  \
-  else if (x_dt == FFQ_I8) { FFQ_N1_J(T, int8_t, true); }   \
-  else { FFQ_N1_J(T, T, true); }
-  if (dt == FFQ_BF16) { FFQ_N1_INPUT(bf16_t) } else { FFQ_N1_INPUT(f16_t) }
-#undef FFQ_N1_INPUT
-#undef FFQ_N1_J
-#undef FFQ_N1
+  dispatch_input(dt, x_dt, x_scale != nullptr, [&](auto t, auto tin, auto deq) {
+    using T = typename decltype(t)::type;
+    using TIn = typename decltype(tin)::type;
+    auto launch = [&](auto j_) {
+      upsample_nearest_quantize_kernel<T, TIn, decltype(deq)::value, decltype(j_)::value><<<grid, kBlock, 0, s>>>(
+          static_cast<const TIn*>(x), x_scale, x_offset, g, static_cast<T*>(out), f);
+    };
+    if (j == 8) launch(Int<8>{}); else launch(Int<1>{});
+  });
   return check_launch("upsample_nearest_quantize_kernel");
 }
