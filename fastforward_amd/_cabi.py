@@ -144,6 +144,30 @@ class SdpaQuantizer(ctypes.Structure):
 
 SDPA_QUANTIZERS = 8  # FFQ_SDPA_QUANTIZERS
 
+FFQ_CAT_MAX_INPUTS = 8
+
+
+class CatInputs(ctypes.Structure):
+    """``ffq_cat_inputs``: the inputs of one ``ffq_cat_quantize`` launch (scale NULL: a plain input)."""
+
+    _fields_ = [
+        ("count", ctypes.c_int32),
+        ("data", ctypes.c_void_p * FFQ_CAT_MAX_INPUTS),
+        ("dt", ctypes.c_int32 * FFQ_CAT_MAX_INPUTS),
+        ("scale", ctypes.c_void_p * FFQ_CAT_MAX_INPUTS),
+        ("offset", ctypes.c_void_p * FFQ_CAT_MAX_INPUTS),
+        ("run", ctypes.c_int64 * FFQ_CAT_MAX_INPUTS),
+    ]
+
+    @classmethod
+    def make(cls, inputs: Sequence[tuple[int | None, int, int | None, int | None, int]]) -> "CatInputs":
+        """`inputs`: (data, container tag, scale, offset, run) per input; the count is checked by the entry point."""
+        c = cls()
+        c.count = len(inputs)
+        for i, (data, tag, scale, offset, run) in enumerate(inputs[:FFQ_CAT_MAX_INPUTS]):
+            c.data[i], c.dt[i], c.scale[i], c.offset[i], c.run[i] = data, int(tag), scale, offset, int(run)
+        return c
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
@@ -216,6 +240,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "ffq_cumsum_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _vp, _fp, _vp]),
     "ffq_pool2d_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i] + [_i64] * 11 + [_i, _i64, _i64, _vp, _fp, _vp]),
     "ffq_upsample_nearest_quantize": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i64, _i64, _i64, _i64, _i64, _d, _d, _i, _vp, _fp, _vp]),
+    "ffq_cat_quantize": (_i, [ctypes.POINTER(CatInputs), _i, _i64, _i64, _i64, _vp, _fp, _vp]),
+    "ffq_pad_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i64, _i, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _i, _vp, _fp, _vp]),
     "ffq_sdpa_quantize": (
         _i,
         [_vp, _vp, _vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _vp, _i, _i,
@@ -246,7 +272,7 @@ DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_
                                          "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
                                          "ffq_activation_quantize", "ffq_sdpa_quantize", "ffq_rms_norm_quantize", "ffq_unary_quantize",
                                          "ffq_sum_quantize_workspace_bytes", "ffq_sum_quantize", "ffq_cumsum_quantize",
-                                         "ffq_pool2d_quantize", "ffq_upsample_nearest_quantize"})
+                                         "ffq_pool2d_quantize", "ffq_upsample_nearest_quantize", "ffq_cat_quantize", "ffq_pad_quantize"})
 
 
 class FFQLibrary:

@@ -1,6 +1,6 @@
 // ffq_onepass.h — what the one-pass quantized families share: ffq_modules.hip (LayerNorm / Embedding / ReLU / SiLU),
-// ffq_elementwise.hip (add / sub / mul / div, softmax, sigmoid, GELU), ffq_math.hip (rms_norm, pow, exp, sin, cos, sum, cumsum) and
-// ffq_pool.hip (the pools, nearest interpolate).
+// ffq_elementwise.hip (add / sub / mul / div, softmax, sigmoid, GELU), ffq_math.hip (rms_norm, pow, exp, sin, cos, sum, cumsum),
+// ffq_pool.hip (the pools, nearest interpolate) and ffq_concat.hip (cat, pad).
 //
 // The arithmetic contract of every kernel in those files:
 //   A2  an operand given as codes is dequantized in registers as ffq_dequantize.hip does: (q + round(o)) * s in fp32 (two roundings,
@@ -75,7 +75,7 @@ __device__ __forceinline__ Chunk<T, kE> operand_packed(const TIn* p, float s, fl
   return h;
 }
 
-// A2 of one code (ffq_pool.hip's gathers). `o` is already rounded.
+// A2 of one code (ffq_pool.hip's gathers, ffq_concat.hip's element forms). `o` is already rounded.
 template <typename T>
 __device__ __forceinline__ float a2_value(float q, float s, float o) {
   const float a = q + o;

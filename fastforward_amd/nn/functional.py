@@ -16,13 +16,17 @@ add / sub / mul / div, softmax, sigmoid and GELU kernels (fallbacks: _gen/fallba
 kernel). ``rms_norm``, ``pow``, ``exp``, ``sin``, ``cos``, ``sum`` and ``cumsum`` follow their fallbacks (_gen/fallback.py:955-1014,
 1520-1541, 1831-1941), and ``fastforward_amd.fused_math`` registers their one-pass kernels. ``avg_pool1d``, ``avg_pool2d``,
 ``max_pool2d`` and ``interpolate`` follow theirs (_gen/fallback.py:505-575, 1574-1646) with the reference's signatures, and
-``fastforward_amd.fused_pool`` registers the one-pass kernels of the pools and of nearest interpolation. The other generated
+``fastforward_amd.fused_pool`` registers the one-pass kernels of the pools and of nearest interpolation. ``cat`` and ``pad`` follow
+theirs (_gen/fallback.py:1453-1479, 1546-1570) with the reference's signatures (``pad``'s default ``mode="..."`` included);
+``fastforward_amd.fused_concat`` registers their one-pass kernels, and a ``cat`` of per-tensor affine tensors that share their
+parameters, without an output quantizer, is the reference's concatenation of the codes
+(quantization/_linear_quantized_ops.py:174-224). The other generated
 operators of the reference are pure float fallbacks and are out of scope.
 """
 
 from __future__ import annotations
 
-from typing import TYPE_CHECKING, Any, Callable, Optional
+from typing import TYPE_CHECKING, Any, Callable, Optional, Sequence
 
 import torch
 
@@ -36,7 +40,7 @@ if TYPE_CHECKING:
 
 __all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
            "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
-           "cumsum", "avg_pool1d", "avg_pool2d", "max_pool2d", "interpolate"]
+           "cumsum", "avg_pool1d", "avg_pool2d", "max_pool2d", "interpolate", "cat", "pad"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -410,6 +414,34 @@ def max_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any = None, paddin
 def interpolate(input: torch.Tensor, size: Any = None, scale_factor: Any = None, mode: str = "nearest", align_corners: bool | None = None, recompute_scale_factor: bool | None = None, antialias: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, size=size, scale_factor=scale_factor, mode=mode, align_corners=align_corners, recompute_scale_factor=recompute_scale_factor, antialias=antialias, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("interpolate", **kwargs) or _fallback_interpolate)(**kwargs)
+
+
+# ---- cat, pad (reference _gen/operators.py:1290, 1383: dispatch(op, **kwargs) or the generated fallback) ---------------------------
+def _fallback_cat(tensors: Sequence[torch.Tensor], dim: int = 0, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize every element, torch.cat, optional output quantizer (reference fallback.py:1453-1479)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    tensors = [_dequantized("elem__", elem__, strict_quantization) for elem__ in tensors]
+    output = torch.cat(tensors=tensors, dim=dim)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _fallback_pad(input: torch.Tensor, pad: Sequence[int], mode: str = "...", value: float | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.pad, optional output quantizer (reference fallback.py:1546-1570)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.pad(input=input, pad=pad, mode=mode, value=value)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def cat(tensors: Sequence[torch.Tensor], dim: int = 0, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(tensors=tensors, dim=dim, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("cat", **kwargs) or _fallback_cat)(**kwargs)
+
+
+def pad(input: torch.Tensor, pad: Sequence[int], mode: str = "...", value: float | None = None, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    # (the default mode is the reference's, an artefact of its generator: F.pad refuses it)
+    kwargs = dict(input=input, pad=pad, mode=mode, value=value, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("pad", **kwargs) or _fallback_pad)(**kwargs)
 
 
 from fastforward_amd.nn.sdpa import scaled_dot_product_attention  # noqa: E402  (nn/sdpa.py calls back into this module)

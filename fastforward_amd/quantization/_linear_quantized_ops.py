@@ -3,12 +3,13 @@
 Subset of src/fastforward/quantization/_linear_quantized_ops.py needed on the Llama linear path
 (SURVEY §2): ``contiguous`` (:94-96) for any quantized tensor and ``view`` / ``view_as`` /
 ``reshape`` / ``transpose`` for per-tensor affine tensors (:99-123). They only move metadata.
-So does ``mul`` by a Python number (:126-171): the same codes with ``scale * other``.
+So does ``mul`` by a Python number (:126-171): the same codes with ``scale * other``. ``cat`` of per-tensor affine tensors that
+share one scale and one offset, without an output quantizer, concatenates the codes (:174-224).
 """
 
 from __future__ import annotations
 
-from typing import Any
+from typing import Any, Sequence
 
 import torch
 
@@ -111,3 +112,53 @@ def scalar_multiply(input: QuantizedTensor, other: float, *_args: Any, **_kwargs
     params = input.quant_args()
     scaled = _ScaleGradient.apply(input.raw_data, other)
     return input.quantization_context.with_changes(scale=params.scale * other).attach(scaled)
+
+
+# ---- cat of tensors that share their parameters: a concatenation of the codes (reference :174-224) ---------------------------------
+def _values_equal(a: Any, b: Any) -> bool:
+    """The reference's ``a == b`` on two parameters. On device tensors it reads the result on the host: it synchronises."""
+    return bool(torch.as_tensor(a == b).all())
+
+
+def _same_tensor(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """One view of one storage: equal without looking at the values."""
+    return (a.device == b.device and a.dtype == b.dtype and a.shape == b.shape and a.stride() == b.stride()
+            and a.storage_offset() == b.storage_offset() and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr())
+
+
+def _same_parameter(a: Any, b: Any) -> bool:
+    if a is b:
+        return True
+    if a is None or b is None:
+        return False
+    if isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and _same_tensor(a, b):
+        return True
+    return _values_equal(a, b)
+
+
+def _is_code_level_cat(tensors: Any = None, dim: Any = 0, *_args: Any, output_quantizer: Any = None, **kwargs: Any) -> bool:
+    """Every element a per-tensor static-affine ``QuantizedTensor``, all scales equal and all offsets equal, no output quantizer:
+    the reference's predicate. Parameters that are one tensor object, or one view of one storage, are equal without a look at
+    their values; only otherwise are the values compared as the reference compares them, which reads device memory on the host —
+    such a call synchronises and cannot be captured in a graph."""
+    if output_quantizer is not None or "out" in kwargs or not isinstance(tensors, (list, tuple)) or not tensors:
+        return False
+    first = None
+    for tensor in tensors:
+        if not _static_affine(tensor) or not isinstance(_granularity_of(tensor), granularities.PerTensor):
+            return False
+        params = tensor.quant_args()
+        if first is not None and not (_same_parameter(params.scale, first.scale) and _same_parameter(params.offset, first.offset)):
+            return False
+        first = params if first is None else first
+    return True
+
+
+cat_predicate = Predicate(_is_code_level_cat)
+
+
+@register("cat", cat_predicate)
+def cat(tensors: Sequence[QuantizedTensor], dim: int = 0, *_args: Any, **_kwargs: Any) -> QuantizedTensor:
+    """``torch.cat`` of the codes, under the first element's context. Serves ``ff.nn.functional.cat`` and ``torch.cat``."""
+    output = torch.cat([t.raw_data for t in tensors], dim=dim)
+    return tensors[0].quantization_context.attach(output)

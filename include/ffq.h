@@ -576,6 +576,45 @@ int ffq_upsample_nearest_quantize(const void* x, int x_dt, const float* x_scale,
                                   double scale_factor_w, int exact, void* out, const ffq_fanout* fan, void* stream);
 
 /*
+ * cat + A1 — ff.nn.functional.cat (reference _gen/fallback.py:1453-1479: A2 of every quantized element, torch.cat, the output
+ * quantizer). The concatenation along any dim is seen as 2-D: input i is [outer, run[i]] (run = shape[dim] * inner), the result z
+ * [outer, out_run]; this launch writes the columns [col0, col0 + sum run[i]) of it, so more than FFQ_CAT_MAX_INPUTS inputs are
+ * several launches into one result (out and the fan-out's codes are the WHOLE result's buffers in every launch).
+ * Each input is on its own plain dt (scale[i] NULL), or int8 / dt codes dequantized as A2 does with its own per-tensor fp32
+ * scale[i] / offset[i] (nullable: zeros); a plain element keeps its bits. codes_j = A1(z; scale_j, offset_j). out is nullable.
+ * When every run[i], col0 and out_run are multiples of 8 the launch moves 8 elements per lane (16 B of values, 8 B of codes),
+ * otherwise one element per lane: any run[i] >= 1. outer * out_run < 2^31; 1 <= count <= FFQ_CAT_MAX_INPUTS, otherwise FFQ_ERR_ARG.
+ * FFQ_ERR_DTYPE for dt other than bf16 / fp16 or an input that is neither dt nor codes with a scale, before any buffer is looked at.
+ */
+#define FFQ_CAT_MAX_INPUTS 8
+typedef struct ffq_cat_inputs {
+  int32_t count;
+  const void* data[FFQ_CAT_MAX_INPUTS];
+  int32_t dt[FFQ_CAT_MAX_INPUTS];           /* the container: `dt` or FFQ_I8                         */
+  const float* scale[FFQ_CAT_MAX_INPUTS];   /* NULL: a plain input                                   */
+  const float* offset[FFQ_CAT_MAX_INPUTS];  /* nullable                                              */
+  int64_t run[FFQ_CAT_MAX_INPUTS];          /* elements of one row of this input                     */
+} ffq_cat_inputs;
+int ffq_cat_quantize(const ffq_cat_inputs* inputs, int dt, int64_t outer, int64_t out_run, int64_t col0, void* out, const ffq_fanout* fan,
+                     void* stream);
+
+/*
+ * pad + A1 — ff.nn.functional.pad (reference _gen/fallback.py:1546-1570: A2, F.pad, the output quantizer) on the last one, two or
+ * three dimensions of an input collapsed to [outer, D2, D1, D0] (a dimension that is not padded is 1, or part of outer);
+ * pads = {left0, right0, left1, right1, left2, right2}, the result z [outer, D2 + l2 + r2, D1 + l1 + r1, D0 + l0 + r0].
+ *   mode 0 constant: z = v at the shifted index, or the fill where there is none; negative pads crop. fill_bits are the bits of the
+ *          fill in dt (what ATen's fill writes for the caller's number); a padded element is the fill, not A2 of a code;
+ *   mode 1 reflect (0 <= pad < extent), mode 2 replicate (0 <= pad): only the index map differs.
+ * v: plain dt, or A2 of int8 / dt codes with one fp32 parameter pair (param_channels 0) or one per channel: param_channels = C > 0
+ * pairs, row r of `outer` reads pair (r / channel_inner) % C (C * channel_inner divides outer). Bit for bit the chain's value.
+ * codes_j = A1(z; scale_j, offset_j). out is nullable. Rows whose length is a multiple of 8 are written 8 elements per lane.
+ * Every extent >= 1, fewer than 2^31 input and output elements; otherwise FFQ_ERR_ARG / FFQ_ERR_DTYPE as ffq_pool2d_quantize.
+ */
+int ffq_pad_quantize(int mode, const void* x, int x_dt, const float* x_scale, const float* x_offset, int64_t param_channels,
+                     int64_t channel_inner, int dt, int64_t outer, int64_t D2, int64_t D1, int64_t D0, const int64_t* pads,
+                     int fill_bits, void* out, const ffq_fanout* fan, void* stream);
+
+/*
  * Quantized scaled_dot_product_attention — ff.nn.functional.scaled_dot_product_attention (reference
  * nn/functional/custom/sdpa.py:116-285: fp32 upcast, q * sqrt(scale) -> A1, k^T * sqrt(scale) -> A1, matmul -> A1, + bias (mask
  * -> A1) -> A1, safe softmax -> A1, dropout (p = 0) -> A1, matmul -> A1) in one launch, no [L, S] matrix in memory.
