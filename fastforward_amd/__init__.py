@@ -38,6 +38,7 @@ from fastforward_amd.range_setting import estimate_ranges as estimate_ranges  # 
 import fastforward_amd.fused_linear  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_modules  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_conv  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_conv_transpose  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_elementwise  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_math  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_pool  # noqa: E402,F401  isort: skip

@@ -253,6 +253,12 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _d, _i,
          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp],
     ),
+    "ffq_conv_transpose2d_w8a8_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i]),
+    "ffq_conv_transpose2d_w8a8": (
+        _i,
+        [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _d, _i,
+         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _sz, _vp],
+    ),
     "ffq_quantize_rows_rowsum": (_i, [_vp, _i, _vp, _vp, _i64, _i64, _d, _vp, _vp, _vp]),
     "ffq_linear_wq_supported": (_i, [_i, _i, _i, _i64, _i64, _i64, _i64, _i64]),
     "ffq_linear_wq_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -269,7 +275,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
 # Entry points only the HIP library must export: a host library (the CPU oracle) without one gets the attribute bound to None and
 # callers treat that as "not covered". Whether the symbol is there is the capability check (FFQ_ABI_VERSION does not move for them).
 DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_quantize", "ffq_embedding_quantize", "ffq_pointwise_quantize",
-                                         "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
+                                         "ffq_conv2d_w8a8", "ffq_conv2d_w8a8_workspace_bytes", "ffq_conv_transpose2d_w8a8",
+                                         "ffq_conv_transpose2d_w8a8_workspace_bytes", "ffq_binary_quantize", "ffq_softmax_quantize",
                                          "ffq_activation_quantize", "ffq_sdpa_quantize", "ffq_rms_norm_quantize", "ffq_unary_quantize",
                                          "ffq_sum_quantize_workspace_bytes", "ffq_sum_quantize", "ffq_cumsum_quantize",
                                          "ffq_pool2d_quantize", "ffq_upsample_nearest_quantize", "ffq_cat_quantize", "ffq_pad_quantize"})

@@ -19,18 +19,12 @@
 //     POSITIONS on the B side: every 16-byte staging slot of a B row is one 16-channel run of one tap of the im2col matrix,
 //     gathered from the NHWC codes (zeros outside the image). The B row lands on lane & 31 of the accumulator, so one
 //     accumulator register over 32 lanes is 32 consecutive output positions of one channel: the epilogue stores NCHW directly.
-#include "ffq_affine.h"
-#include "ffq_common.h"
-#include "ffq_epilogue.h"
-#include "ffq_vec.h"
+#include "ffq_conv_tile.h"
 
 #include <math.h>
 
 namespace ffq {
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int CBM = 128, CBN = 128, CBK = 64;
 constexpr int kConvTileBytes = CBM * CBK;
@@ -53,10 +47,6 @@ struct ConvArgs {
   int tiles_m, tiles_n;
 };
 
-__device__ __forceinline__ uint32_t conv_swizzled(uint32_t row, uint32_t slot) {
-  return row * CBK + ((slot ^ ((row >> 2) & 3u)) << 4);
-}
-
 // [lo, hi) of the taps k with 0 <= o0 + k * d < extent
 __device__ __forceinline__ void tap_range(int o0, int d, int taps, int extent, int& lo, int& hi) {
   lo = o0 >= 0 ? 0 : (-o0 + d - 1) / d;
@@ -77,21 +67,7 @@ __global__ __launch_bounds__(256) void conv_layout_kernel(const int8_t* __restri
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int Cp = groups * 16;
   if (idx < n_in) {
-    const int64_t hw = idx % HW, rest = idx / HW;
-    const int g = (int)(rest % groups);
-    const int64_t b = rest / groups;
-    uint8_t v[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int c = g * 16 + k;
-      v[k] = c < C ? (uint8_t)x[(b * C + c) * HW + hw] : (uint8_t)0;
-    }
-    u32x4 packed;
-    packed.x = v[0] | (v[1] << 8) | (v[2] << 16) | ((uint32_t)v[3] << 24);
-    packed.y = v[4] | (v[5] << 8) | (v[6] << 16) | ((uint32_t)v[7] << 24);
-    packed.z = v[8] | (v[9] << 8) | (v[10] << 16) | ((uint32_t)v[11] << 24);
-    packed.w = v[12] | (v[13] << 8) | (v[14] << 16) | ((uint32_t)v[15] << 24);
-    *reinterpret_cast<u32x4*>(xn + (b * HW + hw) * Cp + g * 16) = packed;
+    nchw_to_nhwc16(x, xn, idx, C, HW, groups);
     return;
   }
   const int64_t j = idx - n_in;
@@ -109,12 +85,7 @@ __global__ __launch_bounds__(256) void conv_layout_kernel(const int8_t* __restri
     v[k] = (uint8_t)q;
     sum += q;
   }
-  u32x4 packed;
-  packed.x = v[0] | (v[1] << 8) | (v[2] << 16) | ((uint32_t)v[3] << 24);
-  packed.y = v[4] | (v[5] << 8) | (v[6] << 16) | ((uint32_t)v[7] << 24);
-  packed.z = v[8] | (v[9] << 8) | (v[10] << 16) | ((uint32_t)v[11] << 24);
-  packed.w = v[12] | (v[13] << 8) | (v[14] << 16) | ((uint32_t)v[15] << 24);
-  *reinterpret_cast<u32x4*>(wn + row_tap * Cp + g * 16) = packed;
+  *reinterpret_cast<u32x4*>(wn + row_tap * Cp + g * 16) = pack16(v);
   if (sum != 0) {
     atomicAdd(tapsum + row_tap, sum);
     atomicAdd(tapsum + (int64_t)OC * taps + n, sum);
@@ -315,20 +286,8 @@ __global__ __launch_bounds__(256) void conv_w8a8_kernel(ConvArgs a) {
             rsw = (float)s;
           }
         }
-        float v = (float)acc[i][j][e];
-        v = v + ox * rsw;
-        v = v + ow * rsx;
-        v = v + cnt * ox * ow;
-        float y = (sx * sw) * v;
-        if (a.bias) y = y + bias;
-        if constexpr (REQUANT) {
-          y = round_to_dt(y, a.y_dt);
-          float qv = rne(y / oscale - ooff);
-          qv = clamp_nan(qv, a.out_lo, a.out_hi);
-          store_out<TOut>(out + out_base + (size_t)m * a.ohw, qv);
-        } else {
-          store_out<TOut>(out + out_base + (size_t)m * a.ohw, y);
-        }
+        const float y = conv_affine(acc[i][j][e], ox, rsw, ow, rsx, cnt, sx, sw, a.bias != nullptr, bias);
+        conv_store<TOut, REQUANT>(out + out_base + (size_t)m * a.ohw, y, a.y_dt, oscale, ooff, a.out_lo, a.out_hi);
       }
     }
   }

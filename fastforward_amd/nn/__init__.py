@@ -27,3 +27,6 @@ from fastforward_amd.nn.activations import QuantizedSilu as QuantizedSilu  # iso
 from fastforward_amd.nn.conv import QuantizedConv1d as QuantizedConv1d  # isort: skip
 from fastforward_amd.nn.conv import QuantizedConv2d as QuantizedConv2d  # isort: skip
 from fastforward_amd.nn.conv import quantized_conv_modules as quantized_conv_modules  # isort: skip
+from fastforward_amd.nn.conv import QuantizedConvTranspose1d as QuantizedConvTranspose1d  # isort: skip
+from fastforward_amd.nn.conv import QuantizedConvTranspose2d as QuantizedConvTranspose2d  # isort: skip
+from fastforward_amd.nn.conv import quantized_conv_transpose_modules as quantized_conv_transpose_modules  # isort: skip

@@ -1,5 +1,5 @@
 """Quantized functional operators: the linear path (``linear``, ``matmul``, ``mm``, ``bmm``), the convolutions (``conv1d``,
-``conv2d``), the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``) and the elementwise operators of a
+``conv2d``, ``conv_transpose1d``, ``conv_transpose2d``), the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``) and the elementwise operators of a
 transformer block outside its linears (``add``, ``sub``, ``mul``, ``div``, ``softmax``, ``sigmoid``, ``gelu``).
 
 Reference: the generated ``ff.nn.functional.*`` (src/fastforward/_gen/operators.py:79-106 for
@@ -20,8 +20,10 @@ kernel). ``rms_norm``, ``pow``, ``exp``, ``sin``, ``cos``, ``sum`` and ``cumsum`
 theirs (_gen/fallback.py:1453-1479, 1546-1570) with the reference's signatures (``pad``'s default ``mode="..."`` included);
 ``fastforward_amd.fused_concat`` registers their one-pass kernels, and a ``cat`` of per-tensor affine tensors that share their
 parameters, without an output quantizer, is the reference's concatenation of the codes
-(quantization/_linear_quantized_ops.py:174-224). The other generated
-operators of the reference are pure float fallbacks and are out of scope.
+(quantization/_linear_quantized_ops.py:174-224). ``conv_transpose1d`` and ``conv_transpose2d`` follow theirs
+(_gen/fallback.py:346-449) with the reference's signatures, and ``fastforward_amd.fused_conv_transpose`` registers the phase-split
+int8 implicit GEMM. The other generated operators of the reference (``conv3d``, ``conv_transpose3d``, ``avg_pool3d`` among them) are
+pure float fallbacks and are out of scope.
 """
 
 from __future__ import annotations
@@ -38,7 +40,7 @@ from fastforward_amd.quantized_tensor import QuantizedTensor
 if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
-__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
+__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "conv_transpose1d", "conv_transpose2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
            "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
            "cumsum", "avg_pool1d", "avg_pool2d", "max_pool2d", "interpolate", "cat", "pad"]
 
@@ -204,6 +206,35 @@ def conv1d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None 
 def conv2d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("conv2d", **kwargs) or _fallback_conv2d)(**kwargs)
+
+
+# ---- the transposed convolutions (reference _gen/operators.py:362-392: dispatch(op, **kwargs) or the generated fallback) --------
+def _conv_transpose_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., torch.Tensor]:
+    def fallback(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, output_padding: Any = 0, groups: int = 1, dilation: Any = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+        """Dequantize input / weight / bias, the float transposed convolution, optional output quantizer (reference fallback.py:346-449)."""
+        _check_output_quantizer(output_quantizer, strict_quantization)
+        input = _dequantized("input", input, strict_quantization)
+        weight = _dequantized("weight", weight, strict_quantization)
+        if bias is not None:
+            bias = _dequantized("bias", bias, strict_quantization, required=False)
+        output = torch_op(input=input, weight=weight, bias=bias, stride=stride, padding=padding, output_padding=output_padding, groups=groups, dilation=dilation)
+        return output_quantizer(output) if output_quantizer is not None else output
+
+    return fallback
+
+
+_fallback_conv_transpose1d = _conv_transpose_fallback(torch.nn.functional.conv_transpose1d)  # fallback.py:346-395
+_fallback_conv_transpose2d = _conv_transpose_fallback(torch.nn.functional.conv_transpose2d)  # fallback.py:399-448
+
+
+def conv_transpose1d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, output_padding: Any = 0, groups: int = 1, dilation: Any = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, output_padding=output_padding, groups=groups, dilation=dilation, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("conv_transpose1d", **kwargs) or _fallback_conv_transpose1d)(**kwargs)
+
+
+def conv_transpose2d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, output_padding: Any = 0, groups: int = 1, dilation: Any = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, output_padding=output_padding, groups=groups, dilation=dilation, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("conv_transpose2d", **kwargs) or _fallback_conv_transpose2d)(**kwargs)
 
 
 # ---- the elementwise operators (reference _gen/operators.py: dispatch(op, **kwargs) or the generated fallback) ---------------------

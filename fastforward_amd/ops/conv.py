@@ -1,7 +1,10 @@
 """The W8A8 convolution on int8 codes (csrc/ffq_conv.hip): what QuantizedConv2d / QuantizedConv1d run on the device instead of the
-reference's fallback.conv2d / fallback.conv1d (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer)."""
+reference's fallback.conv2d / fallback.conv1d (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer),
+and its transposed twin (csrc/ffq_conv_transpose.hip; fallback.conv_transpose1d / conv_transpose2d, _gen/fallback.py:346-449)."""
 
 from __future__ import annotations
+
+import math
 
 from typing import Sequence
 
@@ -14,12 +17,12 @@ from fastforward_amd.ops._base import _dense, _ptr, _tag, _workspace
 _REAL = (torch.float32, torch.bfloat16, torch.float16)
 
 
-def _pair(v: int | Sequence[int], what: str) -> tuple[int, int]:
+def _pair(v: int | Sequence[int], what: str, op: str = "conv2d_w8a8") -> tuple[int, int]:
     if isinstance(v, int):
         return v, v
     t = tuple(int(e) for e in v)
     if len(t) != 2:
-        raise RuntimeError(f"conv2d_w8a8: {what} is an int or a pair, got {v!r}")
+        raise RuntimeError(f"{op}: {what} is an int or a pair, got {v!r}")
     return t  # type: ignore[return-value]
 
 
@@ -93,3 +96,115 @@ def conv2d_w8a8(
         )
     )
     return out
+
+
+def conv_transpose2d_w8a8(
+    x_codes: torch.Tensor,
+    w_codes: torch.Tensor,
+    x_scale: torch.Tensor,
+    x_offset: torch.Tensor | None,
+    w_scale: torch.Tensor,
+    w_offset: torch.Tensor | None,
+    bias: torch.Tensor | None = None,
+    stride: int | Sequence[int] = 1,
+    padding: int | Sequence[int] = 0,
+    output_padding: int | Sequence[int] = 0,
+    dilation: int | Sequence[int] = 1,
+    out_dtype: torch.dtype = torch.bfloat16,
+    out_scale: torch.Tensor | None = None,
+    out_offset: torch.Tensor | None = None,
+    out_num_bits: float = 8.0,
+    requant_from: torch.dtype | None = None,
+) -> torch.Tensor:
+    """``F.conv_transpose2d`` (groups = 1) on int8 codes: `x_codes` [B, C, H, W] (contiguous, or channels-last with C % 16 == 0, which
+    skips the reorder pass's input half), `w_codes` [C, OC, KH, KW] (torch's transposed-weight layout); fp32 parameters, one pair
+    for the input and one for the weight or one per OUTPUT channel (dim 1 of the weight). Returns the contiguous NCHW
+    [B, OC, OH, OW] result in `out_dtype`, OH = (H - 1) * stride - 2 * padding + dilation * (KH - 1) + output_padding + 1: the exact
+    integer contraction over the taps that reach the input, with the affine terms over the same taps (include/ffq.h,
+    ffq_conv_transpose2d_w8a8). With `out_scale` (and optionally `out_offset`) the per-tensor output quantizer runs in the epilogue
+    as in :func:`conv2d_w8a8`: the result is rounded to `requant_from` (default bf16) and A1 writes int8 codes."""
+    op = "conv_transpose2d_w8a8"
+    if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
+        raise TypeError(f"{op} expects int8 codes")
+    if x_codes.dim() != 4 or w_codes.dim() != 4:
+        raise RuntimeError(f"{op}: input [B, C, H, W] and weight [C, OC, KH, KW], got {tuple(x_codes.shape)} and {tuple(w_codes.shape)}")
+    B, C, H, W = x_codes.shape
+    Cw, OC, KH, KW = w_codes.shape
+    if Cw != C:
+        raise RuntimeError(f"{op}: the weight has {Cw} input channels, the input {C} (groups > 1 is not built)")
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride, "stride", op), _pair(padding, "padding", op), _pair(dilation, "dilation", op)
+    oph, opw = _pair(output_padding, "output_padding", op)
+    nhwc = (not x_codes.is_contiguous()) and C % 16 == 0 and x_codes.is_contiguous(memory_format=torch.channels_last)
+    xc = _dense(x_codes.detach(), torch.channels_last if nhwc else torch.contiguous_format)
+    wc = _dense(w_codes.detach())
+
+    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
+        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
+
+    xs, xo, ws_, wo, os_, oo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(out_scale), f32(out_offset)
+    if xs.numel() != 1 or (xo is not None and xo.numel() != 1):
+        raise RuntimeError(f"{op}: the input has one parameter pair (per-tensor)")
+    if ws_.numel() not in (1, OC) or (wo is not None and wo.numel() != ws_.numel()):
+        raise RuntimeError(f"{op}: the weight has 1 or {OC} parameter pairs, got {ws_.numel()}")
+    if os_ is not None and (os_.numel() != 1 or (oo is not None and oo.numel() != 1)):
+        raise RuntimeError(f"{op}: the output quantizer is per tensor")
+    if os_ is None and out_dtype not in _REAL:
+        raise RuntimeError(f"{op}: a real-valued output is f32, bf16 or f16, got {out_dtype}")
+    bias_c = None if bias is None else bias.detach().reshape(-1).contiguous()
+    if bias_c is not None and (bias_c.numel() != OC or bias_c.dtype not in _REAL):
+        raise RuntimeError(f"{op}: the bias is [{OC}] of f32, bf16 or f16")
+    lib, stream = _base._prepare(xc, wc, xs, xo, ws_, wo, bias_c, os_, oo)
+    entry = getattr(lib, "ffq_conv_transpose2d_w8a8", None)
+    if entry is None:
+        raise BackendError("the loaded library does not export ffq_conv_transpose2d_w8a8 (a host library has no convolution kernel)")
+    OH = (H - 1) * sh - 2 * ph + dh * (KH - 1) + oph + 1
+    OW = (W - 1) * sw - 2 * pw + dw * (KW - 1) + opw + 1
+    out = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=torch.int8 if os_ is not None else out_dtype, device=xc.device)
+    nbytes = lib.ffq_conv_transpose2d_w8a8_workspace_bytes(B, C, H, W, OC, KH, KW, int(nhwc))
+    ws = _workspace(nbytes, xc.device)
+    y_dt = _tag(requant_from or torch.bfloat16) if os_ is not None else 0
+    lib.check(
+        entry(
+            _ptr(xc), int(nhwc), _ptr(wc), _ptr(xs), _ptr(xo), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
+            _ptr(bias_c), _tag(bias_c.dtype) if bias_c is not None else 0, _ptr(out), _tag(out.dtype), _ptr(os_), _ptr(oo),
+            float(out_num_bits), y_dt, B, C, H, W, OC, KH, KW, sh, sw, ph, pw, oph, opw, dh, dw, _ptr(ws), nbytes, stream,
+        )
+    )
+    return out
+
+
+MAX_PHASES = 64  # stride_h * stride_w: the phase table of csrc/ffq_conv_transpose.hip
+
+
+def axis_phases(kernel: int, stride: int, padding: int, dilation: int, out_size: int) -> tuple[list[tuple[int, int, int, int]], int, int]:
+    """One axis of the transposed convolution's phase table, as the host code of csrc/ffq_conv_transpose.hip builds it: for every
+    residue r < stride the tuple (k0, n, off0, extent) — the taps k0, k0 + kstep, ... (n of them) are those with stride dividing
+    r + padding - k * dilation, tap a reads input index i + off0 + a * ostep for the output o = r + stride * i, and extent counts
+    the outputs o = r (mod stride) below out_size — and the two steps (kstep, ostep)."""
+    g = math.gcd(stride, dilation)
+    kstep, ostep = stride // g, -(dilation // g)
+    rows = []
+    for r in range(stride):
+        k0 = next((k for k in range(min(kernel, kstep)) if (r + padding - k * dilation) % stride == 0), None)
+        extent = (out_size - r + stride - 1) // stride if r < out_size else 0
+        if k0 is None:
+            rows.append((0, 0, 0, extent))
+        else:
+            rows.append((k0, (kernel - k0 + kstep - 1) // kstep, (r + padding - k0 * dilation) // stride, extent))
+    return rows, kstep, ostep
+
+
+def phase_table(batch: int, kernel: Sequence[int], stride: Sequence[int], padding: Sequence[int], dilation: Sequence[int],
+                out_size: Sequence[int], tile: int = 128) -> list[dict[str, object]]:
+    """The phase table of a transposed convolution, phase p = rh * stride_w + rw: its output grid (`rows` x `cols` positions per
+    image: oh = rh + stride_h * i, ow = rw + stride_w * j), its `taps` in the phase-major order the reordered weight holds them
+    ((kh, kw, ih - i, iw - j) each, w fastest), `tap_begin` (the first of them) and `tile_end` (the prefix of 128-position tiles)."""
+    (ah, ksh, osh), (aw, ksw, osw) = (axis_phases(kernel[i], stride[i], padding[i], dilation[i], out_size[i]) for i in range(2))
+    table, tiles, tap = [], 0, 0
+    for rh, (k0h, nh, offh, eh) in enumerate(ah):
+        for rw, (k0w, nw, offw, ew) in enumerate(aw):
+            tiles += (batch * eh * ew + tile - 1) // tile
+            taps = [(k0h + a * ksh, k0w + b * ksw, offh + a * osh, offw + b * osw) for a in range(nh) for b in range(nw)]
+            table.append(dict(rh=rh, rw=rw, rows=eh, cols=ew, taps=taps, tap_begin=tap, tile_end=tiles))
+            tap += nh * nw
+    return table

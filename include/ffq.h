@@ -686,6 +686,47 @@ int ffq_conv2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, const float*
                     void* stream);
 
 /*
+ * W8A8 transposed convolution — functional conv_transpose2d / conv_transpose1d (reference _gen/fallback.py:346-449: A2 of input and
+ * weight, F.conv_transpose2d, the output quantizer). Integer codes in, a phase-split implicit GEMM on the int8 matrix cores, one
+ * fp32 epilogue per output element. For output (b, n, p), p = (oh, ow), V(p) = the taps (kh, kw) for which stride_h divides
+ * oh + pad_h - kh * dil_h with ih = (oh + pad_h - kh * dil_h) / stride_h in [0, H), and the same for w:
+ *   acc = sum_{t in V(p), c < C} xq[b,c,ih,iw] * wq[c,n,t]                                  (int32, exact)
+ *   rsx = sum_{t in V(p), c < C} xq[b,c,ih,iw]                                              (only with w_offset)
+ *   rsw = sum_{t in V(p)} sum_c wq[c,n,t]                                                    (only when rne(x_offset) != 0)
+ *   v = float(acc); v = v + ox * rsw; v = v + ow * rsx; v = v + (C * |V(p)|) * ox * ow      (fp32, left to right, no FMA)
+ *   y = (sx * sw[n']) * v  (+ bias[n])
+ * with ox / ow = rne(offset) as in A2 and n' = n if w_per_channel else 0. V(p) may be empty (stride 3, kernel 2: a third of the
+ * positions); then v = 0 and y is the bias alone, or 0. The float route never reads outside the input, so the formula is the
+ * reference's sum exactly: no padding subtlety as in ffq_conv2d_w8a8. Channels are padded to a multiple of 16 with code 0 internally.
+ * Layout: xq is [B, C, H, W] contiguous, or (x_nhwc != 0, C % 16 == 0, 16-byte aligned) [B, H, W, C] — a channels-last tensor;
+ * wq is [C, OC, KH, KW] contiguous (torch's transposed-weight layout); out is [B, OC, OH, OW] contiguous (NCHW),
+ * OH = (H - 1) * stride_h - 2 * pad_h + dil_h * (KH - 1) + out_pad_h + 1. conv_transpose1d is this call with H = KH = 1.
+ * Parameters: x per tensor; w per tensor or per OUTPUT channel (w_per_channel: OC pairs); fp32; bias nullable (f32 / bf16 / f16, [OC]).
+ * If out_scale != NULL the output quantizer (per tensor) runs in the epilogue under ffq_conv2d_w8a8's rules: y rounded once to
+ * y_dt, then codes = clamp(rne(y / out_scale - rne(out_offset))) into out (out_dt must be int8) — bit-identical to
+ * ffq_quantize_by_tile on the tensor the call without out_scale writes in y_dt. Else out holds y in out_dt (f32 / bf16 / f16).
+ * Coverage: groups == 1 (the caller's), C * KH * KW <= 131072 (else FFQ_ERR_DTYPE), stride / dilation >= 1, padding >= 0,
+ * 0 <= out_pad < max(stride, dilation) per axis (torch's rule), stride_h * stride_w <= 64 (the phase table; else FFQ_ERR_ARG),
+ * H, W >= 1, OH, OW >= 1, extents <= 2^24, B * OH * OW < 2^31 - 8192. Every argument check runs before any launch; B == 0 or
+ * OC == 0 returns FFQ_OK without one.
+ * Workspace: ffq_conv_transpose2d_w8a8_workspace_bytes(...) bytes, 16-byte aligned — the NHWC input codes (none with x_nhwc), the
+ * weight reordered to [OC, KH * KW * Cp] with the taps phase-major, the per-tap weight sums and 64 per-phase totals per output
+ * channel; less returns FFQ_ERR_WORKSPACE. Two launches (reorder, GEMM) and a memset. The query takes ffq_conv2d_w8a8's arguments
+ * and no stride, so that one workspace serves every geometry of a layer (output_size changes output_padding per call, never the
+ * buffer); the price is the full 64 phase totals, 256 bytes per output channel, whatever stride_h * stride_w is.
+ * Tolerance vs the reference's float route: the contraction is exact, so y differs from it only by the float route's own roundings
+ * (tests/test_conv_transpose_gpu.py checks within check_linear's tolerance and exactly against a float64 accumulator).
+ */
+size_t ffq_conv_transpose2d_w8a8_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW,
+                                                 int x_nhwc);
+int ffq_conv_transpose2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, const float* x_scale, const float* x_offset,
+                              const float* w_scale, const float* w_offset, int w_per_channel, const void* bias, int bias_dt,
+                              void* out, int out_dt, const float* out_scale, const float* out_offset, double out_num_bits, int y_dt,
+                              int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t stride_h,
+                              int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t out_pad_h, int64_t out_pad_w, int64_t dil_h,
+                              int64_t dil_w, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Rotary position embedding in place — attention.py:20-41 (apply_rotary_pos_emb):
  *   out = bf16(bf16(v * cos) + bf16(rotate_half(v) * sin)),  rotate_half(v) = cat(-v[D/2:], v[:D/2])
  * q: [tokens, q_heads, head_dim], k: [tokens, k_heads, head_dim] as they leave the projections;
