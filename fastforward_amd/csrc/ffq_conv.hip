@@ -28,7 +28,7 @@ namespace {
 
 constexpr int CBM = 128, CBN = 128, CBK = 64;
 constexpr int kConvTileBytes = CBM * CBK;
-constexpr int64_t kConvMaxReduction = 131072;  // C * KH * KW bound: |acc| <= 2^14 * 2^17, which int32 holds unless every code is -128
+constexpr int64_t kConvMaxReduction = 131071;  // C * KH * KW bound: |acc| <= 2^14 * (2^17 - 1) < 2^31 (at 2^17 taps of -128 x -128 the sum is 2^31 and wraps)
 
 struct ConvArgs {
   const int8_t* wq;       // [OC, Kp]: weight codes reordered to (kh, kw, c), Kp = KH * KW * Cp
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void conv_w8a8_kernel(ConvArgs a) {
     tap_range(oh * a.sh - a.ph, a.dh, a.KH, a.H, kh_lo, kh_hi);
     tap_range(ow_ * a.sw - a.pw, a.dw, a.KW, a.W, kw_lo, kw_hi);
     const bool full = kh_lo == 0 && kh_hi == a.KH && kw_lo == 0 && kw_hi == a.KW;
-    const float cnt = (float)(a.C * (kh_hi - kh_lo) * (kw_hi - kw_lo));  // C * |V(p)| <= 131072: exact
+    const float cnt = (float)(a.C * (kh_hi - kh_lo) * (kw_hi - kw_lo));  // C * |V(p)| < 131072: exact
     const float rsx = want_rsx ? (float)rsx_s[col] : 0.0f;
     const size_t out_base = (size_t)b * a.OC * a.ohw + p;
 #pragma unroll

@@ -35,7 +35,7 @@ namespace {
 constexpr int TBM = 128, TBN = 128, TBK = 64;
 constexpr int kTileBytes = TBM * TBK;
 constexpr int kMaxPhases = 64;                 // stride_h * stride_w: the size of the phase table
-constexpr int64_t kMaxReduction = 131072;      // C * KH * KW bound, as the forward convolution's
+constexpr int64_t kMaxReduction = 131071;      // C * KH * KW bound, as the forward convolution's
 
 // One residue of one axis: the taps k0, k0 + kstep, ... (n of them); tap a reads input index i + off0 - a * ostep.
 struct AxisPhase { int k0, n, off0, extent; };  // extent: the number of outputs o = r (mod stride) below the output size
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void convt_w8a8_kernel(ConvtArgs a, PhaseTable
     tap_range_down(gi + fh.off0, mh, fh.n, a.H, ta_lo, ta_hi);
     tap_range_down(gj + fw.off0, mw, fw.n, a.W, tb_lo, tb_hi);
     const bool full = ta_lo == 0 && ta_hi == fh.n && tb_lo == 0 && tb_hi == fw.n;
-    const float cnt = (float)(a.C * (ta_hi - ta_lo) * (tb_hi - tb_lo));  // C * |V(p)| <= 131072: exact
+    const float cnt = (float)(a.C * (ta_hi - ta_lo) * (tb_hi - tb_lo));  // C * |V(p)| < 131072: exact
     const float rsx = want_rsx ? (float)rsx_s[col] : 0.0f;
     const size_t out_base = (size_t)b * a.OC * ohw + (size_t)(rh + a.sh * gi) * a.OW + (rw + a.sw * gj);
 #pragma unroll

@@ -39,6 +39,9 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int kTileBytes = BM * BK;  // 8 KiB per operand per stage
+// The int32 accumulator's bound on the contraction length: |code * code| <= 2^14 (both -128), so |acc| <= 2^14 * K, which int32
+// holds for K < 2^17 only (K = 131072 with every code at -128 sums to exactly 2^31 and wraps). Longer contractions are refused.
+constexpr int64_t kMaxContraction = 131071;
 
 struct LinearArgs {
   const int8_t* xq;
@@ -1096,6 +1099,7 @@ static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w
     return fail(FFQ_ERR_DTYPE, "earlier codes: per-tensor activation parameters on the persistent kernel's shapes (ffq_linear_w8a8_takes_earlier)");
   if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
   if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
+  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
   if (K % 16 != 0 || !aligned16(xq) || !aligned16(wq))
     return fail(FFQ_ERR_DTYPE, "w8a8 linear needs K %% 16 == 0 and 16-byte aligned code pointers");
   if (bias && !dt_valid(bias_dt)) return fail(FFQ_ERR_ARG, "bad bias dtype");
@@ -1334,6 +1338,7 @@ extern "C" int ffq_bmm_w8a8(const int8_t* xq, const int8_t* wq, const float* x_s
   if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
   if (batch > 65535 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || batch * M > INT32_MAX || batch * N > INT32_MAX)
     return fail(FFQ_ERR_ARG, "extent out of range");
+  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
   if (K % 16 != 0 || !aligned16(xq) || !aligned16(wq) || (M * K) % 16 != 0 || (N * K) % 16 != 0)
     return fail(FFQ_ERR_DTYPE, "batched w8a8 matmul needs K %% 16 == 0 and 16-byte aligned matrices");
   const bool requant = out_scale != nullptr;
@@ -1413,6 +1418,7 @@ static int mlp_gate_up_w8a8_impl(const int8_t* xq, const int8_t* gate_wq, const 
   if (!xq || !gate_wq || !up_wq || !x_scale || !gate_w_scale || !up_w_scale || (!product_out && (!codes_out || !out_scale)))
     return fail(FFQ_ERR_ARG, "NULL buffer");
   if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
+  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
   if (N % 128 != 0 || K % 128 != 0 || K < 256 || !aligned16(xq) || !aligned16(gate_wq) || !aligned16(up_wq) || !aligned16(product_out ? product_out : (void*)codes_out))
     return fail(FFQ_ERR_DTYPE, "fused gate/up kernel needs N %% 128 == 0, K %% 128 == 0, K >= 256 and 16-byte aligned buffers");
   if (!product_out && !(out_num_bits >= 1 && out_num_bits <= 8 && out_num_bits == floor(out_num_bits)))
@@ -1522,6 +1528,7 @@ extern "C" int ffq_mlp_gate_up_w8a8_estimating(const int8_t* xq_gate, const int8
     return fail(FFQ_ERR_ARG, "NULL buffer");
   if ((extrema_words == nullptr) != (extrema_pair == nullptr)) return fail(FFQ_ERR_ARG, "extrema_words and extrema_pair come together");
   if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
+  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
   const int64_t tiles256 = ((M + BM2 - 1) / BM2) * ((N + 255) / 256);
   // both routes must be able to run: the one-launch mode's shapes and the persistent kernel's whole-line path of the gated epilogue
   if (N % 128 != 0 || K % 128 != 0 || K < 256 || M < 128 || tiles256 < 64 || !aligned16(xq_gate) || !aligned16(xq_up) || !aligned16(gate_wq) ||

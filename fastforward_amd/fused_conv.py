@@ -8,7 +8,7 @@ else, so the reference chain (the fallbacks in :mod:`fastforward_amd.nn.function
 * input and weight static-affine codes on the HIP device with the device library loaded (the C oracle declines): <= 8 bits, an
   int8 container or a float one (converted exactly, as ``DispatcherKernels._int8_codes``), fp32 parameters; the input per tensor,
   the weight per tensor or per output channel; data dtype bf16 / fp16 / fp32, the same for both;
-* ``groups == 1``, a batched input ([B, C, L] / [B, C, H, W]), ``C * prod(kernel) <= 131072``, integer stride / dilation / padding,
+* ``groups == 1``, a batched input ([B, C, L] / [B, C, H, W]), ``C * prod(kernel) < 131072``, integer stride / dilation / padding,
   ``padding='valid'``, and ``padding='same'`` where the padding it implies is symmetric;
 * bias: none, a plain tensor of the data dtype, or static-affine codes that dequantize to it;
 * no operand or parameter that needs a gradient while grad mode is on (the launch has no autograd formula).
@@ -32,7 +32,7 @@ from fastforward_amd.fused_linear import _FLOATS
 from fastforward_amd.fused_modules import KERNELS as _MODULES
 from fastforward_amd.fused_modules import _fp32_param, _needs_grad, _on_device, _settle
 
-MAX_REDUCTION = 131072  # C * KH * KW: the int32 accumulator's bound (include/ffq.h, ffq_conv2d_w8a8)
+MAX_REDUCTION = 131071  # C * KH * KW: the int32 accumulator's bound, 2^14 * taps < 2^31 (include/ffq.h, ffq_conv2d_w8a8)
 
 
 def _ints(v: Any, n: int) -> tuple[int, ...] | None:

@@ -8,7 +8,7 @@ phase-split int8 implicit GEMM of csrc/ffq_conv_transpose.hip covers and return 
 
 * the weight is [C, OC, *kernel]: ``input.shape[1] == weight.shape[0]``, and its tile is the whole tensor or ``(C, 1, *kernel)`` —
   ``PerChannel(1)``, one parameter pair per OUTPUT channel. ``PerChannel(0)`` weights (per input channel) take the chain;
-* ``groups == 1``, a batched input, ``C * prod(kernel) <= 131072``, integer stride / padding / output_padding / dilation with
+* ``groups == 1``, a batched input, ``C * prod(kernel) < 131072``, integer stride / padding / output_padding / dilation with
   ``0 <= output_padding < max(stride, dilation)`` (torch's rule), an output of at least one element per axis, and
   ``stride_h * stride_w <= 64`` (the kernel's phase table);
 * bias, gradient and device rules as for the forward convolution.

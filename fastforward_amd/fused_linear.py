@@ -94,6 +94,7 @@ def weight_only_kernel(enabled: bool = True):
 
 
 _FLOATS = (torch.bfloat16, torch.float16, torch.float32)
+MAX_CONTRACTION = 131071  # K of an int8 GEMM: the int32 accumulator's bound, 2^14 * K < 2^31 (include/ffq.h, ffq_linear_w8a8)
 
 
 def _module_hooked(module: Any) -> bool:
@@ -289,7 +290,7 @@ class DispatcherKernels:
         if isinstance(bias, self.surface.quantized_tensor) and not self.static_affine(bias):
             return False
         if self.row_mode(weight) is not None:  # the int8 GEMM
-            return weight.shape[1] % 16 == 0 and self.row_mode(input) is not None
+            return weight.shape[1] % 16 == 0 and weight.shape[1] <= MAX_CONTRACTION and self.row_mode(input) is not None
         # grouped weights (PerBlock(in, G): W4-g128 x A8): the bf16 GEMM on the dequantized input
         return _WEIGHT_ONLY_KERNEL and self._wq_covers(deq, weight, input.numel() // input.shape[-1]) is not None
 
@@ -372,9 +373,9 @@ class DispatcherKernels:
             return False
         if right.dim() > 2:  # matmul with an N-d right operand: the batched launch when the leading dims agree (no broadcasting)
             return (input.dim() == right.dim() and tuple(input.shape[:-2]) == tuple(right.shape[:-2]) and input.shape[-1] == right.shape[-2]
-                    and right.shape[-2] % 16 == 0 and input.numel() > 0 and right.numel() > 0 and math.prod(input.shape[:-2]) <= 65535
+                    and right.shape[-2] % 16 == 0 and right.shape[-2] <= MAX_CONTRACTION and input.numel() > 0 and right.numel() > 0 and math.prod(input.shape[:-2]) <= 65535
                     and self.row_mode(input) == "tensor" and self.row_mode(right) == "tensor")
-        if right.dim() != 2 or input.dim() < 1 or input.shape[-1] != right.shape[0] or right.shape[0] % 16 or input.numel() == 0 or right.numel() == 0:
+        if right.dim() != 2 or input.dim() < 1 or input.shape[-1] != right.shape[0] or right.shape[0] % 16 or right.shape[0] > MAX_CONTRACTION or input.numel() == 0 or right.numel() == 0:
             return False
         return self.row_mode(input) is not None and self.col_mode(right) is not None
 
@@ -401,7 +402,7 @@ class DispatcherKernels:
             return False
         if input.dim() != 3 or mat2.dim() != 3 or input.shape[0] != mat2.shape[0] or input.shape[2] != mat2.shape[1]:
             return False
-        if input.shape[2] % 16 or input.numel() == 0 or mat2.numel() == 0 or input.shape[0] > 65535:
+        if input.shape[2] % 16 or input.shape[2] > MAX_CONTRACTION or input.numel() == 0 or mat2.numel() == 0 or input.shape[0] > 65535:
             return False
         # one parameter pair for each operand: the batch shares it, every matrix of the batch is one GEMM
         return self.row_mode(input) == "tensor" and self.row_mode(mat2) == "tensor"

@@ -224,7 +224,10 @@ int ffq_unpack_int4(const uint8_t* packed, int64_t numel, int64_t block, void* c
  * nn/linear.py:32-39). Integer codes in, real-valued output out:
  *   y[m,n] = sx[m'] * sw[n'] * sum_k (xq[m,k] + ox[m']) * (wq[n,k] + ow[n'])  (+ bias[n])
  * with ox/ow = round_half_even(offset) (A2), m' = m if x_per_row else 0, n' likewise.
- * The contraction runs on int8 MFMA with int32 accumulation; the zero-point terms use row sums.
+ * The contraction runs on int8 MFMA with int32 accumulation; the zero-point terms use row sums. Coverage: K <= 131071 (else
+ * FFQ_ERR_DTYPE before any launch): |acc| <= 2^14 * K stays below 2^31; at K = 131072 two operands of -128 sum to exactly 2^31,
+ * which int32 does not hold. The same bound holds for every entry point of this family (_multi, _earlier, _gated, ffq_bmm_w8a8,
+ * ffq_mlp_gate_up_w8a8, _estimating).
  * If out_scale != NULL the result is re-quantized in the same launch (the `output_quantizer` of fallback.py:110-111,
  * per-tensor A1): y is rounded once to `y_dt` — the dtype the float GEMM of the reference returns, i.e. the input's
  * dequantize dtype (nn/linear.py:32-39) — and codes = clamp(rne(y / out_scale - rne(out_offset))) go to `out` in the
@@ -669,7 +672,8 @@ int ffq_sdpa_quantize(const void* q, const void* k, const void* v, int dt, const
  * If out_scale != NULL the output quantizer (per tensor) runs in the epilogue as in ffq_linear_w8a8: y rounded once to y_dt, then
  * codes = clamp(rne(y / out_scale - rne(out_offset))) into out (out_dt must be int8) — bit-identical to ffq_quantize_by_tile on the
  * tensor the call without out_scale writes in y_dt. Else out holds y in out_dt (f32 / bf16 / f16).
- * Coverage: groups == 1 (the caller's), C * KH * KW <= 131072 (else FFQ_ERR_DTYPE: |acc| stays within int32), stride / dilation
+ * Coverage: groups == 1 (the caller's), C * KH * KW <= 131071 (else FFQ_ERR_DTYPE: |acc| <= 2^14 * C * KH * KW < 2^31 stays within
+ * int32; 131072 taps of -128 x -128 sum to exactly 2^31), stride / dilation
  * >= 1, padding >= 0, extents <= 2^24, B * OH * OW < 2^31. Every argument check runs before any launch.
  * Workspace: ffq_conv2d_w8a8_workspace_bytes(...) bytes, 16-byte aligned — the NHWC input codes (none with x_nhwc), the reordered
  * weight [OC, KH, KW, Cp] and the per-tap weight sums; less returns FFQ_ERR_WORKSPACE. Two launches (layout, GEMM) and a memset.
@@ -705,7 +709,7 @@ int ffq_conv2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, const float*
  * If out_scale != NULL the output quantizer (per tensor) runs in the epilogue under ffq_conv2d_w8a8's rules: y rounded once to
  * y_dt, then codes = clamp(rne(y / out_scale - rne(out_offset))) into out (out_dt must be int8) — bit-identical to
  * ffq_quantize_by_tile on the tensor the call without out_scale writes in y_dt. Else out holds y in out_dt (f32 / bf16 / f16).
- * Coverage: groups == 1 (the caller's), C * KH * KW <= 131072 (else FFQ_ERR_DTYPE), stride / dilation >= 1, padding >= 0,
+ * Coverage: groups == 1 (the caller's), C * KH * KW <= 131071 (else FFQ_ERR_DTYPE), stride / dilation >= 1, padding >= 0,
  * 0 <= out_pad < max(stride, dilation) per axis (torch's rule), stride_h * stride_w <= 64 (the phase table; else FFQ_ERR_ARG),
  * H, W >= 1, OH, OW >= 1, extents <= 2^24, B * OH * OW < 2^31 - 8192. Every argument check runs before any launch; B == 0 or
  * OC == 0 returns FFQ_OK without one.

@@ -673,6 +673,8 @@ int ffq_linear_w8a8(const int8_t* xq, const int8_t* wq, const int32_t* w_rowsum,
   if (M < 0 || N < 0 || K < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (M == 0 || N == 0) return FFQ_OK;
   if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
+  /* the library's int32 accumulator: 2^14 * K must stay below 2^31 (include/ffq.h); the same refusal here, for every caller below */
+  if (K > 131071) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds 131071 (the int32 accumulator's bound)", (long long)K);
   if (K > 0) {  /* sums handed in by the caller must be the sums of the codes */
     int rc = check_rowsum("weight", wq, w_rowsum, N, K);
     if (rc) return rc;

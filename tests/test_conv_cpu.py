@@ -290,7 +290,7 @@ def _conv(lib, x=FAKE, nhwc=0, w=FAKE, xs=FAKE, ws=FAKE, bias=None, bias_dt=0, o
         (lambda lib: _conv(lib, s=(0, 1)), Status.ERR_ARG),
         (lambda lib: _conv(lib, d=(1, 0)), Status.ERR_ARG),
         (lambda lib: _conv(lib, p=(-1, 0)), Status.ERR_ARG),
-        (lambda lib: _conv(lib, C=16385, KH=3, KW=3), Status.ERR_DTYPE),      # C * KH * KW > 131072
+        (lambda lib: _conv(lib, C=16385, KH=3, KW=3), Status.ERR_DTYPE),      # C * KH * KW >= 131072
         (lambda lib: _conv(lib, nhwc=1, C=24), Status.ERR_DTYPE),             # channels-last needs C % 16 == 0
         (lambda lib: _conv(lib, H=2, p=(0, 0)), Status.ERR_ARG),              # filter larger than the padded input
         (lambda lib: _conv(lib, bias=FAKE, bias_dt=DType.I8), Status.ERR_DTYPE),

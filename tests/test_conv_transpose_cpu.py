@@ -308,7 +308,7 @@ def _convt(lib, x=FAKE, nhwc=0, w=FAKE, xs=FAKE, ws=FAKE, bias=None, bias_dt=0, 
         (lambda lib: _convt(lib, op=(2, 2), d=(3, 3), nbytes=16), Status.ERR_WORKSPACE),  # below the dilation: that check passes
         (lambda lib: _convt(lib, s=(8, 9)), Status.ERR_ARG),                   # 72 phases
         (lambda lib: _convt(lib, s=(1, 65)), Status.ERR_ARG),
-        (lambda lib: _convt(lib, C=16385, KH=3, KW=3), Status.ERR_DTYPE),      # C * KH * KW > 131072
+        (lambda lib: _convt(lib, C=16385, KH=3, KW=3), Status.ERR_DTYPE),      # C * KH * KW >= 131072
         (lambda lib: _convt(lib, nhwc=1, C=24), Status.ERR_DTYPE),             # channels-last needs C % 16 == 0
         (lambda lib: _convt(lib, H=1, W=1, KH=1, KW=1, s=(1, 1), p=(1, 1)), Status.ERR_ARG),  # OH < 1
         (lambda lib: _convt(lib, H=0), Status.ERR_ARG),
