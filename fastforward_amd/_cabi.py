@@ -282,6 +282,16 @@ DEVICE_ONLY: frozenset[str] = frozenset({"ffq_gptq_block_grid", "ffq_layer_norm_
                                          "ffq_pool2d_quantize", "ffq_upsample_nearest_quantize", "ffq_cat_quantize", "ffq_pad_quantize"})
 
 
+# name -> (restype, argtypes); mirrors include/ffq_3d.h one to one. A second table for a second header: SIGNATURES is the ABI both
+# libraries export at FFQ_ABI_VERSION 9, and it stays as it is; these entry points exist in the HIP library only. A library that lacks
+# one gets the attribute bound to None (DEVICE_ONLY's rule), whichever library it is.
+SIGNATURES_3D: dict[str, tuple[object, list[object]]] = {
+    "ffq_conv3d_w8a8_workspace_bytes": (_sz, [_i64] * 9 + [_i]),
+    "ffq_conv3d_w8a8": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _d, _i] + [_i64] * 18 + [_vp, _sz, _vp]),
+    "ffq_pool3d_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i] + [_i64] * 13 + [_i, _i64, _i64, _i64, _vp, _fp, _vp]),
+}
+
+
 class FFQLibrary:
     """A loaded implementation of the ``ffq_*`` ABI."""
 
@@ -308,6 +318,12 @@ class FFQLibrary:
             raise ImportError(f"{self.path} does not export {missing[0]}")
         for name in missing:
             setattr(self, name, None)
+        for name, (restype, argtypes) in SIGNATURES_3D.items():
+            fn = getattr(self._dll, name, None)
+            if fn is not None:
+                fn.restype = restype
+                fn.argtypes = argtypes
+            setattr(self, name, fn)
 
     @property
     def is_device(self) -> bool:

@@ -47,14 +47,6 @@ struct ConvArgs {
   int tiles_m, tiles_n;
 };
 
-// [lo, hi) of the taps k with 0 <= o0 + k * d < extent
-__device__ __forceinline__ void tap_range(int o0, int d, int taps, int extent, int& lo, int& hi) {
-  lo = o0 >= 0 ? 0 : (-o0 + d - 1) / d;
-  hi = extent - o0 <= 0 ? 0 : (extent - o0 + d - 1) / d;
-  hi = hi < taps ? hi : taps;
-  if (hi < lo) hi = lo;
-}
-
 // -------------------------------------------------------------------------------------------------
 // Layout pass. Threads [0, n_in) move the input: one (b, 16-channel group, pixel) each, pixel fastest so that each of the 16
 // byte loads of a wave reads 64 consecutive bytes of one channel plane; the 16 bytes leave as one store. Threads
@@ -72,24 +64,7 @@ __global__ __launch_bounds__(256) void conv_layout_kernel(const int8_t* __restri
   }
   const int64_t j = idx - n_in;
   if (j >= n_w) return;
-  const int g = (int)(j % groups);
-  const int64_t row_tap = j / groups;  // n * taps + t
-  const int t = (int)(row_tap % taps);
-  const int64_t n = row_tap / taps;
-  uint8_t v[16];
-  int sum = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int c = g * 16 + k;
-    const int8_t q = c < C ? w[(n * C + c) * taps + t] : (int8_t)0;
-    v[k] = (uint8_t)q;
-    sum += q;
-  }
-  *reinterpret_cast<u32x4*>(wn + row_tap * Cp + g * 16) = pack16(v);
-  if (sum != 0) {
-    atomicAdd(tapsum + row_tap, sum);
-    atomicAdd(tapsum + (int64_t)OC * taps + n, sum);
-  }
+  weight_to_taps16(w, wn, j, C, groups, Cp, taps, OC, tapsum);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// ffq_conv_tile.h — what the two implicit-GEMM convolutions (ffq_conv.hip, ffq_conv_transpose.hip) share: the MFMA operand types,
-// the swizzled LDS address of a 128 x 64 operand tile, the 16-channel packing of the layout passes with their common input half,
-// and the epilogue of one output element (include/ffq.h, ffq_conv2d_w8a8: fp32, left to right, no FMA).
+// ffq_conv_tile.h — what the implicit-GEMM convolutions (ffq_conv.hip, ffq_conv3d.hip, ffq_conv_transpose.hip) share: the MFMA
+// operand types, the swizzled LDS address of a 128 x 64 operand tile, the 16-channel packing of the layout passes with their common
+// input half (and the weight half of the two forward convolutions), the valid-tap range of one axis, and the epilogue of one output
+// element (include/ffq.h, ffq_conv2d_w8a8: fp32, left to right, no FMA).
 #pragma once
 
 #include "ffq_affine.h"
@@ -43,6 +44,38 @@ __device__ __forceinline__ void nchw_to_nhwc16(const int8_t* __restrict__ x, int
     v[k] = c < C ? (uint8_t)x[(b * C + c) * HW + hw] : (uint8_t)0;
   }
   *reinterpret_cast<u32x4*>(xn + (b * HW + hw) * (groups * 16) + g * 16) = pack16(v);
+}
+
+// The weight half of a layout pass: thread j moves one (n, tap, 16-channel group) of [OC, C, taps] into [OC, taps, Cp = groups * 16], and
+// adds the group's code sum into tapsum[n, tap] and into the total of row n (both zeroed ahead of the launch).
+__device__ __forceinline__ void weight_to_taps16(const int8_t* __restrict__ w, int8_t* __restrict__ wn, int64_t j, int C, int groups, int Cp,
+                                                 int taps, int OC, int32_t* __restrict__ tapsum) {
+  const int g = (int)(j % groups);
+  const int64_t row_tap = j / groups;  // n * taps + t
+  const int t = (int)(row_tap % taps);
+  const int64_t n = row_tap / taps;
+  uint8_t v[16];
+  int sum = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const int c = g * 16 + k;
+    const int8_t q = c < C ? w[(n * C + c) * taps + t] : (int8_t)0;
+    v[k] = (uint8_t)q;
+    sum += q;
+  }
+  *reinterpret_cast<u32x4*>(wn + row_tap * Cp + g * 16) = pack16(v);
+  if (sum != 0) {
+    atomicAdd(tapsum + row_tap, sum);
+    atomicAdd(tapsum + (int64_t)OC * taps + n, sum);
+  }
+}
+
+// [lo, hi) of the taps k with 0 <= o0 + k * d < extent
+__device__ __forceinline__ void tap_range(int o0, int d, int taps, int extent, int& lo, int& hi) {
+  lo = o0 >= 0 ? 0 : (-o0 + d - 1) / d;
+  hi = extent - o0 <= 0 ? 0 : (extent - o0 + d - 1) / d;
+  hi = hi < taps ? hi : taps;
+  if (hi < lo) hi = lo;
 }
 
 // y of one output element from its exact accumulator and the offset terms

@@ -17,7 +17,7 @@
 // neighbours in memory: the overlap of a 3x3 stride-2 window is served by the caches), so maps of any width keep the lanes busy. The
 // block's results meet in LDS and leave in 8-element groups — 16 B of values, 8 B of codes per lane through ffq_fanout.h; the last
 // group of a result whose size is no multiple of 8 leaves element by element.
-#include "ffq_onepass.h"
+#include "ffq_pool_tile.h"
 
 namespace ffq {
 namespace pool {
@@ -33,13 +33,6 @@ struct Geometry {
   int32_t exact;           // nearest: "nearest-exact"
   FastDiv by_ow, by_oh, by_channels;
 };
-
-template <typename T, typename TIn, bool DEQ>
-__device__ __forceinline__ float value_at(const TIn* p, float s, float o) {
-  const float q = to_f32(*p);
-  if constexpr (DEQ) return a2_value<T>(q, s, o);
-  return q;
-}
 
 struct Place {
   uint32_t plane;
@@ -122,43 +115,6 @@ __device__ __forceinline__ float nearest_one(const TIn* __restrict__ x, const fl
   return value_at<T, TIn, DEQ>(x + (size_t)p.plane * (size_t)(g.H * g.W) + (h * g.W + w), p.s, p.o);
 }
 
-// The block's kBlock * J results (fp32, in LDS) -> the data dtype and the codes, 8 per lane; the tail of the result one by one.
-template <typename T, int J>
-__device__ __forceinline__ void store_tile(const float* z, uint32_t base, uint32_t total, T* __restrict__ out, const FanOut& f) {
-  const FanParams fp = load_fan(f);
-  for (uint32_t c = threadIdx.x; c < (uint32_t)(kBlock * J / kE); c += kBlock) {
-    const uint32_t at = base + c * kE;
-    if (at >= total) return;
-    float v[kE];
-#pragma unroll
-    for (int i = 0; i < kE; ++i) v[i] = z[c * kE + i];
-    if (at + kE <= total) {  // (store_chunk's and, below, store_one's steps, spelled out: the helpers change this loop's registers)
-      Chunk<T, kE> y;
-      y.pack(v);  // the one rounding to the data dtype
-      if (out) y.store(out + at);
-#pragma unroll
-      for (int i = 0; i < kE; ++i) v[i] = y.get(i);
-      fan_store(f, fp, v, (size_t)at);
-      continue;
-    }
-    const int ilo = (int)f.lo, ihi = (int)f.hi;
-    for (uint32_t i = 0; at + i < total; ++i) {
-      const float one[1] = {round_stage(z[c * kE + i], TypeTag<T>::value)};
-      if (out) out[at + i] = from_f32<T>(one[0]);
-#pragma unroll
-      for (int j = 0; j < FFQ_MAX_FANOUT; ++j) {
-        if (j >= f.n) break;
-        const Divider<1> d(fp.s[j]);
-        float r[1];
-        quantize_chunk_with<1, 1>(d, one, fp.o[j], r);
-        int code = (int)r[0];  // v_cvt_i32_f32 saturates and maps NaN to 0, as finalize_chunk
-        code = code < ilo ? ilo : (code > ihi ? ihi : code);
-        f.codes[j][at + i] = (int8_t)code;
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------
 // P1: avg / max pool of [planes, H, W] + A1. A block computes kBlock * J consecutive outputs, lane t the outputs t, t + kBlock, ...
 //     Algorithmic bytes: the input once (2 B bf16 / 1 B int8 per element) + per output [2 (z)] + 1 per code tensor.
@@ -196,20 +152,6 @@ __global__ __launch_bounds__(kBlock) void upsample_nearest_quantize_kernel(const
   store_tile<T, J>(z, base, g.total, out, f);
 }
 
-// ATen's pooling_output_shape: the last window starts inside the input or its left padding.
-static int64_t pooled(int64_t in, int64_t k, int64_t pad, int64_t stride, int64_t dil, bool ceil_mode) {
-  const int64_t num = in + 2 * pad - dil * (k - 1) - 1 + (ceil_mode ? stride - 1 : 0);
-  int64_t out = (num >= 0 ? num / stride : -((-num + stride - 1) / stride)) + 1;
-  if (ceil_mode && (out - 1) * stride >= in + pad) --out;
-  return out;
-}
-
-// The checks both entry points share: dtypes first (before any buffer is looked at), then extents and buffers.
-static int check_dtypes(const char* what, int x_dt, const float* scale, const float* offset, int64_t channels, int dt) {
-  if (!value_dtype(dt)) return fail(FFQ_ERR_DTYPE, "%s is built for bf16 / fp16 values", what);
-  return check_operand_form(what, x_dt, scale, offset, channels != 0, dt);
-}
-
 static int check_extents(const char* what, int64_t channels, int64_t planes, int64_t H, int64_t W, int64_t OH, int64_t OW) {
   if (planes < 0 || H < 0 || W < 0 || channels < 0) return fail(FFQ_ERR_ARG, "%s: negative extent", what);
   if (channels && planes % channels != 0) return fail(FFQ_ERR_ARG, "%s: %lld planes are not whole images of %lld channels", what, (long long)planes, (long long)channels);
@@ -233,9 +175,6 @@ static void fill(Geometry* g, int64_t channels, int64_t planes, int64_t H, int64
   g->by_oh = make_fastdiv((uint32_t)OH);
   g->by_channels = make_fastdiv(g->channels);
 }
-
-// Outputs per lane: 8 when that still leaves two blocks per CU of a 256-CU device, else 1 (small results want the lanes).
-static int per_lane(uint32_t total) { return total >= 8u * kBlock * 512u ? 8 : 1; }
 
 }  // namespace pool
 }  // namespace ffq

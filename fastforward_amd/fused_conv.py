@@ -44,9 +44,9 @@ def _ints(v: Any, n: int) -> tuple[int, ...] | None:
     return None
 
 
-def geometry(dims: int, input_shape: Any, kernel: Any, stride: Any, padding: Any, dilation: Any) -> tuple[tuple[int, int], ...] | None:
-    """((stride_h, stride_w), (pad_h, pad_w), (dil_h, dil_w)) of the 2-D launch, or None where the kernel does not take the call
-    (then F.conv raises or computes it on the fallback)."""
+def geometry(dims: int, input_shape: Any, kernel: Any, stride: Any, padding: Any, dilation: Any) -> tuple[tuple[int, ...], ...] | None:
+    """((stride_h, stride_w), (pad_h, pad_w), (dil_h, dil_w)) of the 2-D launch (one triple each for the 3-D launch of
+    fused_conv3d.py), or None where the kernel does not take the call (then F.conv raises or computes it on the fallback)."""
     s, d = _ints(stride, dims), _ints(dilation, dims)
     if s is None or d is None or min(s) < 1 or min(d) < 1:
         return None
@@ -65,7 +65,7 @@ def geometry(dims: int, input_shape: Any, kernel: Any, stride: Any, padding: Any
         return None
     if dims == 1:
         return (1, s[0]), (0, p[0]), (1, d[0])
-    return (s[0], s[1]), (p[0], p[1]), (d[0], d[1])
+    return tuple(s), tuple(p), tuple(d)
 
 
 class ConvKernels:

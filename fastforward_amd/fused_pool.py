@@ -1,19 +1,22 @@
-"""The spatial operators — ``avg_pool1d``, ``avg_pool2d``, ``max_pool2d``, ``interpolate`` — registered in this package's dispatcher.
+"""The spatial operators — ``avg_pool1d``, ``avg_pool2d``, ``avg_pool3d``, ``max_pool2d``, ``interpolate`` — registered in this package's
+dispatcher.
 
 The reference registers no kernel for them: ff.nn.functional runs the generated fallbacks (src/fastforward/_gen/fallback.py:
-avg_pool1d :505, avg_pool2d :542, max_pool2d :1574, interpolate :1611) — A2 of the quantized input, the ATen op, the output
+avg_pool1d :505, avg_pool2d :542, avg_pool3d :579, max_pool2d :1574, interpolate :1611) — A2 of the quantized input, the ATen op, the output
 quantizer: three launches with a temporary between each. The predicates below accept what the one-pass kernels of
-csrc/ffq_pool.hip cover and return False for everything else, so the reference chain (the fallbacks in
+csrc/ffq_pool.hip (and csrc/ffq_pool3d.hip) cover and return False for everything else, so the reference chain (the fallbacks in
 :mod:`fastforward_amd.nn.functional`) runs unchanged there. They follow the rules of ``MathKernels`` (fused_math.py):
 
 * calls of ``ff.nn.functional`` only: a call without the ``strict_quantization`` keyword is declined;
 * the input on the HIP device and the device library loaded (the C oracle declines);
 * bf16 / fp16 values: a plain tensor, or static-affine codes (int8 or value-dtype container, <= 8 bits, fp32 parameters) with
   per-tensor or per-channel (``PerChannel(1)``) parameters;
-* a batched input: ``[B, C, H, W]`` for the 2-D pools, ``[B, C, L]`` for ``avg_pool1d``, either for ``interpolate``; fewer than 2^31
+* a batched input: ``[B, C, H, W]`` for the 2-D pools, ``[B, C, L]`` for ``avg_pool1d``, ``[B, C, D, H, W]`` for ``avg_pool3d`` (whose
+  entry point, include/ffq_3d.h, the loaded library must export), 3-D or 4-D for ``interpolate``; fewer than 2^31
   input and output elements. Planes of any size: nothing here asks for a multiple of 8;
 * any layout but one: a strided or misaligned view reaches the kernel as an aligned copy (``ops._base._dense``); an input whose
-  strides are channels-last is declined, because ATen answers it with a channels-last result;
+  strides are channels-last is declined, because ATen answers it with a channels-last result (``avg_pool3d`` declines a
+  ``channels_last_3d`` input likewise);
 * the pools: int or tuple ``kernel_size`` / ``stride`` / ``padding`` (/ ``dilation``), ``ceil_mode`` and ``count_include_pad``
   either way; geometry ATen refuses (padding beyond half the kernel, an empty output) is declined, so the fallback raises ATen's error;
 * ``interpolate``: ``mode`` "nearest" or "nearest-exact", exactly one of ``size`` / ``scale_factor``, ``align_corners`` None,
@@ -33,7 +36,7 @@ from typing import Any
 
 import torch
 
-from fastforward_amd import ops
+from fastforward_amd import _native, ops
 from fastforward_amd.dispatcher import Predicate, register
 from fastforward_amd.fused_elementwise import _number
 from fastforward_amd.fused_linear import KERNELS as _LINEAR
@@ -83,7 +86,10 @@ class PoolKernels(MathKernels):
             if tile != shape and tile != (shape[0], 1, *shape[2:]):
                 return None
             data = x.raw_data
-        if not data.is_contiguous() and _channels_last_strides(data if data.dim() == 4 else data.unsqueeze(-2)):
+        if data.dim() == 5:
+            if not data.is_contiguous() and data.is_contiguous(memory_format=torch.channels_last_3d):
+                return None
+        elif not data.is_contiguous() and _channels_last_strides(data if data.dim() == 4 else data.unsqueeze(-2)):
             return None
         return dt
 
@@ -120,6 +126,14 @@ class PoolKernels(MathKernels):
             return False
         return self._supported_pool(2, input, kernel_size, stride, padding, 1, ceil_mode, output_quantizer, kwargs)
 
+    def supported_avg_pool3d(self, input: Any = None, kernel_size: Any = None, stride: Any = None, padding: Any = 0, ceil_mode: Any = False,
+                             count_include_pad: Any = True, *_args: Any, output_quantizer: Any = None, **kwargs: Any) -> bool:
+        if _args or not isinstance(count_include_pad, bool):
+            return False
+        if not self._supported_pool(3, input, kernel_size, stride, padding, 1, ceil_mode, output_quantizer, kwargs):
+            return False
+        return getattr(_native.library(), "ffq_pool3d_quantize", None) is not None
+
     def supported_max_pool2d(self, input: Any = None, kernel_size: Any = None, stride: Any = None, padding: Any = 0, dilation: Any = 1,
                              ceil_mode: Any = False, *_args: Any, output_quantizer: Any = None, **kwargs: Any) -> bool:
         if _args:
@@ -147,6 +161,16 @@ class PoolKernels(MathKernels):
     def avg_pool2d(self, input: Any, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *,
                    output_quantizer: Any = None, strict_quantization: bool | None = None) -> Any:
         return self._pool("avg" if count_include_pad else "avg_exclude_pad", 2, input, kernel_size, stride, padding, 1, ceil_mode, output_quantizer)
+
+    def avg_pool3d(self, input: Any, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *,
+                   output_quantizer: Any = None, strict_quantization: bool | None = None) -> Any:
+        dt = self._value_dtype(input)
+        x, dequant = self._dequant(input)
+        fused = self._output(output_quantizer, dt)
+        k, s, p = (_ints(v, 3) for v in (kernel_size, stride, padding))
+        value, codes = ops.pool3d_quantize("avg" if count_include_pad else "avg_exclude_pad", x, k, s, p, ceil_mode, dtype=dt, dequant=dequant,
+                                           **self._launch_args(fused))
+        return self._finish(value, codes, fused, output_quantizer, dt)
 
     def max_pool2d(self, input: Any, kernel_size: Any, stride: Any = None, padding: Any = 0, dilation: Any = 1, ceil_mode: bool = False, *,
                    output_quantizer: Any = None, strict_quantization: bool | None = None) -> Any:
@@ -204,11 +228,13 @@ class PoolKernels(MathKernels):
 KERNELS = PoolKernels(_LINEAR)
 avg_pool1d_predicate = Predicate(KERNELS.supported_avg_pool1d)
 avg_pool2d_predicate = Predicate(KERNELS.supported_avg_pool2d)
+avg_pool3d_predicate = Predicate(KERNELS.supported_avg_pool3d)
 max_pool2d_predicate = Predicate(KERNELS.supported_max_pool2d)
 interpolate_predicate = Predicate(KERNELS.supported_interpolate)
 _registrations = {
     "avg_pool1d": register("avg_pool1d", avg_pool1d_predicate, KERNELS.avg_pool1d),
     "avg_pool2d": register("avg_pool2d", avg_pool2d_predicate, KERNELS.avg_pool2d),
+    "avg_pool3d": register("avg_pool3d", avg_pool3d_predicate, KERNELS.avg_pool3d),
     "max_pool2d": register("max_pool2d", max_pool2d_predicate, KERNELS.max_pool2d),
     "interpolate": register("interpolate", interpolate_predicate, KERNELS.interpolate),
 }

@@ -30,3 +30,5 @@ from fastforward_amd.nn.conv import quantized_conv_modules as quantized_conv_mod
 from fastforward_amd.nn.conv import QuantizedConvTranspose1d as QuantizedConvTranspose1d  # isort: skip
 from fastforward_amd.nn.conv import QuantizedConvTranspose2d as QuantizedConvTranspose2d  # isort: skip
 from fastforward_amd.nn.conv import quantized_conv_transpose_modules as quantized_conv_transpose_modules  # isort: skip
+from fastforward_amd.nn.conv import QuantizedConv3d as QuantizedConv3d  # isort: skip
+from fastforward_amd.nn.conv import quantized_conv3d_modules as quantized_conv3d_modules  # isort: skip

@@ -13,6 +13,9 @@ convert them, as the Llama harness asks for its embedding class::
 ``QuantizedConvTranspose1d`` / ``QuantizedConvTranspose2d`` have no counterpart in the reference (it has the functional operators
 only): they follow ``_QuantizedConv`` — the same four slots — and ``torch.nn.ConvTranspose2d.forward`` for ``output_size``. They are
 offered through ``ff.nn.quantized_conv_transpose_modules()``; ``quantized_conv_modules()`` stays Conv1d / Conv2d.
+
+``QuantizedConv3d`` has no counterpart in the reference either (functional ``conv3d`` only): it is ``_QuantizedConv`` on
+``torch.nn.Conv3d``, offered through ``ff.nn.quantized_conv3d_modules()``.
 """
 
 from __future__ import annotations
@@ -21,7 +24,7 @@ from typing import Callable
 
 import torch
 
-from fastforward_amd.nn.functional import conv1d, conv2d, conv_transpose1d, conv_transpose2d
+from fastforward_amd.nn.functional import conv1d, conv2d, conv3d, conv_transpose1d, conv_transpose2d
 from fastforward_amd.nn.quantized_module import QuantizedModule
 from fastforward_amd.nn.quantizer import Quantizer, QuantizerStub
 
@@ -60,6 +63,10 @@ class QuantizedConv1d(_QuantizedConv, torch.nn.Conv1d, include_in_module_map=Fal
     _functional = staticmethod(conv1d)
 
 
+class QuantizedConv3d(_QuantizedConv, torch.nn.Conv3d, include_in_module_map=False):
+    _functional = staticmethod(conv3d)
+
+
 class _QuantizedConvTranspose(_QuantizedConv, include_in_module_map=False):
     _dims: int
 
@@ -93,3 +100,8 @@ def quantized_conv_modules() -> dict[type[torch.nn.Module], type[QuantizedModule
 def quantized_conv_transpose_modules() -> dict[type[torch.nn.Module], type[QuantizedModule]]:
     """The ``extra_conversion`` entries of ``quantize_model`` that convert ConvTranspose1d / ConvTranspose2d."""
     return {torch.nn.ConvTranspose1d: QuantizedConvTranspose1d, torch.nn.ConvTranspose2d: QuantizedConvTranspose2d}
+
+
+def quantized_conv3d_modules() -> dict[type[torch.nn.Module], type[QuantizedModule]]:
+    """The ``extra_conversion`` entry of ``quantize_model`` that converts Conv3d."""
+    return {torch.nn.Conv3d: QuantizedConv3d}

@@ -1,5 +1,5 @@
 """Quantized functional operators: the linear path (``linear``, ``matmul``, ``mm``, ``bmm``), the convolutions (``conv1d``,
-``conv2d``, ``conv_transpose1d``, ``conv_transpose2d``), the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``) and the elementwise operators of a
+``conv2d``, ``conv3d``, ``conv_transpose1d``, ``conv_transpose2d``), the generic modules' operators (``layer_norm``, ``embedding``, ``relu``, ``silu``) and the elementwise operators of a
 transformer block outside its linears (``add``, ``sub``, ``mul``, ``div``, ``softmax``, ``sigmoid``, ``gelu``).
 
 Reference: the generated ``ff.nn.functional.*`` (src/fastforward/_gen/operators.py:79-106 for
@@ -22,8 +22,10 @@ theirs (_gen/fallback.py:1453-1479, 1546-1570) with the reference's signatures (
 parameters, without an output quantizer, is the reference's concatenation of the codes
 (quantization/_linear_quantized_ops.py:174-224). ``conv_transpose1d`` and ``conv_transpose2d`` follow theirs
 (_gen/fallback.py:346-449) with the reference's signatures, and ``fastforward_amd.fused_conv_transpose`` registers the phase-split
-int8 implicit GEMM. The other generated operators of the reference (``conv3d``, ``conv_transpose3d``, ``avg_pool3d`` among them) are
-pure float fallbacks and are out of scope.
+int8 implicit GEMM. ``conv3d`` and ``avg_pool3d`` follow theirs (_gen/fallback.py:218-265, 579-612) with the reference's signatures;
+``fastforward_amd.fused_conv3d`` registers the 3-D int8 implicit GEMM and ``fastforward_amd.fused_pool`` the one-pass 3-D average
+pool (entry points of include/ffq_3d.h). The other generated operators of the reference (``conv_transpose3d`` among them) are pure
+float fallbacks and are out of scope.
 """
 
 from __future__ import annotations
@@ -40,9 +42,9 @@ from fastforward_amd.quantized_tensor import QuantizedTensor
 if TYPE_CHECKING:
     from fastforward_amd.nn.quantizer import Quantizer
 
-__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "conv_transpose1d", "conv_transpose2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
+__all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "conv3d", "conv_transpose1d", "conv_transpose2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
            "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
-           "cumsum", "avg_pool1d", "avg_pool2d", "max_pool2d", "interpolate", "cat", "pad"]
+           "cumsum", "avg_pool1d", "avg_pool2d", "avg_pool3d", "max_pool2d", "interpolate", "cat", "pad"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -196,6 +198,7 @@ def _conv_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., torch
 
 _fallback_conv1d = _conv_fallback(torch.nn.functional.conv1d)  # fallback.py:116-164
 _fallback_conv2d = _conv_fallback(torch.nn.functional.conv2d)  # fallback.py:167-214
+_fallback_conv3d = _conv_fallback(torch.nn.functional.conv3d)  # fallback.py:218-265
 
 
 def conv1d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
@@ -206,6 +209,11 @@ def conv1d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None 
 def conv2d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("conv2d", **kwargs) or _fallback_conv2d)(**kwargs)
+
+
+def conv3d(input: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, weight=weight, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("conv3d", **kwargs) or _fallback_conv3d)(**kwargs)
 
 
 # ---- the transposed convolutions (reference _gen/operators.py:362-392: dispatch(op, **kwargs) or the generated fallback) --------
@@ -409,6 +417,7 @@ def _avg_pool_fallback(torch_op: Callable[..., torch.Tensor]) -> Callable[..., t
 
 _fallback_avg_pool1d = _avg_pool_fallback(torch.nn.functional.avg_pool1d)  # fallback.py:505-538
 _fallback_avg_pool2d = _avg_pool_fallback(torch.nn.functional.avg_pool2d)  # fallback.py:542-575
+_fallback_avg_pool3d = _avg_pool_fallback(torch.nn.functional.avg_pool3d)  # fallback.py:579-612
 
 
 def _fallback_max_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any = None, padding: Any = 0, dilation: Any = 1, ceil_mode: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
@@ -435,6 +444,11 @@ def avg_pool1d(input: torch.Tensor, kernel_size: Any, stride: Any, padding: Any 
 def avg_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, kernel_size=kernel_size, stride=stride, padding=padding, ceil_mode=ceil_mode, count_include_pad=count_include_pad, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("avg_pool2d", **kwargs) or _fallback_avg_pool2d)(**kwargs)
+
+
+def avg_pool3d(input: torch.Tensor, kernel_size: Any, stride: Any, padding: Any = 0, ceil_mode: bool = False, count_include_pad: bool = True, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, kernel_size=kernel_size, stride=stride, padding=padding, ceil_mode=ceil_mode, count_include_pad=count_include_pad, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("avg_pool3d", **kwargs) or _fallback_avg_pool3d)(**kwargs)
 
 
 def max_pool2d(input: torch.Tensor, kernel_size: Any, stride: Any = None, padding: Any = 0, dilation: Any = 1, ceil_mode: bool = False, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:

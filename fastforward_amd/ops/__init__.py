@@ -12,9 +12,9 @@ the library (outputs and scratch are torch allocations), legal under hipGraph ca
 The package is split by family (round 6; one 1,700-line module before): ``static`` (the four registry operators and the row-batched
 forms of A1), ``reductions`` (A4 / A5), ``packing`` (A7, GGUF, GPTQ, the grid estimator), ``gemm`` (A6 on int8 codes), ``wq`` (A6 with a
 quantized weight and a plain input), ``producers`` (RMSNorm / SiLU*up / rotary / attention with A1 fused), ``modules``
-(LayerNorm / Embedding / ReLU / SiLU with A2 and A1 fused), ``conv`` (the W8A8 convolution), ``elementwise`` (add / sub / mul / div,
+(LayerNorm / Embedding / ReLU / SiLU with A2 and A1 fused), ``conv`` (the W8A8 convolutions, 2-D, transposed and 3-D), ``elementwise`` (add / sub / mul / div,
 softmax, sigmoid, GELU with A2 and A1 fused), ``math`` (rms_norm, pow by a number, exp / sin / cos, sum and cumsum with A2 and A1
-fused), ``pool`` (avg_pool1d / avg_pool2d / max_pool2d and nearest interpolate with A2 and A1 fused), ``concat`` (cat and pad with A2 and A1 fused), ``sdpa`` (the quantized scaled_dot_product_attention in one launch), ``registry`` (the torch operator
+fused), ``pool`` (avg_pool1d / avg_pool2d / avg_pool3d / max_pool2d and nearest interpolate with A2 and A1 fused), ``concat`` (cat and pad with A2 and A1 fused), ``sdpa`` (the quantized scaled_dot_product_attention in one launch), ``registry`` (the torch operator
 library and the C++ extension), ``_base`` (device check, tags, scratch). Every public name is re-exported here: ``ops.linear_wq`` etc.
 """
 
@@ -48,10 +48,10 @@ from fastforward_amd.ops.producers import (  # noqa: F401
 from fastforward_amd.ops.modules import (  # noqa: F401
     embedding_quantize, layer_norm_quantize, pointwise_quantize,
 )
-from fastforward_amd.ops.conv import conv2d_w8a8, conv_transpose2d_w8a8  # noqa: F401
+from fastforward_amd.ops.conv import conv2d_w8a8, conv3d_w8a8, conv_transpose2d_w8a8  # noqa: F401
 from fastforward_amd.ops.elementwise import activation_quantize, binary_quantize, softmax_quantize  # noqa: F401
 from fastforward_amd.ops.math import cumsum_quantize, rms_norm_quantize, sum_quantize, unary_quantize  # noqa: F401
-from fastforward_amd.ops.pool import pool2d_quantize, upsample_nearest_quantize  # noqa: F401
+from fastforward_amd.ops.pool import pool2d_quantize, pool3d_quantize, upsample_nearest_quantize  # noqa: F401
 from fastforward_amd.ops.concat import cat_quantize, pad_quantize  # noqa: F401
 from fastforward_amd.ops.sdpa import sdpa_quantize  # noqa: F401
 from fastforward_amd.ops.registry import NATIVE_DISPATCH, TORCH_EXTENSION_PATH, _LIBRARY  # noqa: F401,E402
@@ -90,6 +90,7 @@ __all__ = [
     "pointwise_quantize",
     "conv2d_w8a8",
     "conv_transpose2d_w8a8",
+    "conv3d_w8a8",
     "binary_quantize",
     "softmax_quantize",
     "activation_quantize",
@@ -99,6 +100,7 @@ __all__ = [
     "cumsum_quantize",
     "pool2d_quantize",
     "upsample_nearest_quantize",
+    "pool3d_quantize",
     "cat_quantize",
     "pad_quantize",
     "sdpa_quantize",

@@ -1,6 +1,7 @@
 """The W8A8 convolution on int8 codes (csrc/ffq_conv.hip): what QuantizedConv2d / QuantizedConv1d run on the device instead of the
 reference's fallback.conv2d / fallback.conv1d (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer),
-and its transposed twin (csrc/ffq_conv_transpose.hip; fallback.conv_transpose1d / conv_transpose2d, _gen/fallback.py:346-449)."""
+its transposed twin (csrc/ffq_conv_transpose.hip; fallback.conv_transpose1d / conv_transpose2d, _gen/fallback.py:346-449), and the
+3-D convolution (csrc/ffq_conv3d.hip; fallback.conv3d, _gen/fallback.py:218-265; include/ffq_3d.h)."""
 
 from __future__ import annotations
 
@@ -168,6 +169,84 @@ def conv_transpose2d_w8a8(
             _ptr(xc), int(nhwc), _ptr(wc), _ptr(xs), _ptr(xo), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
             _ptr(bias_c), _tag(bias_c.dtype) if bias_c is not None else 0, _ptr(out), _tag(out.dtype), _ptr(os_), _ptr(oo),
             float(out_num_bits), y_dt, B, C, H, W, OC, KH, KW, sh, sw, ph, pw, oph, opw, dh, dw, _ptr(ws), nbytes, stream,
+        )
+    )
+    return out
+
+
+def _triple(v: int | Sequence[int], what: str) -> tuple[int, int, int]:
+    if isinstance(v, int):
+        return v, v, v
+    t = tuple(int(e) for e in v)
+    if len(t) != 3:
+        raise RuntimeError(f"conv3d_w8a8: {what} is an int or a triple, got {v!r}")
+    return t  # type: ignore[return-value]
+
+
+def conv3d_w8a8(
+    x_codes: torch.Tensor,
+    w_codes: torch.Tensor,
+    x_scale: torch.Tensor,
+    x_offset: torch.Tensor | None,
+    w_scale: torch.Tensor,
+    w_offset: torch.Tensor | None,
+    bias: torch.Tensor | None = None,
+    stride: int | Sequence[int] = 1,
+    padding: int | Sequence[int] = 0,
+    dilation: int | Sequence[int] = 1,
+    out_dtype: torch.dtype = torch.bfloat16,
+    out_scale: torch.Tensor | None = None,
+    out_offset: torch.Tensor | None = None,
+    out_num_bits: float = 8.0,
+    requant_from: torch.dtype | None = None,
+) -> torch.Tensor:
+    """``F.conv3d`` (groups = 1) on int8 codes: `x_codes` [B, C, D, H, W] (contiguous, or ``torch.channels_last_3d`` with
+    C % 16 == 0, which skips the layout pass's input half), `w_codes` [OC, C, KD, KH, KW]; parameters, bias, `padding` (an int or a
+    triple, symmetric per side) and the output quantizer as in :func:`conv2d_w8a8`. Returns the contiguous [B, OC, OD, OH, OW]
+    result (include/ffq_3d.h, ffq_conv3d_w8a8). Raises ``BackendError`` ("not covered") on a library without the entry point."""
+    op = "conv3d_w8a8"
+    if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
+        raise TypeError(f"{op} expects int8 codes")
+    if x_codes.dim() != 5 or w_codes.dim() != 5:
+        raise RuntimeError(f"{op}: input [B, C, D, H, W] and weight [OC, C, KD, KH, KW], got {tuple(x_codes.shape)} and {tuple(w_codes.shape)}")
+    B, C, D, H, W = x_codes.shape
+    OC, Cw, KD, KH, KW = w_codes.shape
+    if Cw != C:
+        raise RuntimeError(f"{op}: the weight has {Cw} input channels, the input {C} (groups > 1 is not built)")
+    s, p, d = _triple(stride, "stride"), _triple(padding, "padding"), _triple(dilation, "dilation")
+    ndhwc = (not x_codes.is_contiguous()) and C % 16 == 0 and x_codes.is_contiguous(memory_format=torch.channels_last_3d)
+    xc = _dense(x_codes.detach(), torch.channels_last_3d if ndhwc else torch.contiguous_format)
+    wc = _dense(w_codes.detach())
+
+    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
+        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
+
+    xs, xo, ws_, wo, os_, oo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(out_scale), f32(out_offset)
+    if xs.numel() != 1 or (xo is not None and xo.numel() != 1):
+        raise RuntimeError(f"{op}: the input has one parameter pair (per-tensor)")
+    if ws_.numel() not in (1, OC) or (wo is not None and wo.numel() != ws_.numel()):
+        raise RuntimeError(f"{op}: the weight has 1 or {OC} parameter pairs, got {ws_.numel()}")
+    if os_ is not None and (os_.numel() != 1 or (oo is not None and oo.numel() != 1)):
+        raise RuntimeError(f"{op}: the output quantizer is per tensor")
+    if os_ is None and out_dtype not in _REAL:
+        raise RuntimeError(f"{op}: a real-valued output is f32, bf16 or f16, got {out_dtype}")
+    bias_c = None if bias is None else bias.detach().reshape(-1).contiguous()
+    if bias_c is not None and (bias_c.numel() != OC or bias_c.dtype not in _REAL):
+        raise RuntimeError(f"{op}: the bias is [{OC}] of f32, bf16 or f16")
+    lib, stream = _base._prepare(xc, wc, xs, xo, ws_, wo, bias_c, os_, oo)
+    entry = getattr(lib, "ffq_conv3d_w8a8", None)
+    if entry is None:
+        raise BackendError("not covered: the loaded library does not export ffq_conv3d_w8a8 (include/ffq_3d.h; a host library has no convolution kernel)")
+    size = [max((n + 2 * pi - di * (k - 1) - 1) // si + 1, 0) for n, k, si, pi, di in zip((D, H, W), (KD, KH, KW), s, p, d)]
+    out = torch.empty((B, OC, *size), dtype=torch.int8 if os_ is not None else out_dtype, device=xc.device)
+    nbytes = lib.ffq_conv3d_w8a8_workspace_bytes(B, C, D, H, W, OC, KD, KH, KW, int(ndhwc))
+    ws = _workspace(nbytes, xc.device)
+    y_dt = _tag(requant_from or torch.bfloat16) if os_ is not None else 0
+    lib.check(
+        entry(
+            _ptr(xc), int(ndhwc), _ptr(wc), _ptr(xs), _ptr(xo), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
+            _ptr(bias_c), _tag(bias_c.dtype) if bias_c is not None else 0, _ptr(out), _tag(out.dtype), _ptr(os_), _ptr(oo),
+            float(out_num_bits), y_dt, B, C, D, H, W, OC, KD, KH, KW, *s, *p, *d, _ptr(ws), nbytes, stream,
         )
     )
     return out

@@ -5,7 +5,9 @@ interpolate :1611).
 
 The input is ``[B, C, H, W]`` (the 1-D forms come as ``[B, C, 1, L]``). Given as codes it comes with ``dequant=(scale, offset)``:
 int8 or value-dtype codes with fp32 parameters, one pair for the tensor or one per channel. Each function returns
-``(value or None, [codes per quantizer])``; the value has the data dtype and the shape the ATen op gives."""
+``(value or None, [codes per quantizer])``; the value has the data dtype and the shape the ATen op gives.
+
+``avg_pool3d`` (reference _gen/fallback.py:579) is csrc/ffq_pool3d.hip's one pass over ``[B, C, D, H, W]`` (include/ffq_3d.h)."""
 
 from __future__ import annotations
 
@@ -13,6 +15,7 @@ import ctypes
 
 import torch
 
+from fastforward_amd.exceptions import BackendError
 from fastforward_amd.ops import _base
 from fastforward_amd.ops._base import _ptr, _tag
 from fastforward_amd.ops.modules import Quantizers, _entry, _operand
@@ -79,6 +82,57 @@ def pool2d_quantize(
         _entry(lib, "ffq_pool2d_quantize")(
             POOL_MODES[mode], _ptr(xc), _tag(xc.dtype), _ptr(s), _ptr(o), C if per_channel else 0, _tag(dtype), B * C, H, W, kh, kw, sh, sw,
             ph, pw, dh, dw, int(bool(ceil_mode)), OH, OW, _ptr(value), ctypes.byref(fan), stream,
+        )
+    )
+    del keep
+    return value, codes
+
+
+def _triple(v, what: str) -> tuple[int, int, int]:
+    t = tuple(v)
+    if len(t) != 3 or any(isinstance(e, bool) or not isinstance(e, int) for e in t):
+        raise RuntimeError(f"{what} is a triple of ints, got {v!r}")
+    return t  # type: ignore[return-value]
+
+
+def pool3d_quantize(
+    mode: str,
+    x: torch.Tensor,
+    kernel_size: tuple[int, int, int],
+    stride: tuple[int, int, int],
+    padding: tuple[int, int, int] = (0, 0, 0),
+    ceil_mode: bool = False,
+    quantizers: Quantizers = (),
+    num_bits: float = 8.0,
+    dtype: torch.dtype | None = None,
+    dequant: tuple[torch.Tensor, torch.Tensor | None] | None = None,
+    want_value: bool = True,
+) -> tuple[torch.Tensor | None, list[torch.Tensor]]:
+    """``F.avg_pool3d`` (mode="avg": count_include_pad, "avg_exclude_pad": without) of `x` [B, C, D, H, W] + A1, one pass; every
+    geometry argument is a (d, h, w) triple. `x` plain or codes with per-tensor or per-channel parameters. Geometry ATen refuses
+    raises before a launch; a library without the entry point raises ``BackendError`` ("not covered")."""
+    if mode not in ("avg", "avg_exclude_pad"):
+        raise RuntimeError(f"pool3d_quantize: mode is 'avg' or 'avg_exclude_pad', got {mode!r}")
+    dtype = dtype or x.dtype
+    if x.dim() != 5:
+        raise RuntimeError(f"pool3d_quantize: the input is [B, C, D, H, W], got {x.dim()} dims")
+    B, C, D, H, W = x.shape
+    k, s_, p = _triple(kernel_size, "kernel_size"), _triple(stride, "stride"), _triple(padding, "padding")
+    if min(*k, *s_) < 1 or min(p) < 0 or 0 in (D, H, W):
+        raise RuntimeError("pool3d_quantize: kernel size and stride must be positive, padding non-negative, the map not empty")
+    size = [pooled_size(n, ki, pi, si, 1, ceil_mode) for n, ki, pi, si in zip((D, H, W), k, p, s_)]
+    xc, s, o, per_channel = _operand(x, dtype, C, dequant, "pool3d_quantize")
+    lib, stream = _base._prepare(xc, s, o, *[t for q in quantizers for t in q])
+    entry = getattr(lib, "ffq_pool3d_quantize", None)
+    if entry is None:
+        raise BackendError("not covered: the loaded library does not export ffq_pool3d_quantize (include/ffq_3d.h)")
+    shape = (B, C, *(max(n, 0) for n in size))
+    value = torch.empty(shape, dtype=dtype, device=xc.device) if want_value else None
+    fan, codes, keep = _fan(quantizers, num_bits, shape, xc.device)
+    lib.check(
+        entry(
+            POOL_MODES[mode], _ptr(xc), _tag(xc.dtype), _ptr(s), _ptr(o), C if per_channel else 0, _tag(dtype), B * C, D, H, W, *k, *s_, *p,
+            int(bool(ceil_mode)), *size, _ptr(value), ctypes.byref(fan), stream,
         )
     )
     del keep
