@@ -40,6 +40,7 @@ import fastforward_amd.fused_modules  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_conv  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_conv_transpose  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_conv3d  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_depthwise  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_elementwise  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_math  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_pool  # noqa: E402,F401  isort: skip

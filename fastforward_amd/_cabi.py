@@ -291,6 +291,12 @@ SIGNATURES_3D: dict[str, tuple[object, list[object]]] = {
     "ffq_pool3d_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i64, _i] + [_i64] * 13 + [_i, _i64, _i64, _i64, _vp, _fp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ffq_depthwise.h one to one: the third header's table, bound as SIGNATURES_3D is (None on
+# a library without the symbol).
+SIGNATURES_DEPTHWISE: dict[str, tuple[object, list[object]]] = {
+    "ffq_depthwise_conv2d_w8a8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _d, _i] + [_i64] * 13 + [_vp]),
+}
+
 
 class FFQLibrary:
     """A loaded implementation of the ``ffq_*`` ABI."""
@@ -318,7 +324,7 @@ class FFQLibrary:
             raise ImportError(f"{self.path} does not export {missing[0]}")
         for name in missing:
             setattr(self, name, None)
-        for name, (restype, argtypes) in SIGNATURES_3D.items():
+        for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

@@ -13,7 +13,8 @@ else, so the reference chain (the fallbacks in :mod:`fastforward_amd.nn.function
 * bias: none, a plain tensor of the data dtype, or static-affine codes that dequantize to it;
 * no operand or parameter that needs a gradient while grad mode is on (the launch has no autograd formula).
 
-Conv1d runs as a conv2d with H = KH = 1. The output quantizer runs inside the launch under the int8 GEMM's rules
+``groups == C`` (depthwise) is not this module's: :mod:`fastforward_amd.fused_depthwise` registers a second kernel on both operators for
+it, and any other ``groups != 1`` stays on the fallback. Conv1d runs as a conv2d with H = KH = 1. The output quantizer runs inside the launch under the int8 GEMM's rules
 (``DispatcherKernels._requant``, int8 containers only), so range estimation still sees the real-valued output. Nothing here reads
 device memory on the host: the route is capturable in a ``torch.cuda.graph``.
 """

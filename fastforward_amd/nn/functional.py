@@ -24,7 +24,9 @@ parameters, without an output quantizer, is the reference's concatenation of the
 (_gen/fallback.py:346-449) with the reference's signatures, and ``fastforward_amd.fused_conv_transpose`` registers the phase-split
 int8 implicit GEMM. ``conv3d`` and ``avg_pool3d`` follow theirs (_gen/fallback.py:218-265, 579-612) with the reference's signatures;
 ``fastforward_amd.fused_conv3d`` registers the 3-D int8 implicit GEMM and ``fastforward_amd.fused_pool`` the one-pass 3-D average
-pool (entry points of include/ffq_3d.h). The other generated operators of the reference (``conv_transpose3d`` among them) are pure
+pool (entry points of include/ffq_3d.h). ``conv1d`` / ``conv2d`` with ``groups == C`` (depthwise, any channel multiplier, at most 1024
+taps) have a second kernel, the direct int8 stencil ``fastforward_amd.fused_depthwise`` registers (include/ffq_depthwise.h); every other
+``groups != 1`` runs the fallback. The other generated operators of the reference (``conv_transpose3d`` among them) are pure
 float fallbacks and are out of scope.
 """
 

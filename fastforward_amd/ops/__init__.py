@@ -48,7 +48,7 @@ from fastforward_amd.ops.producers import (  # noqa: F401
 from fastforward_amd.ops.modules import (  # noqa: F401
     embedding_quantize, layer_norm_quantize, pointwise_quantize,
 )
-from fastforward_amd.ops.conv import conv2d_w8a8, conv3d_w8a8, conv_transpose2d_w8a8  # noqa: F401
+from fastforward_amd.ops.conv import conv2d_w8a8, conv3d_w8a8, conv_transpose2d_w8a8, depthwise_conv2d_w8a8  # noqa: F401
 from fastforward_amd.ops.elementwise import activation_quantize, binary_quantize, softmax_quantize  # noqa: F401
 from fastforward_amd.ops.math import cumsum_quantize, rms_norm_quantize, sum_quantize, unary_quantize  # noqa: F401
 from fastforward_amd.ops.pool import pool2d_quantize, pool3d_quantize, upsample_nearest_quantize  # noqa: F401
@@ -91,6 +91,7 @@ __all__ = [
     "conv2d_w8a8",
     "conv_transpose2d_w8a8",
     "conv3d_w8a8",
+    "depthwise_conv2d_w8a8",
     "binary_quantize",
     "softmax_quantize",
     "activation_quantize",

@@ -1,7 +1,8 @@
 """The W8A8 convolution on int8 codes (csrc/ffq_conv.hip): what QuantizedConv2d / QuantizedConv1d run on the device instead of the
 reference's fallback.conv2d / fallback.conv1d (_gen/fallback.py:116-214: A2 of input and weight, F.conv2d, the output quantizer),
 its transposed twin (csrc/ffq_conv_transpose.hip; fallback.conv_transpose1d / conv_transpose2d, _gen/fallback.py:346-449), and the
-3-D convolution (csrc/ffq_conv3d.hip; fallback.conv3d, _gen/fallback.py:218-265; include/ffq_3d.h)."""
+3-D convolution (csrc/ffq_conv3d.hip; fallback.conv3d, _gen/fallback.py:218-265; include/ffq_3d.h), and the depthwise convolution
+(groups == C: csrc/ffq_depthwise.hip, a direct stencil; include/ffq_depthwise.h)."""
 
 from __future__ import annotations
 
@@ -94,6 +95,76 @@ def conv2d_w8a8(
             _ptr(xc), int(nhwc), _ptr(wc), _ptr(xs), _ptr(xo), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
             _ptr(bias_c), _tag(bias_c.dtype) if bias_c is not None else 0, _ptr(out), _tag(out.dtype), _ptr(os_), _ptr(oo),
             float(out_num_bits), y_dt, B, C, H, W, OC, KH, KW, sh, sw, ph, pw, dh, dw, _ptr(ws), nbytes, stream,
+        )
+    )
+    return out
+
+
+def depthwise_conv2d_w8a8(
+    x_codes: torch.Tensor,
+    w_codes: torch.Tensor,
+    x_scale: torch.Tensor,
+    x_offset: torch.Tensor | None,
+    w_scale: torch.Tensor,
+    w_offset: torch.Tensor | None,
+    bias: torch.Tensor | None = None,
+    stride: int | Sequence[int] = 1,
+    padding: int | Sequence[int] = 0,
+    dilation: int | Sequence[int] = 1,
+    out_dtype: torch.dtype = torch.bfloat16,
+    out_scale: torch.Tensor | None = None,
+    out_offset: torch.Tensor | None = None,
+    out_num_bits: float = 8.0,
+    requant_from: torch.dtype | None = None,
+) -> torch.Tensor:
+    """``F.conv2d(groups=C)`` on int8 codes: `x_codes` [B, C, H, W], `w_codes` [C * M, 1, KH, KW] (``torch.nn.Conv2d(groups=C)``'s
+    layout, channel multiplier M >= 1, KH * KW <= 1024); parameters, bias, `padding` and the output quantizer as in
+    :func:`conv2d_w8a8`. Returns the contiguous NCHW [B, C * M, OH, OW] result: channel n is bit for bit :func:`conv2d_w8a8` on
+    the one-channel slice ``x_codes[:, n // M]``, ``w_codes[n]`` (include/ffq_depthwise.h, csrc/ffq_depthwise.hip: one launch, no
+    workspace). The kernel reads NCHW: an input in another layout (``channels_last``, a view) is copied to it first, so it gives the
+    bits of its contiguous copy. Raises ``BackendError`` ("not covered") on a library without the entry point."""
+    op = "depthwise_conv2d_w8a8"
+    if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
+        raise TypeError(f"{op} expects int8 codes")
+    if x_codes.dim() != 4 or w_codes.dim() != 4:
+        raise RuntimeError(f"{op}: input [B, C, H, W] and weight [C * M, 1, KH, KW], got {tuple(x_codes.shape)} and {tuple(w_codes.shape)}")
+    B, C, H, W = x_codes.shape
+    OC, Cw, KH, KW = w_codes.shape
+    if Cw != 1 or (C == 0 and OC != 0) or (C != 0 and OC % C != 0):
+        raise RuntimeError(f"{op}: the weight is [C * M, 1, KH, KW] for an input of {C} channels, got {tuple(w_codes.shape)}")
+    M = OC // C if C else 1
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride, "stride", op), _pair(padding, "padding", op), _pair(dilation, "dilation", op)
+    xc = _dense(x_codes.detach())
+    wc = _dense(w_codes.detach())
+
+    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
+        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
+
+    xs, xo, ws_, wo, os_, oo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(out_scale), f32(out_offset)
+    if xs.numel() != 1 or (xo is not None and xo.numel() != 1):
+        raise RuntimeError(f"{op}: the input has one parameter pair (per-tensor)")
+    if ws_.numel() not in (1, OC) or (wo is not None and wo.numel() != ws_.numel()):
+        raise RuntimeError(f"{op}: the weight has 1 or {OC} parameter pairs, got {ws_.numel()}")
+    if os_ is not None and (os_.numel() != 1 or (oo is not None and oo.numel() != 1)):
+        raise RuntimeError(f"{op}: the output quantizer is per tensor")
+    if os_ is None and out_dtype not in _REAL:
+        raise RuntimeError(f"{op}: a real-valued output is f32, bf16 or f16, got {out_dtype}")
+    bias_c = None if bias is None else bias.detach().reshape(-1).contiguous()
+    if bias_c is not None and (bias_c.numel() != OC or bias_c.dtype not in _REAL):
+        raise RuntimeError(f"{op}: the bias is [{OC}] of f32, bf16 or f16")
+    lib, stream = _base._prepare(xc, wc, xs, xo, ws_, wo, bias_c, os_, oo)
+    entry = getattr(lib, "ffq_depthwise_conv2d_w8a8", None)
+    if entry is None:
+        raise BackendError("not covered: the loaded library does not export ffq_depthwise_conv2d_w8a8 (include/ffq_depthwise.h; a host library has no convolution kernel)")
+    OH = (H + 2 * ph - dh * (KH - 1) - 1) // sh + 1
+    OW = (W + 2 * pw - dw * (KW - 1) - 1) // sw + 1
+    out = torch.empty((B, OC, max(OH, 0), max(OW, 0)), dtype=torch.int8 if os_ is not None else out_dtype, device=xc.device)
+    y_dt = _tag(requant_from or torch.bfloat16) if os_ is not None else 0
+    lib.check(
+        entry(
+            _ptr(xc), _ptr(wc), _ptr(xs), _ptr(xo), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
+            _ptr(bias_c), _tag(bias_c.dtype) if bias_c is not None else 0, _ptr(out), _tag(out.dtype), _ptr(os_), _ptr(oo),
+            float(out_num_bits), y_dt, B, C, M, H, W, KH, KW, sh, sw, ph, pw, dh, dw, stream,
         )
     )
     return out
