@@ -297,6 +297,13 @@ SIGNATURES_DEPTHWISE: dict[str, tuple[object, list[object]]] = {
     "ffq_depthwise_conv2d_w8a8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _d, _i] + [_i64] * 13 + [_vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ffq_index.h one to one: the fourth header's table (the quantized index_add and permute),
+# bound as SIGNATURES_3D is (None on a library without the symbol).
+SIGNATURES_INDEX: dict[str, tuple[object, list[object]]] = {
+    "ffq_index_add_quantize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _vp, _d, _i, _i64, _i64, _i64, _vp, _fp, _vp]),
+    "ffq_permute_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _fp, _vp]),
+}
+
 
 class FFQLibrary:
     """A loaded implementation of the ``ffq_*`` ABI."""
@@ -324,7 +331,7 @@ class FFQLibrary:
             raise ImportError(f"{self.path} does not export {missing[0]}")
         for name in missing:
             setattr(self, name, None)
-        for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items()):
+        for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

@@ -20,47 +20,6 @@ namespace concat {
 
 constexpr int kPerLane = 4;  // units (groups or elements) per lane, kBlock apart: independent loads in flight
 
-// ---- shared: one value and its codes ----------------------------------------------------------------------------------------
-
-// The codes of ONE value of the data dtype (store_one's arithmetic without its store: a plain element keeps its own bits).
-__device__ __forceinline__ void fan_one(const FanOut& f, const FanParams& p, float z, size_t at) {
-  const float one[1] = {z};
-  const int ilo = (int)f.lo, ihi = (int)f.hi;
-#pragma unroll
-  for (int j = 0; j < FFQ_MAX_FANOUT; ++j) {
-    if (j >= f.n) break;
-    const Divider<1> d(p.s[j]);
-    float r[1];
-    quantize_chunk_with<1, 1>(d, one, p.o[j], r);
-    int v = (int)r[0];  // v_cvt_i32_f32 saturates and maps NaN to 0, as finalize_chunk
-    v = v < ilo ? ilo : (v > ihi ? ihi : v);
-    f.codes[j][at] = (int8_t)v;
-  }
-}
-
-// Element `i` of an operand as a value of T: its own bits when plain, A2 of the code otherwise.
-template <typename T, typename TIn, bool DEQ>
-__device__ __forceinline__ T element(const TIn* x, size_t i, float s, float o) {
-  if constexpr (DEQ) return from_f32<T>(a2_value<T>(to_f32(x[i]), s, o));
-  else return reinterpret_cast<const T*>(x)[i];
-}
-
-template <typename T>
-__device__ __forceinline__ void put_one(T* out, const FanOut& f, const FanParams& p, T v, size_t at) {
-  if (out) out[at] = v;
-  if (f.n) fan_one(f, p, to_f32(v), at);
-}
-
-template <typename T>
-__device__ __forceinline__ void put_group(T* out, const FanOut& f, const FanParams& p, const Chunk<T, kE>& h, size_t at) {
-  if (out) h.store(out + at);
-  if (f.n) {
-    float v[kE];
-    unpack(h, v);
-    fan_store(f, p, v, at);
-  }
-}
-
 // 8 consecutive elements from an address that is only element-aligned (a pad shifts rows by any amount).
 template <typename TIn>
 __device__ __forceinline__ Chunk<TIn, kE> load_unaligned(const TIn* p) {

@@ -1,6 +1,6 @@
 // ffq_onepass.h — what the one-pass quantized families share: ffq_modules.hip (LayerNorm / Embedding / ReLU / SiLU),
 // ffq_elementwise.hip (add / sub / mul / div, softmax, sigmoid, GELU), ffq_math.hip (rms_norm, pow, exp, sin, cos, sum, cumsum),
-// ffq_pool.hip (the pools, nearest interpolate) and ffq_concat.hip (cat, pad).
+// ffq_pool.hip (the pools, nearest interpolate), ffq_concat.hip (cat, pad) and ffq_index.hip (index_add, permute).
 //
 // The arithmetic contract of every kernel in those files:
 //   A2  an operand given as codes is dequantized in registers as ffq_dequantize.hip does: (q + round(o)) * s in fp32 (two roundings,
@@ -140,6 +140,47 @@ __device__ __forceinline__ void store_one(T* out, const FanOut& f, const FanPara
     int v = (int)r[0];  // v_cvt_i32_f32 saturates and maps NaN to 0, as finalize_chunk
     v = v < ilo ? ilo : (v > ihi ? ihi : v);
     f.codes[j][at] = (int8_t)v;
+  }
+}
+
+// ---- device: one value or one group that only moves (ffq_concat.hip, ffq_index.hip) --------------------------------------------
+
+// The codes of ONE value of the data dtype (store_one's arithmetic without its store: a plain element keeps its own bits).
+__device__ __forceinline__ void fan_one(const FanOut& f, const FanParams& p, float z, size_t at) {
+  const float one[1] = {z};
+  const int ilo = (int)f.lo, ihi = (int)f.hi;
+#pragma unroll
+  for (int j = 0; j < FFQ_MAX_FANOUT; ++j) {
+    if (j >= f.n) break;
+    const Divider<1> d(p.s[j]);
+    float r[1];
+    quantize_chunk_with<1, 1>(d, one, p.o[j], r);
+    int v = (int)r[0];  // v_cvt_i32_f32 saturates and maps NaN to 0, as finalize_chunk
+    v = v < ilo ? ilo : (v > ihi ? ihi : v);
+    f.codes[j][at] = (int8_t)v;
+  }
+}
+
+// Element `i` of an operand as a value of T: its own bits when plain, A2 of the code otherwise.
+template <typename T, typename TIn, bool DEQ>
+__device__ __forceinline__ T element(const TIn* x, size_t i, float s, float o) {
+  if constexpr (DEQ) return from_f32<T>(a2_value<T>(to_f32(x[i]), s, o));
+  else return reinterpret_cast<const T*>(x)[i];
+}
+
+template <typename T>
+__device__ __forceinline__ void put_one(T* out, const FanOut& f, const FanParams& p, T v, size_t at) {
+  if (out) out[at] = v;
+  if (f.n) fan_one(f, p, to_f32(v), at);
+}
+
+template <typename T>
+__device__ __forceinline__ void put_group(T* out, const FanOut& f, const FanParams& p, const Chunk<T, kE>& h, size_t at) {
+  if (out) h.store(out + at);
+  if (f.n) {
+    float v[kE];
+    unpack(h, v);
+    fan_store(f, p, v, at);
   }
 }
 

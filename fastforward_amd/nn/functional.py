@@ -26,7 +26,10 @@ int8 implicit GEMM. ``conv3d`` and ``avg_pool3d`` follow theirs (_gen/fallback.p
 ``fastforward_amd.fused_conv3d`` registers the 3-D int8 implicit GEMM and ``fastforward_amd.fused_pool`` the one-pass 3-D average
 pool (entry points of include/ffq_3d.h). ``conv1d`` / ``conv2d`` with ``groups == C`` (depthwise, any channel multiplier, at most 1024
 taps) have a second kernel, the direct int8 stencil ``fastforward_amd.fused_depthwise`` registers (include/ffq_depthwise.h); every other
-``groups != 1`` runs the fallback. The other generated operators of the reference (``conv_transpose3d`` among them) are pure
+``groups != 1`` runs the fallback. ``index_add`` and ``permute`` follow theirs (_gen/fallback.py:1427-1449, 1483-1516) with the
+reference's signatures, and ``fastforward_amd.fused_index`` registers their one-pass kernels (include/ffq_index.h): an
+``index_add`` that sums the addends of a row in fp32 in index order, and a ``permute`` under an output quantizer that writes the
+permuted codes directly. The other generated operators of the reference (``conv_transpose3d`` among them) are pure
 float fallbacks and are out of scope.
 """
 
@@ -46,7 +49,7 @@ if TYPE_CHECKING:
 
 __all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "conv3d", "conv_transpose1d", "conv_transpose2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
            "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
-           "cumsum", "avg_pool1d", "avg_pool2d", "avg_pool3d", "max_pool2d", "interpolate", "cat", "pad"]
+           "cumsum", "avg_pool1d", "avg_pool2d", "avg_pool3d", "max_pool2d", "interpolate", "cat", "pad", "index_add", "permute"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -489,6 +492,34 @@ def pad(input: torch.Tensor, pad: Sequence[int], mode: str = "...", value: float
     # (the default mode is the reference's, an artefact of its generator: F.pad refuses it)
     kwargs = dict(input=input, pad=pad, mode=mode, value=value, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("pad", **kwargs) or _fallback_pad)(**kwargs)
+
+
+# ---- index_add, permute (reference _gen/operators.py: dispatch(op, **kwargs) or the generated fallback) ------------------------------
+def _fallback_index_add(input: torch.Tensor, dim: int, index: torch.Tensor, source: torch.Tensor, alpha: float = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize input / source, torch.index_add, optional output quantizer (reference fallback.py:1483-1516)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    source = _dequantized("source", source, strict_quantization)
+    output = torch.index_add(input=input, dim=dim, index=index, source=source, alpha=alpha)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def _fallback_permute(input: torch.Tensor, dims: tuple[int, ...], *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, torch.permute, optional output quantizer (reference fallback.py:1427-1449)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.permute(input=input, dims=dims)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def index_add(input: torch.Tensor, dim: int, index: torch.Tensor, source: torch.Tensor, alpha: float = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, dim=dim, index=index, source=source, alpha=alpha, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("index_add", **kwargs) or _fallback_index_add)(**kwargs)
+
+
+def permute(input: torch.Tensor, dims: tuple[int, ...], *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, dims=dims, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("permute", **kwargs) or _fallback_permute)(**kwargs)
 
 
 from fastforward_amd.nn.sdpa import scaled_dot_product_attention  # noqa: E402  (nn/sdpa.py calls back into this module)

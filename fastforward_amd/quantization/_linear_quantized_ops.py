@@ -4,7 +4,10 @@ Subset of src/fastforward/quantization/_linear_quantized_ops.py needed on the Ll
 (SURVEY §2): ``contiguous`` (:94-96) for any quantized tensor and ``view`` / ``view_as`` /
 ``reshape`` / ``transpose`` for per-tensor affine tensors (:99-123). They only move metadata.
 So does ``mul`` by a Python number (:126-171): the same codes with ``scale * other``. ``cat`` of per-tensor affine tensors that
-share one scale and one offset, without an output quantizer, concatenates the codes (:174-224).
+share one scale and one offset, without an output quantizer, concatenates the codes (:174-224). ``expand``, ``unsqueeze``,
+``take_along_dim`` and ``topk`` of per-tensor affine tensors act on the codes too (:232-280): the order of the codes is the order of
+the values (a positive scale), so the top-k codes are the top-k values and their indices. Per-channel and per-tile tensors keep the
+dequantizing route for them, and ``__getitem__`` stays unimplemented.
 """
 
 from __future__ import annotations
@@ -162,3 +165,26 @@ def cat(tensors: Sequence[QuantizedTensor], dim: int = 0, *_args: Any, **_kwargs
     """``torch.cat`` of the codes, under the first element's context. Serves ``ff.nn.functional.cat`` and ``torch.cat``."""
     output = torch.cat([t.raw_data for t in tensors], dim=dim)
     return tensors[0].quantization_context.attach(output)
+
+
+# ---- expand / unsqueeze / take_along_dim / topk of per-tensor affine tensors: the torch op on the codes (reference :232-280) --------
+@register("expand", affine_per_tensor_predicate)
+def expand(input: QuantizedTensor, *args: Any) -> QuantizedTensor:
+    return apply_and_reattach(lambda x: x.expand(*args), input)
+
+
+@register("unsqueeze", affine_per_tensor_predicate)
+def unsqueeze(input: QuantizedTensor, dim: int) -> QuantizedTensor:
+    # (per tensor only: the reference's per-channel arm computes the new axes as ``ax + ax >= dim``, a bool per axis)
+    return apply_and_reattach(lambda x: x.unsqueeze(dim), input)
+
+
+@register("take_along_dim", affine_per_tensor_predicate)
+def take_along_dim(input: QuantizedTensor, indices: torch.Tensor, dim: int | None = None) -> QuantizedTensor:
+    return apply_and_reattach(lambda x: torch.take_along_dim(x, indices, dim=dim), input)
+
+
+@register("topk", affine_per_tensor_predicate)
+def topk(input: QuantizedTensor, k: int, dim: int = -1, largest: bool = True, sorted: bool = True) -> Any:
+    values, indices = torch.topk(input.raw_data, k, dim=dim, largest=largest, sorted=sorted)
+    return torch.return_types.topk((apply_and_reattach(lambda _: values, input), indices))
