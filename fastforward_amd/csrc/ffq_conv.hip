@@ -19,16 +19,14 @@
 //     POSITIONS on the B side: every 16-byte staging slot of a B row is one 16-channel run of one tap of the im2col matrix,
 //     gathered from the NHWC codes (zeros outside the image). The B row lands on lane & 31 of the accumulator, so one
 //     accumulator register over 32 lanes is 32 consecutive output positions of one channel: the epilogue stores NCHW directly.
+#include "ffq_conv_host.h"
 #include "ffq_conv_tile.h"
-
-#include <math.h>
 
 namespace ffq {
 namespace {
 
 constexpr int CBM = 128, CBN = 128, CBK = 64;
 constexpr int kConvTileBytes = CBM * CBK;
-constexpr int64_t kConvMaxReduction = 131071;  // C * KH * KW bound: |acc| <= 2^14 * (2^17 - 1) < 2^31 (at 2^17 taps of -128 x -128 the sum is 2^31 and wraps)
 
 struct ConvArgs {
   const int8_t* wq;       // [OC, Kp]: weight codes reordered to (kh, kw, c), Kp = KH * KW * Cp
@@ -268,42 +266,6 @@ __global__ __launch_bounds__(256) void conv_w8a8_kernel(ConvArgs a) {
   }
 }
 
-struct ConvGeometry {
-  int64_t OH, OW, Cp, taps, Kp, npos;
-  size_t x_bytes, w_bytes, sum_bytes;
-};
-
-size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// 0 with the geometry filled in, else the status of the first check that fails (no HIP call is made here)
-int conv_geometry(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph,
-                  int64_t pw, int64_t dh, int64_t dw, int x_nhwc, ConvGeometry* g) {
-  if (B < 0 || C < 0 || H < 0 || W < 0 || OC < 0 || KH < 0 || KW < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (C == 0 || KH == 0 || KW == 0) return fail(FFQ_ERR_EMPTY, "a convolution over an empty filter");
-  if (sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return fail(FFQ_ERR_ARG, "stride and dilation >= 1, padding >= 0");
-  const int64_t lim = (int64_t)1 << 24;
-  if (H > lim || W > lim || KH > lim || KW > lim || sh > lim || sw > lim || dh > lim || dw > lim || ph > lim || pw > lim)
-    return fail(FFQ_ERR_ARG, "extent, stride, padding or dilation above 2^24");
-  if (C * KH * KW > kConvMaxReduction)
-    return fail(FFQ_ERR_DTYPE, "C * KH * KW = %lld exceeds %lld (the int32 accumulator's bound)", (long long)(C * KH * KW), (long long)kConvMaxReduction);
-  if (x_nhwc && C % 16 != 0) return fail(FFQ_ERR_DTYPE, "channels-last input codes need C %% 16 == 0");
-  const int64_t eff_h = dh * (KH - 1) + 1, eff_w = dw * (KW - 1) + 1;
-  if (H + 2 * ph < eff_h || W + 2 * pw < eff_w) return fail(FFQ_ERR_ARG, "the dilated filter is larger than the padded input");
-  g->OH = (H + 2 * ph - eff_h) / sh + 1;
-  g->OW = (W + 2 * pw - eff_w) / sw + 1;
-  g->Cp = (C + 15) / 16 * 16;
-  g->taps = KH * KW;
-  g->Kp = g->taps * g->Cp;
-  g->npos = B * g->OH * g->OW;
-  if (g->npos >= ((int64_t)1 << 31) || B * H * W * g->Cp >= ((int64_t)1 << 40) || OC >= ((int64_t)1 << 31) ||
-      B * OC * g->OH * g->OW >= ((int64_t)1 << 40) || OC * g->taps * (g->Cp / 16) >= ((int64_t)1 << 40))
-    return fail(FFQ_ERR_ARG, "extent too large for one launch");
-  g->x_bytes = x_nhwc ? 0 : round256((size_t)(B * H * W * g->Cp));
-  g->w_bytes = round256((size_t)(OC * g->Kp));
-  g->sum_bytes = round256((size_t)(OC * g->taps + OC) * 4);
-  return FFQ_OK;
-}
-
 }  // namespace
 }  // namespace ffq
 
@@ -311,9 +273,8 @@ using namespace ffq;
 
 extern "C" size_t ffq_conv2d_w8a8_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW,
                                                   int x_nhwc) {
-  if (B < 0 || C <= 0 || H < 0 || W < 0 || OC < 0 || KH <= 0 || KW <= 0) return 0;
-  const int64_t Cp = (C + 15) / 16 * 16;
-  return (x_nhwc ? 0 : round256((size_t)(B * H * W * Cp))) + round256((size_t)(OC * KH * KW * Cp)) + round256((size_t)(OC * KH * KW + OC) * 4);
+  const int64_t in[2] = {H, W}, k[2] = {KH, KW};
+  return conv_workspace_query(B, C, OC, 2, in, k, x_nhwc, 1);
 }
 
 extern "C" int ffq_conv2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, const float* x_scale, const float* x_offset,
@@ -323,67 +284,41 @@ extern "C" int ffq_conv2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, c
                                int64_t pad_h, int64_t pad_w, int64_t dil_h, int64_t dil_w, void* workspace, size_t workspace_bytes,
                                void* stream) {
   ConvGeometry g;
-  int rc = conv_geometry(B, C, H, W, OC, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, x_nhwc, &g);
+  const int64_t in[2] = {H, W}, k[2] = {KH, KW}, st[2] = {stride_h, stride_w}, pd[2] = {pad_h, pad_w}, dl[2] = {dil_h, dil_w};
+  int rc = conv_geometry(2, B, C, OC, in, k, st, pd, dl, x_nhwc, &g);
   if (rc) return rc;
-  if (bias && !(bias_dt == FFQ_F32 || bias_dt == FFQ_BF16 || bias_dt == FFQ_F16)) return fail(FFQ_ERR_DTYPE, "bias must be f32, bf16 or f16");
   const bool requant = out_scale != nullptr;
-  if (requant) {
-    if (out_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "the re-quantized convolution writes int8 codes");
-    if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
-      return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, out_num_bits);
-    if (!(y_dt == FFQ_F32 || y_dt == FFQ_BF16 || y_dt == FFQ_F16))
-      return fail(FFQ_ERR_DTYPE, "the re-quantized convolution's real-valued dtype must be f32, bf16 or f16");
-  } else if (!(out_dt == FFQ_F32 || out_dt == FFQ_BF16 || out_dt == FFQ_F16)) {
-    return fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
-  }
+  rc = check_conv_output("convolution", bias, bias_dt, requant, out_dt, out_num_bits, y_dt);
+  if (rc) return rc;
   if (B == 0 || OC == 0) return FFQ_OK;
-  if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (x_nhwc && !aligned16(xq)) return fail(FFQ_ERR_ARG, "channels-last input codes must be 16-byte aligned");
-  const size_t need = g.x_bytes + g.w_bytes + g.sum_bytes;
-  if (!workspace || workspace_bytes < need || !aligned16(workspace))
-    return fail(FFQ_ERR_WORKSPACE, "w8a8 convolution needs %zu workspace bytes (16-byte aligned), got %zu", need, workspace_bytes);
+  rc = check_conv_buffers("convolution", xq, x_nhwc, wq, x_scale, w_scale, out, workspace, workspace_bytes, g.ws.total());
+  if (rc) return rc;
 
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint8_t* ws = static_cast<uint8_t*>(workspace);
-  int8_t* xn = x_nhwc ? const_cast<int8_t*>(xq) : reinterpret_cast<int8_t*>(ws);
-  int8_t* wn = reinterpret_cast<int8_t*>(ws + g.x_bytes);
-  int32_t* tapsum = reinterpret_cast<int32_t*>(ws + g.x_bytes + g.w_bytes);
-  hipError_t e = hipMemsetAsync(tapsum, 0, (size_t)(OC * g.taps + OC) * 4, s);
-  if (e != hipSuccess) return fail(FFQ_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
+  ConvBuffers buf;
+  rc = carve_conv_workspace(xq, x_nhwc, workspace, g.ws, OC * g.taps + OC, s, &buf);
+  if (rc) return rc;
   const int groups = (int)(g.Cp / 16);
-  const int64_t n_in = x_nhwc ? 0 : B * H * W * groups;
+  const int64_t n_in = x_nhwc ? 0 : g.voxels * groups;
   const int64_t n_w = OC * g.taps * groups;
   const int64_t threads = n_in + n_w;
-  conv_layout_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(xq, xn, n_in, (int)C, H * W, groups, wq, wn, n_w, (int)g.taps,
-                                                                        (int)OC, tapsum);
+  conv_layout_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(xq, buf.xn, n_in, (int)C, H * W, groups, wq, buf.wn, n_w,
+                                                                        (int)g.taps, (int)OC, buf.tapsum);
   rc = check_launch("conv_layout_kernel");
   if (rc) return rc;
 
   ConvArgs a;
-  a.wq = wn; a.xq = xn; a.tapsum = tapsum;
-  a.x_scale = x_scale; a.x_offset = x_offset;
-  a.w_scale = w_scale; a.w_offset = w_offset; a.w_per_row = w_per_channel ? 1 : 0;
-  a.bias = bias; a.bias_dt = bias_dt;
-  a.out = out;
-  a.out_scale = out_scale; a.out_offset = out_offset;
-  const double lo = -pow(2.0, out_num_bits - 1.0);
-  a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
-  a.y_dt = y_dt;
+  a.wq = buf.wn; a.xq = buf.xn; a.tapsum = buf.tapsum;
+  fill_conv_operands(a, x_scale, x_offset, w_scale, w_offset, w_per_channel, bias, bias_dt, out, out_scale, out_offset, out_num_bits, y_dt);
   a.OC = (int)OC; a.C = (int)C; a.Cp = (int)g.Cp; a.H = (int)H; a.W = (int)W; a.KH = (int)KH; a.KW = (int)KW;
-  a.OH = (int)g.OH; a.OW = (int)g.OW;
+  a.OH = (int)g.o[0]; a.OW = (int)g.o[1];
   a.sh = (int)stride_h; a.sw = (int)stride_w; a.ph = (int)pad_h; a.pw = (int)pad_w; a.dh = (int)dil_h; a.dw = (int)dil_w;
-  a.Kp = (int)g.Kp; a.npos = (int)g.npos; a.ohw = (int)(g.OH * g.OW);
+  a.Kp = (int)g.Kp; a.npos = (int)g.npos; a.ohw = (int)(g.o[0] * g.o[1]);
   a.tiles_m = (int)((OC + CBM - 1) / CBM);
   a.tiles_n = (int)((g.npos + CBN - 1) / CBN);
   const unsigned grid = (unsigned)((int64_t)a.tiles_m * a.tiles_n);
-  if (requant) {
-    conv_w8a8_kernel<int8_t, true><<<grid, 256, 0, s>>>(a);
-  } else {
-    switch (out_dt) {
-      case FFQ_BF16: conv_w8a8_kernel<bf16_t, false><<<grid, 256, 0, s>>>(a); break;
-      case FFQ_F16: conv_w8a8_kernel<f16_t, false><<<grid, 256, 0, s>>>(a); break;
-      default: conv_w8a8_kernel<float, false><<<grid, 256, 0, s>>>(a); break;
-    }
-  }
+  dispatch_conv_output(requant, out_dt, [&](auto t, auto q) {
+    conv_w8a8_kernel<typename decltype(t)::type, decltype(q)::value><<<grid, 256, 0, s>>>(a);
+  });
   return check_launch("conv_w8a8_kernel");
 }

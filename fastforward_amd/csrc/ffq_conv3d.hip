@@ -18,18 +18,16 @@
 //     v_mfma_i32_32x32x32_i8, XCD-aware tile order) with K = (kd, kh, kw, c): every 16-byte staging slot of a B row is one
 //     16-channel run of one tap, gathered from [B, D, H, W, Cp] (zeros outside the volume). One accumulator register over 32 lanes
 //     is 32 consecutive output positions of one channel: the epilogue stores NCDHW directly.
+#include "ffq_conv_host.h"
 #include "ffq_conv_tile.h"
 
 #include "../../include/ffq_3d.h"
-
-#include <math.h>
 
 namespace ffq {
 namespace {
 
 constexpr int CBM = 128, CBN = 128, CBK = 64;
 constexpr int kConvTileBytes = CBM * CBK;
-constexpr int64_t kConvMaxReduction = 131071;  // C * KD * KH * KW bound: |acc| <= 2^14 * (2^17 - 1) < 2^31 (docs/numerics.md)
 
 struct Conv3dArgs {
   const int8_t* wq;       // [OC, Kp]: weight codes reordered to (kd, kh, kw, c), Kp = KD * KH * KW * Cp
@@ -272,58 +270,6 @@ __global__ __launch_bounds__(256) void conv3d_w8a8_kernel(Conv3dArgs a) {
   }
 }
 
-struct Conv3dGeometry {
-  int64_t OD, OH, OW, Cp, taps, Kp, npos, voxels;  // voxels = B * D * H * W
-  size_t x_bytes, w_bytes, sum_bytes;
-};
-
-size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// a * b, or `limit` when the product reaches it (a, b >= 0; limit <= 2^62): extents of 2^24 per axis overflow a plain product
-int64_t mul_capped(int64_t a, int64_t b, int64_t limit) {
-  if (a == 0 || b == 0) return 0;
-  return a >= (limit + b - 1) / b ? limit : a * b;
-}
-
-constexpr int64_t kBig = (int64_t)1 << 40;  // elements one launch addresses
-
-// 0 with the geometry filled in, else the status of the first check that fails (no HIP call is made here)
-int conv3d_geometry(int64_t B, int64_t C, int64_t D, int64_t H, int64_t W, int64_t OC, int64_t KD, int64_t KH, int64_t KW, const int64_t* s,
-                    const int64_t* p, const int64_t* d, int x_ndhwc, Conv3dGeometry* g) {
-  if (B < 0 || C < 0 || D < 0 || H < 0 || W < 0 || OC < 0 || KD < 0 || KH < 0 || KW < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (C == 0 || KD == 0 || KH == 0 || KW == 0) return fail(FFQ_ERR_EMPTY, "a convolution over an empty filter");
-  const int64_t lim = (int64_t)1 << 24;
-  const int64_t in[3] = {D, H, W}, k[3] = {KD, KH, KW};
-  for (int i = 0; i < 3; ++i)
-    if (s[i] < 1 || d[i] < 1 || p[i] < 0) return fail(FFQ_ERR_ARG, "stride and dilation >= 1, padding >= 0");
-  for (int i = 0; i < 3; ++i)
-    if (in[i] > lim || k[i] > lim || s[i] > lim || d[i] > lim || p[i] > lim)
-      return fail(FFQ_ERR_ARG, "extent, stride, padding or dilation above 2^24");
-  const int64_t reduction = mul_capped(mul_capped(mul_capped(C, KD, kBig), KH, kBig), KW, kBig);
-  if (reduction > kConvMaxReduction)
-    return fail(FFQ_ERR_DTYPE, "C * KD * KH * KW = %lld exceeds %lld (the int32 accumulator's bound)", (long long)reduction, (long long)kConvMaxReduction);
-  if (x_ndhwc && C % 16 != 0) return fail(FFQ_ERR_DTYPE, "channels-last input codes need C %% 16 == 0");
-  int64_t o[3];
-  for (int i = 0; i < 3; ++i) {
-    const int64_t eff = d[i] * (k[i] - 1) + 1;
-    if (in[i] + 2 * p[i] < eff) return fail(FFQ_ERR_ARG, "the dilated filter is larger than the padded input");
-    o[i] = (in[i] + 2 * p[i] - eff) / s[i] + 1;
-  }
-  g->OD = o[0]; g->OH = o[1]; g->OW = o[2];
-  g->Cp = (C + 15) / 16 * 16;
-  g->taps = KD * KH * KW;
-  g->Kp = g->taps * g->Cp;
-  g->npos = mul_capped(mul_capped(mul_capped(B, o[0], kBig), o[1], kBig), o[2], kBig);
-  g->voxels = mul_capped(mul_capped(mul_capped(B, D, kBig), H, kBig), W, kBig);
-  if (g->npos >= ((int64_t)1 << 31) || mul_capped(g->voxels, g->Cp, kBig) >= kBig || OC >= ((int64_t)1 << 31) ||
-      mul_capped(g->npos, OC, kBig) >= kBig || mul_capped(OC, g->taps * (g->Cp / 16), kBig) >= kBig)
-    return fail(FFQ_ERR_ARG, "extent too large for one launch");
-  g->x_bytes = x_ndhwc ? 0 : round256((size_t)(g->voxels * g->Cp));
-  g->w_bytes = round256((size_t)(OC * g->Kp));
-  g->sum_bytes = round256((size_t)(OC * g->taps + OC) * 4);
-  return FFQ_OK;
-}
-
 }  // namespace
 }  // namespace ffq
 
@@ -331,13 +277,8 @@ using namespace ffq;
 
 extern "C" size_t ffq_conv3d_w8a8_workspace_bytes(int64_t B, int64_t C, int64_t D, int64_t H, int64_t W, int64_t OC, int64_t KD, int64_t KH,
                                                   int64_t KW, int x_ndhwc) {
-  if (B < 0 || C <= 0 || D < 0 || H < 0 || W < 0 || OC < 0 || KD <= 0 || KH <= 0 || KW <= 0) return 0;
-  const int64_t Cp = mul_capped((C + 15) / 16, 16, kBig);
-  const int64_t taps = mul_capped(mul_capped(KD, KH, kBig), KW, kBig);
-  const int64_t x = mul_capped(mul_capped(mul_capped(mul_capped(B, D, kBig), H, kBig), W, kBig), Cp, kBig);
-  const int64_t w = mul_capped(mul_capped(OC, taps, kBig), Cp, kBig);
-  if (x >= kBig || w >= kBig) return 0;  // no launch takes it (ffq_conv3d_w8a8 answers FFQ_ERR_ARG or FFQ_ERR_DTYPE)
-  return (x_ndhwc ? 0 : round256((size_t)x)) + round256((size_t)w) + round256((size_t)(OC * taps + OC) * 4);
+  const int64_t in[3] = {D, H, W}, k[3] = {KD, KH, KW};
+  return conv_workspace_query(B, C, OC, 3, in, k, x_ndhwc, 1);
 }
 
 extern "C" int ffq_conv3d_w8a8(const int8_t* xq, int x_ndhwc, const int8_t* wq, const float* x_scale, const float* x_offset,
@@ -346,71 +287,45 @@ extern "C" int ffq_conv3d_w8a8(const int8_t* xq, int x_ndhwc, const int8_t* wq, 
                                int64_t C, int64_t D, int64_t H, int64_t W, int64_t OC, int64_t KD, int64_t KH, int64_t KW, int64_t stride_d,
                                int64_t stride_h, int64_t stride_w, int64_t pad_d, int64_t pad_h, int64_t pad_w, int64_t dil_d, int64_t dil_h,
                                int64_t dil_w, void* workspace, size_t workspace_bytes, void* stream) {
-  Conv3dGeometry g;
+  ConvGeometry g;
+  const int64_t in[3] = {D, H, W}, k[3] = {KD, KH, KW};
   const int64_t st[3] = {stride_d, stride_h, stride_w}, pd[3] = {pad_d, pad_h, pad_w}, dl[3] = {dil_d, dil_h, dil_w};
-  int rc = conv3d_geometry(B, C, D, H, W, OC, KD, KH, KW, st, pd, dl, x_ndhwc, &g);
+  int rc = conv_geometry(3, B, C, OC, in, k, st, pd, dl, x_ndhwc, &g);
   if (rc) return rc;
-  if (bias && !(bias_dt == FFQ_F32 || bias_dt == FFQ_BF16 || bias_dt == FFQ_F16)) return fail(FFQ_ERR_DTYPE, "bias must be f32, bf16 or f16");
   const bool requant = out_scale != nullptr;
-  if (requant) {
-    if (out_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "the re-quantized convolution writes int8 codes");
-    if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
-      return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, out_num_bits);
-    if (!(y_dt == FFQ_F32 || y_dt == FFQ_BF16 || y_dt == FFQ_F16))
-      return fail(FFQ_ERR_DTYPE, "the re-quantized convolution's real-valued dtype must be f32, bf16 or f16");
-  } else if (!(out_dt == FFQ_F32 || out_dt == FFQ_BF16 || out_dt == FFQ_F16)) {
-    return fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
-  }
+  rc = check_conv_output("convolution", bias, bias_dt, requant, out_dt, out_num_bits, y_dt);
+  if (rc) return rc;
   if (B == 0 || OC == 0) return FFQ_OK;
-  if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (x_ndhwc && !aligned16(xq)) return fail(FFQ_ERR_ARG, "channels-last input codes must be 16-byte aligned");
-  const size_t need = g.x_bytes + g.w_bytes + g.sum_bytes;
-  if (!workspace || workspace_bytes < need || !aligned16(workspace))
-    return fail(FFQ_ERR_WORKSPACE, "w8a8 3-D convolution needs %zu workspace bytes (16-byte aligned), got %zu", need, workspace_bytes);
+  rc = check_conv_buffers("3-D convolution", xq, x_ndhwc, wq, x_scale, w_scale, out, workspace, workspace_bytes, g.ws.total());
+  if (rc) return rc;
 
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint8_t* ws = static_cast<uint8_t*>(workspace);
-  int8_t* xn = x_ndhwc ? const_cast<int8_t*>(xq) : reinterpret_cast<int8_t*>(ws);
-  int8_t* wn = reinterpret_cast<int8_t*>(ws + g.x_bytes);
-  int32_t* tapsum = reinterpret_cast<int32_t*>(ws + g.x_bytes + g.w_bytes);
-  hipError_t e = hipMemsetAsync(tapsum, 0, (size_t)(OC * g.taps + OC) * 4, s);
-  if (e != hipSuccess) return fail(FFQ_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
+  ConvBuffers buf;
+  rc = carve_conv_workspace(xq, x_ndhwc, workspace, g.ws, OC * g.taps + OC, s, &buf);
+  if (rc) return rc;
   const int groups = (int)(g.Cp / 16);
   const int64_t n_in = x_ndhwc ? 0 : g.voxels * groups;
   const int64_t n_w = OC * g.taps * groups;
   const int64_t threads = n_in + n_w;
-  conv3d_layout_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(xq, xn, n_in, (int)C, D * H * W, groups, wq, wn, n_w, (int)g.taps,
-                                                                          (int)OC, tapsum);
+  conv3d_layout_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(xq, buf.xn, n_in, (int)C, D * H * W, groups, wq, buf.wn, n_w,
+                                                                          (int)g.taps, (int)OC, buf.tapsum);
   rc = check_launch("conv3d_layout_kernel");
   if (rc) return rc;
 
   Conv3dArgs a;
-  a.wq = wn; a.xq = xn; a.tapsum = tapsum;
-  a.x_scale = x_scale; a.x_offset = x_offset;
-  a.w_scale = w_scale; a.w_offset = w_offset; a.w_per_row = w_per_channel ? 1 : 0;
-  a.bias = bias; a.bias_dt = bias_dt;
-  a.out = out;
-  a.out_scale = out_scale; a.out_offset = out_offset;
-  const double lo = -pow(2.0, out_num_bits - 1.0);
-  a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
-  a.y_dt = y_dt;
+  a.wq = buf.wn; a.xq = buf.xn; a.tapsum = buf.tapsum;
+  fill_conv_operands(a, x_scale, x_offset, w_scale, w_offset, w_per_channel, bias, bias_dt, out, out_scale, out_offset, out_num_bits, y_dt);
   a.OC = (int)OC; a.C = (int)C; a.Cp = (int)g.Cp; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.KD = (int)KD; a.KH = (int)KH; a.KW = (int)KW;
-  a.OH = (int)g.OH; a.OW = (int)g.OW;
+  a.OH = (int)g.o[1]; a.OW = (int)g.o[2];
   a.sd = (int)stride_d; a.sh = (int)stride_h; a.sw = (int)stride_w;
   a.pd = (int)pad_d; a.ph = (int)pad_h; a.pw = (int)pad_w;
   a.dd = (int)dil_d; a.dh = (int)dil_h; a.dw = (int)dil_w;
-  a.Kp = (int)g.Kp; a.npos = (int)g.npos; a.ovol = (int)(g.OD * g.OH * g.OW); a.ohw = (int)(g.OH * g.OW);
+  a.Kp = (int)g.Kp; a.npos = (int)g.npos; a.ovol = (int)(g.o[0] * g.o[1] * g.o[2]); a.ohw = (int)(g.o[1] * g.o[2]);
   a.tiles_m = (int)((OC + CBM - 1) / CBM);
   a.tiles_n = (int)((g.npos + CBN - 1) / CBN);
   const unsigned grid = (unsigned)((int64_t)a.tiles_m * a.tiles_n);
-  if (requant) {
-    conv3d_w8a8_kernel<int8_t, true><<<grid, 256, 0, s>>>(a);
-  } else {
-    switch (out_dt) {
-      case FFQ_BF16: conv3d_w8a8_kernel<bf16_t, false><<<grid, 256, 0, s>>>(a); break;
-      case FFQ_F16: conv3d_w8a8_kernel<f16_t, false><<<grid, 256, 0, s>>>(a); break;
-      default: conv3d_w8a8_kernel<float, false><<<grid, 256, 0, s>>>(a); break;
-    }
-  }
+  dispatch_conv_output(requant, out_dt, [&](auto t, auto q) {
+    conv3d_w8a8_kernel<typename decltype(t)::type, decltype(q)::value><<<grid, 256, 0, s>>>(a);
+  });
   return check_launch("conv3d_w8a8_kernel");
 }

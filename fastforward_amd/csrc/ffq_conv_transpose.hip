@@ -25,9 +25,8 @@
 //     v_mfma_i32_32x32x32_i8, XCD-aware tile order), the weight on the A side, output positions on the B side. Every 128-position
 //     tile lies inside one phase (a host-built table gives each phase's tile prefix, K range and per-axis taps); its K loop runs
 //     over that phase's taps only. Stores go to NCHW at ow = rw + stride_w * j.
+#include "ffq_conv_host.h"
 #include "ffq_conv_tile.h"
-
-#include <math.h>
 
 namespace ffq {
 namespace {
@@ -35,7 +34,6 @@ namespace {
 constexpr int TBM = 128, TBN = 128, TBK = 64;
 constexpr int kTileBytes = TBM * TBK;
 constexpr int kMaxPhases = 64;                 // stride_h * stride_w: the size of the phase table
-constexpr int64_t kMaxReduction = 131071;      // C * KH * KW bound, as the forward convolution's
 
 // One residue of one axis: the taps k0, k0 + kstep, ... (n of them); tap a reads input index i + off0 - a * ostep.
 struct AxisPhase { int k0, n, off0, extent; };  // extent: the number of outputs o = r (mod stride) below the output size
@@ -342,10 +340,8 @@ __global__ __launch_bounds__(256) void convt_w8a8_kernel(ConvtArgs a, PhaseTable
 
 struct ConvtGeometry {
   int64_t OH, OW, Cp, taps, Kp, nph;
-  size_t x_bytes, w_bytes, sum_bytes;
+  ConvWorkspace ws;
 };
-
-size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int64_t gcd64(int64_t x, int64_t y) {
   while (y) { const int64_t t = x % y; x = y; y = t; }
@@ -370,37 +366,32 @@ void axis_phases(int64_t K, int64_t s, int64_t pad, int64_t d, int64_t O, AxisPh
 }
 
 // 0 with the geometry filled in, else the status of the first check that fails (no HIP call is made here)
-int convt_geometry(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph,
-                   int64_t pw, int64_t oph, int64_t opw, int64_t dh, int64_t dw, int x_nhwc, ConvtGeometry* g) {
-  if (B < 0 || C < 0 || H < 0 || W < 0 || OC < 0 || KH < 0 || KW < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (C == 0 || KH == 0 || KW == 0) return fail(FFQ_ERR_EMPTY, "a transposed convolution over an empty filter");
-  if (sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return fail(FFQ_ERR_ARG, "stride and dilation >= 1, padding >= 0");
-  const int64_t lim = (int64_t)1 << 24;
-  if (H > lim || W > lim || KH > lim || KW > lim || sh > lim || sw > lim || dh > lim || dw > lim || ph > lim || pw > lim)
-    return fail(FFQ_ERR_ARG, "extent, stride, padding or dilation above 2^24");
-  if (oph < 0 || opw < 0 || oph >= (sh > dh ? sh : dh) || opw >= (sw > dw ? sw : dw))
+int convt_geometry(int64_t B, int64_t C, int64_t OC, const int64_t* in, const int64_t* k, const int64_t* s, const int64_t* p, const int64_t* op,
+                   const int64_t* d, int x_nhwc, ConvtGeometry* g) {
+  int rc = check_conv_axes("transposed convolution", 2, B, C, OC, in, k, s, p, d);
+  if (rc) return rc;
+  if (op[0] < 0 || op[1] < 0 || op[0] >= (s[0] > d[0] ? s[0] : d[0]) || op[1] >= (s[1] > d[1] ? s[1] : d[1]))
     return fail(FFQ_ERR_ARG, "output padding must be >= 0 and smaller than either stride or dilation");
-  if (sh * sw > kMaxPhases)
-    return fail(FFQ_ERR_ARG, "stride_h * stride_w = %lld exceeds %d (the phase table)", (long long)(sh * sw), kMaxPhases);
-  if (C * KH * KW > kMaxReduction)
-    return fail(FFQ_ERR_DTYPE, "C * KH * KW = %lld exceeds %lld (the int32 accumulator's bound)", (long long)(C * KH * KW), (long long)kMaxReduction);
+  if (s[0] * s[1] > kMaxPhases)
+    return fail(FFQ_ERR_ARG, "stride_h * stride_w = %lld exceeds %d (the phase table)", (long long)(s[0] * s[1]), kMaxPhases);
+  rc = check_conv_reduction(C, 2, k);
+  if (rc) return rc;
   if (x_nhwc && C % 16 != 0) return fail(FFQ_ERR_DTYPE, "channels-last input codes need C %% 16 == 0");
-  if (H < 1 || W < 1) return fail(FFQ_ERR_ARG, "a transposed convolution of an empty image");
-  g->OH = (H - 1) * sh - 2 * ph + dh * (KH - 1) + oph + 1;
-  g->OW = (W - 1) * sw - 2 * pw + dw * (KW - 1) + opw + 1;
+  if (in[0] < 1 || in[1] < 1) return fail(FFQ_ERR_ARG, "a transposed convolution of an empty image");
+  g->OH = (in[0] - 1) * s[0] - 2 * p[0] + d[0] * (k[0] - 1) + op[0] + 1;
+  g->OW = (in[1] - 1) * s[1] - 2 * p[1] + d[1] * (k[1] - 1) + op[1] + 1;
   if (g->OH < 1 || g->OW < 1) return fail(FFQ_ERR_ARG, "the padding leaves no output (%lld x %lld)", (long long)g->OH, (long long)g->OW);
   g->Cp = (C + 15) / 16 * 16;
-  g->taps = KH * KW;
+  g->taps = k[0] * k[1];
   g->Kp = g->taps * g->Cp;
-  g->nph = sh * sw;
-  const int64_t npos = B * g->OH * g->OW;
+  g->nph = s[0] * s[1];
+  const int64_t o[2] = {g->OH, g->OW};
+  const int64_t npos = product_capped(B, 2, o), voxels = product_capped(B, 2, in);
   if (g->OH > ((int64_t)1 << 30) || g->OW > ((int64_t)1 << 30) || npos >= ((int64_t)1 << 31) - kMaxPhases * TBN ||
-      B * H * W * g->Cp >= ((int64_t)1 << 40) || OC >= ((int64_t)1 << 31) || B * OC * g->OH * g->OW >= ((int64_t)1 << 40) ||
-      OC * g->taps * (g->Cp / 16) >= ((int64_t)1 << 40))
+      mul_capped(voxels, g->Cp, kConvBig) >= kConvBig || OC >= ((int64_t)1 << 31) || mul_capped(npos, OC, kConvBig) >= kConvBig ||
+      mul_capped(OC, g->taps * (g->Cp / 16), kConvBig) >= kConvBig)
     return fail(FFQ_ERR_ARG, "extent too large for one launch");
-  g->x_bytes = x_nhwc ? 0 : round256((size_t)(B * H * W * g->Cp));
-  g->w_bytes = round256((size_t)(OC * g->Kp));
-  g->sum_bytes = round256((size_t)(OC * g->taps + OC * kMaxPhases) * 4);
+  g->ws = conv_workspace(voxels * g->Cp, x_nhwc, OC * g->Kp, OC * g->taps + OC * kMaxPhases);
   return FFQ_OK;
 }
 
@@ -411,10 +402,8 @@ using namespace ffq;
 
 extern "C" size_t ffq_conv_transpose2d_w8a8_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH,
                                                             int64_t KW, int x_nhwc) {
-  if (B < 0 || C <= 0 || H < 0 || W < 0 || OC < 0 || KH <= 0 || KW <= 0) return 0;
-  const int64_t Cp = (C + 15) / 16 * 16;
-  return (x_nhwc ? 0 : round256((size_t)(B * H * W * Cp))) + round256((size_t)(OC * KH * KW * Cp)) +
-         round256((size_t)(OC * KH * KW + OC * kMaxPhases) * 4);
+  const int64_t in[2] = {H, W}, k[2] = {KH, KW};
+  return conv_workspace_query(B, C, OC, 2, in, k, x_nhwc, kMaxPhases);
 }
 
 extern "C" int ffq_conv_transpose2d_w8a8(const int8_t* xq, int x_nhwc, const int8_t* wq, const float* x_scale, const float* x_offset,
@@ -425,25 +414,16 @@ extern "C" int ffq_conv_transpose2d_w8a8(const int8_t* xq, int x_nhwc, const int
                                          int64_t out_pad_w, int64_t dil_h, int64_t dil_w, void* workspace, size_t workspace_bytes,
                                          void* stream) {
   ConvtGeometry g;
-  int rc = convt_geometry(B, C, H, W, OC, KH, KW, stride_h, stride_w, pad_h, pad_w, out_pad_h, out_pad_w, dil_h, dil_w, x_nhwc, &g);
+  const int64_t in[2] = {H, W}, k[2] = {KH, KW}, st[2] = {stride_h, stride_w}, pd[2] = {pad_h, pad_w};
+  const int64_t op[2] = {out_pad_h, out_pad_w}, dl[2] = {dil_h, dil_w};
+  int rc = convt_geometry(B, C, OC, in, k, st, pd, op, dl, x_nhwc, &g);
   if (rc) return rc;
-  if (bias && !(bias_dt == FFQ_F32 || bias_dt == FFQ_BF16 || bias_dt == FFQ_F16)) return fail(FFQ_ERR_DTYPE, "bias must be f32, bf16 or f16");
   const bool requant = out_scale != nullptr;
-  if (requant) {
-    if (out_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "the re-quantized transposed convolution writes int8 codes");
-    if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
-      return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, out_num_bits);
-    if (!(y_dt == FFQ_F32 || y_dt == FFQ_BF16 || y_dt == FFQ_F16))
-      return fail(FFQ_ERR_DTYPE, "the re-quantized transposed convolution's real-valued dtype must be f32, bf16 or f16");
-  } else if (!(out_dt == FFQ_F32 || out_dt == FFQ_BF16 || out_dt == FFQ_F16)) {
-    return fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
-  }
+  rc = check_conv_output("transposed convolution", bias, bias_dt, requant, out_dt, out_num_bits, y_dt);
+  if (rc) return rc;
   if (B == 0 || OC == 0) return FFQ_OK;
-  if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (x_nhwc && !aligned16(xq)) return fail(FFQ_ERR_ARG, "channels-last input codes must be 16-byte aligned");
-  const size_t need = g.x_bytes + g.w_bytes + g.sum_bytes;
-  if (!workspace || workspace_bytes < need || !aligned16(workspace))
-    return fail(FFQ_ERR_WORKSPACE, "w8a8 transposed convolution needs %zu workspace bytes (16-byte aligned), got %zu", need, workspace_bytes);
+  rc = check_conv_buffers("transposed convolution", xq, x_nhwc, wq, x_scale, w_scale, out, workspace, workspace_bytes, g.ws.total());
+  if (rc) return rc;
 
   // the phase table: per-axis residues, then per phase the tile prefix and the first tap of the phase-major order
   PhaseTable tab = {};
@@ -462,47 +442,31 @@ extern "C" int ffq_conv_transpose2d_w8a8(const int8_t* xq, int x_nhwc, const int
   if (tiles * tiles_m >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "extent too large for one launch");
 
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint8_t* ws = static_cast<uint8_t*>(workspace);
-  int8_t* xn = x_nhwc ? const_cast<int8_t*>(xq) : reinterpret_cast<int8_t*>(ws);
-  int8_t* wn = reinterpret_cast<int8_t*>(ws + g.x_bytes);
-  int32_t* tapsum = reinterpret_cast<int32_t*>(ws + g.x_bytes + g.w_bytes);
-  hipError_t e = hipMemsetAsync(tapsum, 0, (size_t)(OC * g.taps + OC * g.nph) * 4, s);
-  if (e != hipSuccess) return fail(FFQ_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
+  ConvBuffers buf;
+  rc = carve_conv_workspace(xq, x_nhwc, workspace, g.ws, OC * g.taps + OC * g.nph, s, &buf);
+  if (rc) return rc;
   const int groups = (int)(g.Cp / 16);
   const int64_t n_in = x_nhwc ? 0 : B * H * W * groups;
   const int64_t n_w = OC * g.taps * groups;
   const int64_t threads = n_in + n_w;
   if ((threads + 255) / 256 >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "extent too large for one launch");
-  convt_reorder_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(xq, xn, n_in, (int)C, H * W, groups, wq, wn, n_w, (int)g.taps,
-                                                                          (int)KW, (int)OC, (int)stride_h, (int)stride_w, (int)pad_h,
-                                                                          (int)pad_w, (int)dil_h, (int)dil_w, tapsum, tab);
+  convt_reorder_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(xq, buf.xn, n_in, (int)C, H * W, groups, wq, buf.wn, n_w,
+                                                                          (int)g.taps, (int)KW, (int)OC, (int)stride_h, (int)stride_w,
+                                                                          (int)pad_h, (int)pad_w, (int)dil_h, (int)dil_w, buf.tapsum, tab);
   rc = check_launch("convt_reorder_kernel");
   if (rc) return rc;
 
   ConvtArgs a;
-  a.wq = wn; a.xq = xn; a.tapsum = tapsum;
-  a.x_scale = x_scale; a.x_offset = x_offset;
-  a.w_scale = w_scale; a.w_offset = w_offset; a.w_per_row = w_per_channel ? 1 : 0;
-  a.bias = bias; a.bias_dt = bias_dt;
-  a.out = out;
-  a.out_scale = out_scale; a.out_offset = out_offset;
-  const double lo = -pow(2.0, out_num_bits - 1.0);
-  a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
-  a.y_dt = y_dt;
+  a.wq = buf.wn; a.xq = buf.xn; a.tapsum = buf.tapsum;
+  fill_conv_operands(a, x_scale, x_offset, w_scale, w_offset, w_per_channel, bias, bias_dt, out, out_scale, out_offset, out_num_bits, y_dt);
   a.B = (int)B; a.OC = (int)OC; a.C = (int)C; a.Cp = (int)g.Cp; a.H = (int)H; a.W = (int)W;
   a.OH = (int)g.OH; a.OW = (int)g.OW; a.taps = (int)g.taps;
   a.sh = (int)stride_h; a.sw = (int)stride_w; a.nph = (int)g.nph;
   a.Kp = (int)g.Kp;
   a.tiles_m = (int)tiles_m;
   const unsigned grid = (unsigned)(tiles * tiles_m);
-  if (requant) {
-    convt_w8a8_kernel<int8_t, true><<<grid, 256, 0, s>>>(a, tab);
-  } else {
-    switch (out_dt) {
-      case FFQ_BF16: convt_w8a8_kernel<bf16_t, false><<<grid, 256, 0, s>>>(a, tab); break;
-      case FFQ_F16: convt_w8a8_kernel<f16_t, false><<<grid, 256, 0, s>>>(a, tab); break;
-      default: convt_w8a8_kernel<float, false><<<grid, 256, 0, s>>>(a, tab); break;
-    }
-  }
+  dispatch_conv_output(requant, out_dt, [&](auto t, auto q) {
+    convt_w8a8_kernel<typename decltype(t)::type, decltype(q)::value><<<grid, 256, 0, s>>>(a, tab);
+  });
   return check_launch("convt_w8a8_kernel");
 }

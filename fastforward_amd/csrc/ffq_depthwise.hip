@@ -19,11 +19,10 @@
 //     kStrided: one byte per tap and output from the staged patch; kDirect (a patch above the LDS budget: very large dilation or
 //     stride): the same loop on bounds-checked global bytes, served by the caches;
 //   * the 4 results leave as one 4 / 8 / 16-byte store (codes / 16-bit / fp32) when OW % 4 == 0, else element by element (the tail form).
+#include "ffq_conv_host.h"
 #include "ffq_conv_tile.h"
 
 #include "../../include/ffq_depthwise.h"
-
-#include <math.h>
 
 namespace ffq {
 namespace {
@@ -271,30 +270,15 @@ extern "C" int ffq_depthwise_conv2d_w8a8(const int8_t* xq, const int8_t* wq, con
   const int64_t TW = (int64_t)LX * kRun;
   const int64_t tiles_x = (OW + TW - 1) / TW, tiles_y = (OH + LY - 1) / LY;
   if (B * OC >= kDwMaxBlocks / (tiles_x * tiles_y)) return fail(FFQ_ERR_ARG, "extent too large for one launch");
-  if (bias && !(bias_dt == FFQ_F32 || bias_dt == FFQ_BF16 || bias_dt == FFQ_F16)) return fail(FFQ_ERR_DTYPE, "bias must be f32, bf16 or f16");
   const bool requant = out_scale != nullptr;
-  if (requant) {
-    if (out_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "the re-quantized convolution writes int8 codes");
-    if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
-      return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, out_num_bits);
-    if (!(y_dt == FFQ_F32 || y_dt == FFQ_BF16 || y_dt == FFQ_F16))
-      return fail(FFQ_ERR_DTYPE, "the re-quantized convolution's real-valued dtype must be f32, bf16 or f16");
-  } else if (!(out_dt == FFQ_F32 || out_dt == FFQ_BF16 || out_dt == FFQ_F16)) {
-    return fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
-  }
+  int rc = check_conv_output("convolution", bias, bias_dt, requant, out_dt, out_num_bits, y_dt);
+  if (rc) return rc;
   if (B == 0 || C == 0) return FFQ_OK;
   if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
 
   DepthwiseArgs a;
   a.xq = xq; a.wq = wq;
-  a.x_scale = x_scale; a.x_offset = x_offset;
-  a.w_scale = w_scale; a.w_offset = w_offset; a.w_per_row = w_per_channel ? 1 : 0;
-  a.bias = bias; a.bias_dt = bias_dt;
-  a.out = out;
-  a.out_scale = out_scale; a.out_offset = out_offset;
-  const double lo = -pow(2.0, out_num_bits - 1.0);
-  a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
-  a.y_dt = y_dt;
+  fill_conv_operands(a, x_scale, x_offset, w_scale, w_offset, w_per_channel, bias, bias_dt, out, out_scale, out_offset, out_num_bits, y_dt);
   a.C = (int)C; a.M = (int)M; a.OC = (int)OC; a.H = (int)H; a.W = (int)W; a.KH = (int)KH; a.KW = (int)KW; a.OH = (int)OH; a.OW = (int)OW;
   a.sh = (int)stride_h; a.sw = (int)stride_w; a.ph = (int)pad_h; a.pw = (int)pad_w; a.dh = (int)dil_h; a.dw = (int)dil_w;
   a.lx_log2 = __builtin_ctz((unsigned)LX); a.LY = LY;
@@ -314,14 +298,8 @@ extern "C" int ffq_depthwise_conv2d_w8a8(const int8_t* xq, const int8_t* wq, con
   const unsigned grid = (unsigned)(B * OC * tiles_x * tiles_y);
   const unsigned block = LX * LY < 64 ? 64u : (unsigned)(LX * LY);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (requant) {
-    launch_depthwise<int8_t, true>(mode, grid, block, lds_bytes, s, a);
-  } else {
-    switch (out_dt) {
-      case FFQ_BF16: launch_depthwise<bf16_t, false>(mode, grid, block, lds_bytes, s, a); break;
-      case FFQ_F16: launch_depthwise<f16_t, false>(mode, grid, block, lds_bytes, s, a); break;
-      default: launch_depthwise<float, false>(mode, grid, block, lds_bytes, s, a); break;
-    }
-  }
+  dispatch_conv_output(requant, out_dt, [&](auto t, auto q) {
+    launch_depthwise<typename decltype(t)::type, decltype(q)::value>(mode, grid, block, lds_bytes, s, a);
+  });
   return check_launch("depthwise_w8a8_kernel");
 }

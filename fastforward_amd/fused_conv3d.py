@@ -23,40 +23,24 @@ from __future__ import annotations
 
 from typing import Any
 
-from fastforward_amd import _native, ops
 from fastforward_amd.dispatcher import Predicate, register
-from fastforward_amd.fused_conv import ConvKernels, geometry
+from fastforward_amd.fused_conv import MAX_REDUCTION, ConvKernels, ConvSet, any_operands, geometry, ungrouped
 from fastforward_amd.fused_modules import KERNELS as _MODULES
-from fastforward_amd.fused_modules import _settle
 
 
 class Conv3dKernels(ConvKernels):
-    """Predicate and kernel of ``conv3d``."""
+    """Predicate and kernel of ``conv3d``: ``ConvKernels``' rules and run body under the operator's names."""
 
     def supported_conv3d(self, **kwargs: Any) -> bool:
-        # (`supported` first: it is what establishes that the device library is loaded)
-        return self.supported(3, **kwargs) and getattr(_native.library(), "ffq_conv3d_w8a8", None) is not None
+        return self._accepts(3, **kwargs)
 
     def conv3d(self, input: Any, weight: Any, bias: Any = None, stride: Any = 1, padding: Any = 0, dilation: Any = 1, groups: int = 1, *,
                output_quantizer: Any = None, strict_quantization: bool | None = None) -> Any:
-        k = self._k
-        deq = k._deq_dtype(input)
-        stride3, padding3, dilation3 = geometry(3, input.shape[2:], weight.shape[2:], stride, padding, dilation)
-        if isinstance(bias, k.surface.quantized_tensor):
-            bias = bias.dequantize()
-        _settle(input)
-        _settle(weight)
-        (xs, xo), (ws, wo) = k._scale_offset(input), k._scale_offset(weight)
-        x, w = k._int8_codes(input), k._int8_codes(weight)
-        fused = self._m._output(output_quantizer, deq)
-        if fused is not None:
-            args = dict(out_scale=fused["out_scale"], out_offset=fused["out_offset"], out_num_bits=fused["out_num_bits"], requant_from=deq)
-        else:
-            args = dict(out_dtype=deq)
-        out = ops.conv3d_w8a8(x, w, xs, xo, ws, wo, bias, stride3, padding3, dilation3, **args)
-        return self._m._finish(out, [out], fused, output_quantizer, deq)
+        return self._run(3, input, weight, bias, output_quantizer, stride, padding, dilation)
 
 
-KERNELS = Conv3dKernels(_MODULES)
+KERNELS = Conv3dKernels(_MODULES, ConvSet(in_axis=1, oc_axis=0, groups_rule=ungrouped, grouping_rule=any_operands, bound=MAX_REDUCTION, geometry=geometry,
+                                          geometry_operands=("stride", "padding", "dilation"), op="conv3d_w8a8",
+                                          symbol="ffq_conv3d_w8a8"))
 conv3d_predicate = Predicate(KERNELS.supported_conv3d)
 _registrations = {"conv3d": register("conv3d", conv3d_predicate, KERNELS.conv3d)}

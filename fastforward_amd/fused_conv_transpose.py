@@ -23,14 +23,9 @@ import math
 
 from typing import Any
 
-import torch
-
-from fastforward_amd import ops
 from fastforward_amd.dispatcher import Predicate, register
-from fastforward_amd.fused_conv import KERNELS as _CONV
-from fastforward_amd.fused_conv import MAX_REDUCTION, _ints
-from fastforward_amd.fused_linear import _FLOATS
-from fastforward_amd.fused_modules import _needs_grad, _on_device, _settle
+from fastforward_amd.fused_conv import MAX_REDUCTION, ConvKernels, ConvSet, _ints, any_operands, ungrouped
+from fastforward_amd.fused_modules import KERNELS as _MODULES
 from fastforward_amd.ops.conv import MAX_PHASES
 
 
@@ -52,83 +47,29 @@ def transposed_geometry(dims: int, input_shape: Any, kernel: Any, stride: Any, p
     return (s[0], s[1]), (p[0], p[1]), (op[0], op[1]), (d[0], d[1])
 
 
-class ConvTransposeKernels:
-    """Predicates and kernels of ``conv_transpose1d`` / ``conv_transpose2d`` (through ``ConvKernels``' helpers)."""
-
-    def __init__(self, conv: Any) -> None:
-        self._c = conv
-        self._m = conv._m
-        self._k = conv._k
-
-    def supported(self, dims: int, input: Any = None, weight: Any = None, bias: Any = None, stride: Any = 1, padding: Any = 0,
-                  output_padding: Any = 0, groups: int = 1, dilation: Any = 1, output_quantizer: Any = None,
-                  strict_quantization: bool | None = None, **_: Any) -> bool:
-        k, codes_ok = self._k, self._c._codes_ok
-        if not self._m._strict_ok(strict_quantization, output_quantizer, input, weight) or groups != 1:
-            return False
-        if not (codes_ok(input) and codes_ok(weight)) or input.dim() != dims + 2 or weight.dim() != dims + 2:
-            return False
-        if not _on_device(input, weight) or input.numel() == 0 or weight.numel() == 0 or input.shape[1] != weight.shape[0]:
-            return False
-        deq = k._deq_dtype(input)
-        if deq not in _FLOATS or k._deq_dtype(weight) != deq:
-            return False
-        if k._tile(input) != tuple(input.shape) or k._tile(weight) not in (tuple(weight.shape), (weight.shape[0], 1, *weight.shape[2:])):
-            return False  # per-tensor activations; per-tensor or per-output-channel (dim 1) weights
-        if weight.shape[0] * math.prod(weight.shape[2:]) > MAX_REDUCTION:
-            return False
-        if transposed_geometry(dims, input.shape[2:], weight.shape[2:], stride, padding, output_padding, dilation) is None:
-            return False
-        if bias is not None:
-            if isinstance(bias, k.surface.quantized_tensor):
-                if not k.static_affine(bias) or k._deq_dtype(bias) != deq:
-                    return False
-            elif not isinstance(bias, torch.Tensor) or bias.dtype != deq:
-                return False
-            if bias.numel() != weight.shape[1] or not _on_device(bias):
-                return False
-        return not _needs_grad(input, weight, bias)
+class ConvTransposeKernels(ConvKernels):
+    """Predicates and kernels of ``conv_transpose1d`` / ``conv_transpose2d``: ``ConvKernels``' rules and run body under the
+    operators' names and argument order."""
 
     def supported_conv_transpose1d(self, **kwargs: Any) -> bool:
-        return self.supported(1, **kwargs)
+        return self._accepts(1, **kwargs)
 
     def supported_conv_transpose2d(self, **kwargs: Any) -> bool:
-        return self.supported(2, **kwargs)
-
-    def _conv_transpose(self, dims: int, input: Any, weight: Any, bias: Any, stride: Any, padding: Any, output_padding: Any,
-                        dilation: Any, output_quantizer: Any) -> Any:
-        k = self._k
-        deq = k._deq_dtype(input)
-        stride2, padding2, out_padding2, dilation2 = transposed_geometry(dims, input.shape[2:], weight.shape[2:], stride, padding,
-                                                                         output_padding, dilation)
-        if isinstance(bias, k.surface.quantized_tensor):
-            bias = bias.dequantize()
-        _settle(input)
-        _settle(weight)
-        (xs, xo), (ws, wo) = k._scale_offset(input), k._scale_offset(weight)
-        x, w = k._int8_codes(input), k._int8_codes(weight)
-        if dims == 1:
-            x, w = x.unsqueeze(2), w.unsqueeze(2)
-        fused = self._m._output(output_quantizer, deq)
-        if fused is not None:
-            args = dict(out_scale=fused["out_scale"], out_offset=fused["out_offset"], out_num_bits=fused["out_num_bits"], requant_from=deq)
-        else:
-            args = dict(out_dtype=deq)
-        out = ops.conv_transpose2d_w8a8(x, w, xs, xo, ws, wo, bias, stride2, padding2, out_padding2, dilation2, **args)
-        if dims == 1:
-            out = out.squeeze(2)
-        return self._m._finish(out, [out], fused, output_quantizer, deq)
+        return self._accepts(2, **kwargs)
 
     def conv_transpose1d(self, input: Any, weight: Any, bias: Any = None, stride: Any = 1, padding: Any = 0, output_padding: Any = 0,
                          groups: int = 1, dilation: Any = 1, *, output_quantizer: Any = None, strict_quantization: bool | None = None) -> Any:
-        return self._conv_transpose(1, input, weight, bias, stride, padding, output_padding, dilation, output_quantizer)
+        return self._run(1, input, weight, bias, output_quantizer, stride, padding, output_padding, dilation)
 
     def conv_transpose2d(self, input: Any, weight: Any, bias: Any = None, stride: Any = 1, padding: Any = 0, output_padding: Any = 0,
                          groups: int = 1, dilation: Any = 1, *, output_quantizer: Any = None, strict_quantization: bool | None = None) -> Any:
-        return self._conv_transpose(2, input, weight, bias, stride, padding, output_padding, dilation, output_quantizer)
+        return self._run(2, input, weight, bias, output_quantizer, stride, padding, output_padding, dilation)
 
 
-KERNELS = ConvTransposeKernels(_CONV)
+KERNELS = ConvTransposeKernels(_MODULES, ConvSet(in_axis=0, oc_axis=1, groups_rule=ungrouped, grouping_rule=any_operands, bound=MAX_REDUCTION,
+                                                 geometry=transposed_geometry,
+                                                 geometry_operands=("stride", "padding", "output_padding", "dilation"),
+                                                 op="conv_transpose2d_w8a8"))
 conv_transpose1d_predicate = Predicate(KERNELS.supported_conv_transpose1d)
 conv_transpose2d_predicate = Predicate(KERNELS.supported_conv_transpose2d)
 _registrations = {

@@ -21,91 +21,32 @@ device memory on the host: the route is capturable in a ``torch.cuda.graph``. ``
 
 from __future__ import annotations
 
-import math
-
 from typing import Any
 
-import torch
-
-from fastforward_amd import _native, fused_conv, ops
 from fastforward_amd.dispatcher import Predicate, register
-from fastforward_amd.fused_conv import geometry
-from fastforward_amd.fused_linear import _FLOATS
+from fastforward_amd.fused_conv import ConvKernels, ConvSet, geometry
 from fastforward_amd.fused_modules import KERNELS as _MODULES
-from fastforward_amd.fused_modules import _needs_grad, _settle
 
 MAX_TAPS = 1024  # KH * KW (include/ffq_depthwise.h)
 
 
-class DepthwiseKernels(fused_conv.ConvKernels):
-    """Predicates and kernels of the depthwise ``conv1d`` / ``conv2d`` (``_codes_ok`` is ConvKernels'; ``supported`` is not)."""
-
-    def supported(self, dims: int, input: Any = None, weight: Any = None, bias: Any = None, stride: Any = 1, padding: Any = 0,
-                  dilation: Any = 1, groups: int = 1, output_quantizer: Any = None, strict_quantization: bool | None = None, **_: Any) -> bool:
-        k = self._k
-        if not self._m._strict_ok(strict_quantization, output_quantizer, input, weight):
-            return False
-        if not (self._codes_ok(input) and self._codes_ok(weight)) or input.dim() != dims + 2 or weight.dim() != dims + 2:
-            return False
-        if not isinstance(groups, int) or isinstance(groups, bool) or not groups == input.shape[1] > 1:
-            return False
-        if weight.shape[1] != 1 or weight.shape[0] % groups != 0 or math.prod(weight.shape[2:]) > MAX_TAPS:
-            return False
-        if not fused_conv._on_device(input, weight) or input.numel() == 0 or weight.numel() == 0:
-            return False
-        deq = k._deq_dtype(input)
-        if deq not in _FLOATS or k._deq_dtype(weight) != deq:
-            return False
-        if k._tile(input) != tuple(input.shape) or k._tile(weight) not in (tuple(weight.shape), (1, *weight.shape[1:])):
-            return False  # per-tensor activations; per-tensor or per-output-channel weights
-        if getattr(k._params(weight).granularity, "channel_dims", (0,)) != (0,):
-            return False  # PerChannel(1): one "input channel" per group, so its tile IS the tensor; still not a per-tensor quantizer
-        if geometry(dims, input.shape[2:], weight.shape[2:], stride, padding, dilation) is None:
-            return False
-        if bias is not None:
-            if isinstance(bias, k.surface.quantized_tensor):
-                if not k.static_affine(bias) or k._deq_dtype(bias) != deq:
-                    return False
-            elif not isinstance(bias, torch.Tensor) or bias.dtype != deq:
-                return False
-            if bias.numel() != weight.shape[0] or not fused_conv._on_device(bias):
-                return False
-        return not _needs_grad(input, weight, bias)
-
-    def _exported(self) -> bool:
-        # (`supported` first: it is what establishes that the device library is loaded)
-        return getattr(_native.library(), "ffq_depthwise_conv2d_w8a8", None) is not None
-
-    def supported_conv1d(self, **kwargs: Any) -> bool:
-        return self.supported(1, **kwargs) and self._exported()
-
-    def supported_conv2d(self, **kwargs: Any) -> bool:
-        return self.supported(2, **kwargs) and self._exported()
-
-    def _conv(self, dims: int, input: Any, weight: Any, bias: Any, stride: Any, padding: Any, dilation: Any, output_quantizer: Any) -> Any:
-        k = self._k
-        deq = k._deq_dtype(input)
-        stride2, padding2, dilation2 = geometry(dims, input.shape[2:], weight.shape[2:], stride, padding, dilation)
-        if isinstance(bias, k.surface.quantized_tensor):
-            bias = bias.dequantize()
-        _settle(input)
-        _settle(weight)
-        (xs, xo), (ws, wo) = k._scale_offset(input), k._scale_offset(weight)
-        x, w = k._int8_codes(input), k._int8_codes(weight)
-        if dims == 1:
-            x, w = x.unsqueeze(2), w.unsqueeze(2)
-        fused = self._m._output(output_quantizer, deq)
-        if fused is not None:
-            args = dict(out_scale=fused["out_scale"], out_offset=fused["out_offset"], out_num_bits=fused["out_num_bits"], requant_from=deq)
-        else:
-            args = dict(out_dtype=deq)
-        out = ops.depthwise_conv2d_w8a8(x, w, xs, xo, ws, wo, bias, stride2, padding2, dilation2, **args)
-        if dims == 1:
-            out = out.squeeze(2)
-        return self._m._finish(out, [out], fused, output_quantizer, deq)
+def many_groups(groups: Any) -> bool:
+    """The groups rule of the stencil: a plain int above 1 (``groups == 1`` is the implicit GEMM's, C = 1 included)."""
+    return isinstance(groups, int) and not isinstance(groups, bool) and groups > 1
 
 
-KERNELS = DepthwiseKernels(_MODULES)
+def one_channel_per_group(groups: Any, x_shape: Any, w_shape: Any, weight: Any) -> bool:
+    """... and of the operands: as many groups as input channels, whole channel multipliers, no PerChannel(1) weight."""
+    if groups != x_shape[1] or w_shape[0] % groups != 0:
+        return False
+    # PerChannel(1): one "input channel" per group, so its tile IS the tensor; still not a per-tensor quantizer
+    return getattr(_MODULES._k._params(weight).granularity, "channel_dims", (0,)) == (0,)
+
+
+# the predicates and kernels of the depthwise ``conv1d`` / ``conv2d`` are ``ConvKernels``' own, on this set
+KERNELS = ConvKernels(_MODULES, ConvSet(in_axis=1, oc_axis=0, groups_rule=many_groups, grouping_rule=one_channel_per_group, bound=MAX_TAPS, geometry=geometry,
+                                        geometry_operands=("stride", "padding", "dilation"), op="depthwise_conv2d_w8a8",
+                                        symbol="ffq_depthwise_conv2d_w8a8"))
 conv1d_predicate = Predicate(KERNELS.supported_conv1d)
 conv2d_predicate = Predicate(KERNELS.supported_conv2d)
 _registrations = {

@@ -254,6 +254,43 @@ def test_geometry():
     assert g(2, (8, 8), (3, 3), 1, "circular", 1) is None
 
 
+# ---- the wrappers' shared validation ------------------------------------------------------------------------------------------------
+OC = 4
+WRAPPERS = {  # name -> (input shape, weight shape), OC output channels each: a few dozen elements
+    "conv2d_w8a8": ((1, 2, 4, 4), (OC, 2, 3, 3)),
+    "depthwise_conv2d_w8a8": ((1, 2, 4, 4), (OC, 1, 3, 3)),
+    "conv_transpose2d_w8a8": ((1, 2, 4, 4), (2, OC, 3, 3)),
+    "conv3d_w8a8": ((1, 2, 3, 4, 4), (OC, 2, 2, 3, 3)),
+}
+
+
+def _wrapper_error(name, **change):
+    """The exception `name` raises on otherwise valid operands with `change` applied (these checks run before any library is touched)."""
+    x_shape, w_shape = WRAPPERS[name]
+    one = torch.ones(1)
+    call = dict(x_codes=torch.zeros(x_shape, dtype=torch.int8), w_codes=torch.zeros(w_shape, dtype=torch.int8), x_scale=one, x_offset=None,
+                w_scale=one, w_offset=None)
+    call.update(change)
+    with pytest.raises((TypeError, RuntimeError)) as caught:
+        getattr(ff.ops, name)(**call)
+    return type(caught.value), str(caught.value).replace(name, "<op>")
+
+
+@pytest.mark.parametrize(
+    "change,kind,text",
+    [
+        (dict(x_codes=torch.zeros(1, 2, 4, 4)), TypeError, "<op> expects int8 codes"),
+        (dict(x_scale=torch.ones(2)), RuntimeError, "<op>: the input has one parameter pair (per-tensor)"),
+        (dict(w_scale=torch.ones(OC + 1)), RuntimeError, "<op>: the weight has 1 or 4 parameter pairs, got 5"),
+        (dict(bias=torch.zeros(OC - 1)), RuntimeError, "<op>: the bias is [4] of f32, bf16 or f16"),
+        (dict(out_dtype=torch.int8), RuntimeError, "<op>: a real-valued output is f32, bf16 or f16, got torch.int8"),
+    ],
+)
+def test_the_four_wrappers_check_their_operands_alike(change, kind, text):
+    errors = {name: _wrapper_error(name, **change) for name in WRAPPERS}
+    assert set(errors.values()) == {(kind, text)}, errors   # one type, and one message but for the op's name
+
+
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_the_hip_library_exports_both_symbols():
     dll = ctypes.CDLL(str(HIP_SO))
@@ -291,6 +328,8 @@ def _conv(lib, x=FAKE, nhwc=0, w=FAKE, xs=FAKE, ws=FAKE, bias=None, bias_dt=0, o
         (lambda lib: _conv(lib, d=(1, 0)), Status.ERR_ARG),
         (lambda lib: _conv(lib, p=(-1, 0)), Status.ERR_ARG),
         (lambda lib: _conv(lib, C=16385, KH=3, KW=3), Status.ERR_DTYPE),      # C * KH * KW >= 131072
+        (lambda lib: _conv(lib, C=1 << 62, KH=2, KW=2), Status.ERR_DTYPE),     # ... and no int64 overflow on the way: 2^64 wraps to 0
+        (lambda lib: _conv(lib, C=1 << 40, KH=1 << 24, KW=1 << 24, p=(1 << 24, 1 << 24)), Status.ERR_DTYPE),
         (lambda lib: _conv(lib, nhwc=1, C=24), Status.ERR_DTYPE),             # channels-last needs C % 16 == 0
         (lambda lib: _conv(lib, H=2, p=(0, 0)), Status.ERR_ARG),              # filter larger than the padded input
         (lambda lib: _conv(lib, bias=FAKE, bias_dt=DType.I8), Status.ERR_DTYPE),
@@ -319,6 +358,7 @@ def test_workspace_bytes():
     # NHWC input [2, 8, 8, 16] + weight [32, 3, 3, 16] + tap sums (32 * 9 + 32) int32, each rounded up to 256 bytes
     assert lib.ffq_conv2d_w8a8_workspace_bytes(2, 3, 8, 8, 32, 3, 3, 0) == 2048 + 4608 + 1280
     assert lib.ffq_conv2d_w8a8_workspace_bytes(2, 16, 8, 8, 32, 3, 3, 1) == 4608 + 1280
+    assert lib.ffq_conv2d_w8a8_workspace_bytes(1 << 20, 16, 1 << 24, 1 << 24, 32, 3, 3, 0) == 0   # no launch takes it; no overflow into a small number
 
 
 def test_the_new_kernels_spill_nothing_and_use_no_scratch():

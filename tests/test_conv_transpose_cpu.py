@@ -309,6 +309,7 @@ def _convt(lib, x=FAKE, nhwc=0, w=FAKE, xs=FAKE, ws=FAKE, bias=None, bias_dt=0, 
         (lambda lib: _convt(lib, s=(8, 9)), Status.ERR_ARG),                   # 72 phases
         (lambda lib: _convt(lib, s=(1, 65)), Status.ERR_ARG),
         (lambda lib: _convt(lib, C=16385, KH=3, KW=3), Status.ERR_DTYPE),      # C * KH * KW >= 131072
+        (lambda lib: _convt(lib, C=1 << 62, KH=2, KW=2), Status.ERR_DTYPE),     # ... and no int64 overflow on the way: 2^64 wraps to 0
         (lambda lib: _convt(lib, nhwc=1, C=24), Status.ERR_DTYPE),             # channels-last needs C % 16 == 0
         (lambda lib: _convt(lib, H=1, W=1, KH=1, KW=1, s=(1, 1), p=(1, 1)), Status.ERR_ARG),  # OH < 1
         (lambda lib: _convt(lib, H=0), Status.ERR_ARG),
@@ -339,6 +340,7 @@ def test_workspace_bytes():
     assert lib.ffq_conv_transpose2d_w8a8_workspace_bytes(2, 3, 8, 8, 32, 3, 3, 0) == 2048 + 4608 + 9472
     assert lib.ffq_conv_transpose2d_w8a8_workspace_bytes(2, 16, 8, 8, 32, 3, 3, 1) == 4608 + 9472
     assert lib.ffq_conv_transpose2d_w8a8_workspace_bytes(2, 0, 8, 8, 32, 3, 3, 0) == 0
+    assert lib.ffq_conv_transpose2d_w8a8_workspace_bytes(1 << 20, 16, 1 << 24, 1 << 24, 32, 3, 3, 0) == 0   # no launch takes it; no overflow
 
 
 def test_the_new_kernels_spill_nothing_and_use_no_scratch():

@@ -142,14 +142,33 @@ def test_the_predicate_accepts_and_declines(monkeypatch):
         assert not fused_depthwise.KERNELS.supported(2, input=x, weight=w, groups=16, **common)           # a gradient is needed
 
 
-def test_both_kernels_are_registered_and_the_gemm_predicate_is_untouched():
+def test_both_kernels_are_registered_and_the_gemm_predicate_is_untouched(monkeypatch):
     from fastforward_amd import dispatcher, fused_conv3d, fused_conv_transpose
 
     for op in ("conv1d", "conv2d"):
         fns = [item.fn for item in dispatcher._DISPATCHER[op]]
         assert getattr(fused_depthwise.KERNELS, op) in fns and getattr(fused_conv.KERNELS, op) in fns and len(fns) == 2
-    assert type(fused_conv3d.KERNELS).supported is fused_conv.ConvKernels.supported
-    assert type(fused_conv_transpose.KERNELS).__mro__[1] is not fused_depthwise.DepthwiseKernels
+    # the depthwise rules do not leak into the other sets, nor theirs into it: with the device check out of the way (as above), the
+    # depthwise operands are declined by every groups == 1 predicate, which takes its own groups == 1 call, and the reverse
+    monkeypatch.setattr("fastforward_amd.fused_conv._on_device", lambda *t: True)
+    common = dict(output_quantizer=None, strict_quantization=False)
+    x, x3 = _codes((2, 16, 9, 10)), _codes((2, 16, 6, 9, 10))
+    transposed = (fused_conv_transpose.conv_transpose2d_predicate, fused_conv_transpose.KERNELS.supported_conv_transpose2d)
+    with torch.no_grad():
+        assert fused_depthwise.KERNELS.supported(2, input=x, weight=_w((16, 1, 3, 3)), groups=16, **common)
+        assert not fused_conv.conv2d_predicate(input=x, weight=_w((16, 1, 3, 3)), groups=16, **common)
+        assert not fused_conv3d.conv3d_predicate(input=x3, weight=_w((16, 1, 3, 3, 3)), groups=16, **common)
+        for predicate in transposed:
+            assert not predicate(input=x, weight=_w((16, 1, 3, 3)), groups=16, **common)
+        assert not fused_conv_transpose.conv_transpose1d_predicate(input=_codes((2, 16, 40)), weight=_w((16, 1, 3)), groups=16, **common)
+        assert fused_conv.conv2d_predicate(input=x, weight=_w((16, 16, 3, 3)), groups=1, **common)
+        assert fused_conv3d.conv3d_predicate(input=x3, weight=_w((16, 16, 3, 3, 3)), groups=1, **common)
+        for predicate in transposed:
+            assert predicate(input=x, weight=_w((16, 1, 3, 3)), groups=1, **common)
+        assert fused_conv_transpose.conv_transpose1d_predicate(input=_codes((2, 16, 40)), weight=_w((16, 1, 3)), groups=1, **common)
+        for weight in (_w((16, 1, 3, 3)), _w((16, 16, 3, 3))):
+            assert not fused_depthwise.conv2d_predicate(input=x, weight=weight, groups=1, **common)
+            assert not fused_depthwise.KERNELS.supported(2, input=x, weight=weight, groups=1, **common)
 
 
 def test_the_wrapper_says_not_covered_on_a_library_without_the_symbol(oracle_backend):
