@@ -46,6 +46,7 @@ import fastforward_amd.fused_math  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_pool  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_concat  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_index  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_unfold  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_sdpa  # noqa: E402,F401  isort: skip
 
 __version__ = "0.1.0"

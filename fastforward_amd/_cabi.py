@@ -304,6 +304,12 @@ SIGNATURES_INDEX: dict[str, tuple[object, list[object]]] = {
     "ffq_permute_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _fp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ffq_unfold.h one to one: the fifth header's table (the quantized unfold), bound as
+# SIGNATURES_3D is (None on a library without the symbol).
+SIGNATURES_UNFOLD: dict[str, tuple[object, list[object]]] = {
+    "ffq_unfold_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_i64] * 12 + [_vp, _fp, _vp]),
+}
+
 
 class FFQLibrary:
     """A loaded implementation of the ``ffq_*`` ABI."""
@@ -331,7 +337,8 @@ class FFQLibrary:
             raise ImportError(f"{self.path} does not export {missing[0]}")
         for name in missing:
             setattr(self, name, None)
-        for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items()):
+        for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items(),
+                                          *SIGNATURES_UNFOLD.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

@@ -1,6 +1,7 @@
 // ffq_onepass.h — what the one-pass quantized families share: ffq_modules.hip (LayerNorm / Embedding / ReLU / SiLU),
 // ffq_elementwise.hip (add / sub / mul / div, softmax, sigmoid, GELU), ffq_math.hip (rms_norm, pow, exp, sin, cos, sum, cumsum),
-// ffq_pool.hip (the pools, nearest interpolate), ffq_concat.hip (cat, pad) and ffq_index.hip (index_add, permute).
+// ffq_pool.hip (the pools, nearest interpolate), ffq_concat.hip (cat, pad), ffq_index.hip (index_add, permute) and ffq_unfold.hip
+// (unfold).
 //
 // The arithmetic contract of every kernel in those files:
 //   A2  an operand given as codes is dequantized in registers as ffq_dequantize.hip does: (q + round(o)) * s in fp32 (two roundings,
@@ -143,7 +144,7 @@ __device__ __forceinline__ void store_one(T* out, const FanOut& f, const FanPara
   }
 }
 
-// ---- device: one value or one group that only moves (ffq_concat.hip, ffq_index.hip) --------------------------------------------
+// ---- device: one value or one group that only moves (ffq_concat.hip, ffq_index.hip, ffq_unfold.hip) ----------------------------
 
 // The codes of ONE value of the data dtype (store_one's arithmetic without its store: a plain element keeps its own bits).
 __device__ __forceinline__ void fan_one(const FanOut& f, const FanParams& p, float z, size_t at) {

@@ -29,8 +29,10 @@ taps) have a second kernel, the direct int8 stencil ``fastforward_amd.fused_dept
 ``groups != 1`` runs the fallback. ``index_add`` and ``permute`` follow theirs (_gen/fallback.py:1427-1449, 1483-1516) with the
 reference's signatures, and ``fastforward_amd.fused_index`` registers their one-pass kernels (include/ffq_index.h): an
 ``index_add`` that sums the addends of a row in fp32 in index order, and a ``permute`` under an output quantizer that writes the
-permuted codes directly. The other generated operators of the reference (``conv_transpose3d`` among them) are pure
-float fallbacks and are out of scope.
+permuted codes directly. ``unfold`` follows its fallback (_gen/fallback.py:1650-1677) with the reference's signature, and
+``fastforward_amd.fused_unfold`` registers the one-pass im2col (include/ffq_unfold.h), which writes the codes of the columns
+directly. The other generated operators of the reference (``conv_transpose3d`` among them) are pure float fallbacks and are out of
+scope.
 """
 
 from __future__ import annotations
@@ -49,7 +51,7 @@ if TYPE_CHECKING:
 
 __all__ = ["linear", "matmul", "mm", "bmm", "conv1d", "conv2d", "conv3d", "conv_transpose1d", "conv_transpose2d", "layer_norm", "embedding", "relu", "silu", "add", "sub", "mul", "div",
            "softmax", "sigmoid", "gelu", "dropout", "scaled_dot_product_attention", "rms_norm", "pow", "exp", "sin", "cos", "sum",
-           "cumsum", "avg_pool1d", "avg_pool2d", "avg_pool3d", "max_pool2d", "interpolate", "cat", "pad", "index_add", "permute"]
+           "cumsum", "avg_pool1d", "avg_pool2d", "avg_pool3d", "max_pool2d", "interpolate", "cat", "pad", "index_add", "permute", "unfold"]
 
 
 def _dequantized(name: str, value: Any, strict: bool, required: bool = True) -> Any:
@@ -520,6 +522,20 @@ def index_add(input: torch.Tensor, dim: int, index: torch.Tensor, source: torch.
 def permute(input: torch.Tensor, dims: tuple[int, ...], *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
     kwargs = dict(input=input, dims=dims, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
     return (dispatch("permute", **kwargs) or _fallback_permute)(**kwargs)
+
+
+# ---- unfold (reference _gen/operators.py:1500: dispatch(op, **kwargs) or the generated fallback) --------------------------------------
+def _fallback_unfold(input: torch.Tensor, kernel_size: Any, dilation: Any = 1, padding: Any = 0, stride: Any = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool = True) -> torch.Tensor:
+    """Dequantize, F.unfold, optional output quantizer (reference fallback.py:1650-1677)."""
+    _check_output_quantizer(output_quantizer, strict_quantization)
+    input = _dequantized("input", input, strict_quantization)
+    output = torch.nn.functional.unfold(input=input, kernel_size=kernel_size, dilation=dilation, padding=padding, stride=stride)
+    return output_quantizer(output) if output_quantizer is not None else output
+
+
+def unfold(input: torch.Tensor, kernel_size: Any, dilation: Any = 1, padding: Any = 0, stride: Any = 1, *, output_quantizer: Optional["Quantizer"] = None, strict_quantization: bool | None = None) -> torch.Tensor:
+    kwargs = dict(input=input, kernel_size=kernel_size, dilation=dilation, padding=padding, stride=stride, output_quantizer=output_quantizer, strict_quantization=_strict(strict_quantization))
+    return (dispatch("unfold", **kwargs) or _fallback_unfold)(**kwargs)
 
 
 from fastforward_amd.nn.sdpa import scaled_dot_product_attention  # noqa: E402  (nn/sdpa.py calls back into this module)
