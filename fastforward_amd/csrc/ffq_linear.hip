@@ -1068,95 +1068,169 @@ __global__ __launch_bounds__(1024) void offsets_nonzero_kernel(const float* __re
 
 using namespace ffq;
 
-// workspace: [M] activation row sums, [N] weight row sums, one flag word (+ padding)
-extern "C" size_t ffq_linear_w8a8_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  (void)K;
-  if (M < 0 || N < 0) return 0;
-  return (size_t)(((M + N + 1) * 4 + 255) & ~(int64_t)255);
-}
+// ---- the launch rules of this file's entry points, each stated once -----------------------------------------------------------------
+static int64_t tiles(int64_t extent, int64_t tile) { return (extent + tile - 1) / tile; }
 
 // the persistent kernel's shape class (the only one whose launches can read an earlier quantizer's codes)
-static bool linear_takes_earlier(int64_t M, int64_t N, int64_t K) {
+static bool persistent_class(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return false;
-  const int64_t tiles256 = ((M + BM2 - 1) / BM2) * ((N + 255) / 256);
-  return K % 128 == 0 && K >= 256 && M >= 128 && N >= 128 && tiles256 >= 64;
+  return K % 128 == 0 && K >= 256 && M >= 128 && N >= 128 && tiles(M, BM2) * tiles(N, 256) >= 64;
 }
 
-extern "C" int ffq_linear_w8a8_takes_earlier(int64_t M, int64_t N, int64_t K) { return linear_takes_earlier(M, N, K) ? 1 : 0; }
+extern "C" int ffq_linear_w8a8_takes_earlier(int64_t M, int64_t N, int64_t K) { return persistent_class(M, N, K) ? 1 : 0; }
 
-static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w_rowsum, const float* x_scale,
-                            const float* x_offset, int x_per_row, const float* w_scale, const float* w_offset,
-                            int w_per_row, const void* bias, int bias_dt, void* out, int out_dt,
-                            const float* out_scale, const float* out_offset, double out_num_bits, int y_dt, int64_t M,
-                            int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream, const void* gate,
-                            uint32_t* extrema_words = nullptr, void* extrema_pair = nullptr, const int32_t* run_if = nullptr, int run_when = 0,
-                            EarlierCodes earlier = {nullptr, nullptr, nullptr}, int seg_count = 1, const int64_t* seg_ns = nullptr,
-                            void* const* seg_outs = nullptr) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (M < 0 || N < 0 || K < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (M == 0 || N == 0) return FFQ_OK;
-  if (earlier.codes && (!earlier.scale || x_per_row || !aligned16(earlier.codes) || !linear_takes_earlier(M, N, K)))
-    return fail(FFQ_ERR_DTYPE, "earlier codes: per-tensor activation parameters on the persistent kernel's shapes (ffq_linear_w8a8_takes_earlier)");
-  if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
-  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
-  if (K % 16 != 0 || !aligned16(xq) || !aligned16(wq))
-    return fail(FFQ_ERR_DTYPE, "w8a8 linear needs K %% 16 == 0 and 16-byte aligned code pointers");
-  if (bias && !dt_valid(bias_dt)) return fail(FFQ_ERR_ARG, "bad bias dtype");
-  const bool requant = out_scale != nullptr;
-  if (requant) {
-    if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
-      return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.",
-                  out_dt, out_num_bits);
-    if (!(y_dt == FFQ_F32 || y_dt == FFQ_BF16 || y_dt == FFQ_F16))
-      return fail(FFQ_ERR_DTYPE, "the re-quantized linear's real-valued dtype must be f32, bf16 or f16");
-  } else if (!(out_dt == FFQ_F32 || out_dt == FFQ_BF16 || out_dt == FFQ_F16)) {
-    return fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
-  }
-  const size_t need = ffq_linear_w8a8_workspace_bytes(M, N, K);
-  // what the workspace holds: the weight row sums of a persistent launch (the tail kernel sums its own), the activation row sums and
-  // the flag of a launch with weight offsets / earlier codes. A launch with none of them runs with workspace == NULL (include/ffq.h)
-  const bool sums_in_workspace = x_offset && !w_rowsum && linear_takes_earlier(M, N, K);
-  if ((sums_in_workspace || w_offset || earlier.codes) && (need > workspace_bytes || !workspace))
-    return fail(FFQ_ERR_WORKSPACE, "w8a8 linear needs %zu workspace bytes, got %zu", need, workspace_bytes);
+// row tiles per group of the persistent kernel's tile walk: 8; 4 for long contractions (down_proj, K = 14336: +3 %; A/B of
+// 2 / 3 / 4 / 6 / 8 / 16 / 32 on one box) — the group's A panels are 256 x K bytes each
+static int walk_group_m(int64_t K) { return K >= 8192 ? 4 : GROUP_M2; }
 
-  LinearArgs a;
-  a.xq = xq; a.wq = wq;
-  a.x_scale = x_scale; a.x_offset = x_offset;
-  a.w_scale = w_scale; a.w_offset = w_offset;
-  a.rowsum_x = nullptr; a.rowsum_w = nullptr; a.woff_live = nullptr; a.rowsum_w_inside = 0;
-  a.seg_start[0] = a.seg_start[1] = INT32_MAX; a.seg_out[0] = a.seg_out[1] = nullptr;
-  a.wq2 = nullptr; a.w_scale2 = nullptr; a.rowsum_w2 = nullptr;
-  a.batch_x = a.batch_w = a.batch_out = 0;
-  a.bias = bias; a.bias_dt = bias_dt;
+// the persistent kernel's dynamic LDS: two operand slots (SLOT_BYTES each), the silu table (MLP, GATED), the threads' running extrema
+constexpr size_t persistent_lds(bool silu_table, bool extrema) {
+  return (size_t)2 * (BM2 + 256) * 128 + (silu_table ? kSiluBytes : 0) + (extrema ? 3 * 512 * 4 : 0);
+}
+
+// one instantiation of the persistent kernel over a.tiles_m x a.tiles_n tiles: one block per CU
+template <typename T, bool RQ, bool MLP, bool WO = false, bool GATED = false>
+static void launch_persistent(const LinearArgs& a, hipStream_t s) {
+  constexpr size_t lds = persistent_lds(MLP || GATED, GATED || (MLP && !RQ));
+  const unsigned total = (unsigned)(a.tiles_m * a.tiles_n);
+  static uint64_t attr_set = 0;
+  ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<T, RQ, MLP, WO, GATED>), (int)lds);
+  w8a8_gemm256fq_kernel<T, RQ, MLP, WO, GATED><<<total < 256u ? total : 256u, 512, lds, s>>>(a, (int)total);
+}
+
+// the tile kernel by output container and epilogue. Defined behind linear_w8a8_impl only so that the code object stays comparable byte for
+// byte with earlier builds (kernels lie in it in the order of their first instantiation); nothing else depends on the order
+static int launch_tile_kernel(const LinearArgs& a, dim3 grid, hipStream_t s, const char* what);
+
+// every pointer NULL, every switch off; each entry point sets the fields it means
+static LinearArgs linear_args(int64_t M, int64_t N, int64_t K) {
+  LinearArgs a{};
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.group_m = GROUP_M2;
+  a.seg_start[0] = a.seg_start[1] = INT32_MAX;
+  return a;
+}
+
+static void set_output(LinearArgs& a, void* out, int out_dt, const float* out_scale, const float* out_offset, double out_num_bits, int y_dt) {
   a.out = out; a.out_dt = out_dt;
   a.out_scale = out_scale; a.out_offset = out_offset;
   const double lo = -pow(2.0, out_num_bits - 1.0);
   a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
   a.y_dt = y_dt;
-  a.x_per_row = x_per_row; a.w_per_row = w_per_row;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.group_m = GROUP_M2;
-  a.group_cols = 0;
-  a.gate = static_cast<const bf16_t*>(gate);
-  a.run_if = run_if; a.run_when = run_when;
-  a.earlier = earlier;
-  a.extrema.words = extrema_words; a.extrema.pair = extrema_pair; a.extrema.pair_dt = FFQ_BF16;
+}
 
-  int32_t* ws = static_cast<int32_t*>(workspace);
-  const int64_t tiles256 = ((M + BM2 - 1) / BM2) * ((N + 255) / 256);
-  const bool persistent = K % 128 == 0 && K >= 256 && M >= 128 && N >= 128 && tiles256 >= 64;
+// ---- the argument checks, in the order every entry point runs them: extents, (its buffers), contraction, code pointers, output ---------
+static int check_extents(int64_t batch, int64_t M, int64_t N, int64_t K, bool* empty) {
+  *empty = batch == 0 || M == 0 || N == 0;  // nothing to do: the caller returns FFQ_OK
+  return batch < 0 || M < 0 || N < 0 || K < 0 ? fail(FFQ_ERR_ARG, "negative extent") : FFQ_OK;
+}
+
+static int check_contraction(int64_t M, int64_t N, int64_t K) {
+  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
+  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
+  return FFQ_OK;
+}
+
+static int check_codes(const char* what, const char* operands, int64_t K, bool aligned) {
+  return K % 16 != 0 || !aligned ? fail(FFQ_ERR_DTYPE, "%s needs K %% 16 == 0 and 16-byte aligned %s", what, operands) : FFQ_OK;
+}
+
+static bool real_dt(int dt) { return dt == FFQ_F32 || dt == FFQ_BF16 || dt == FFQ_F16; }
+
+static int check_output(const char* result, int out_dt, bool requant, double out_num_bits, int y_dt) {
+  if (!requant) return real_dt(out_dt) ? FFQ_OK : fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
+  if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
+    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, out_num_bits);
+  return real_dt(y_dt) ? FFQ_OK : fail(FFQ_ERR_DTYPE, "the re-quantized %s's real-valued dtype must be f32, bf16 or f16", result);
+}
+
+static int check_workspace(bool needed, const char* what, size_t need, const void* workspace, size_t workspace_bytes) {
+  return needed && (need > workspace_bytes || !workspace) ? fail(FFQ_ERR_WORKSPACE, "%s needs %zu workspace bytes, got %zu", what, need, workspace_bytes) : FFQ_OK;
+}
+
+// ---- the workspaces: one function per layout gives the byte count and the carved pointers (NULL base: the byte count alone) ----------------
+static size_t round256(int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); }
+
+// the linear's: [M] activation row sums, [N] weight row sums, one flag word (+ padding)
+struct LinearWorkspace { int32_t* rowsum_x; int32_t* rowsum_w; int32_t* flag; size_t bytes; };
+static LinearWorkspace linear_workspace(void* base, int64_t M, int64_t N) {
+  int32_t* ws = static_cast<int32_t*>(base);
+  return {ws, ws ? ws + M : nullptr, ws ? ws + M + N : nullptr, round256((M + N + 1) * 4)};
+}
+
+// gate/up's: [N] gate row sums, [N] up row sums
+struct GateUpWorkspace { int32_t* rowsum_gate; int32_t* rowsum_up; size_t bytes; };
+static GateUpWorkspace gate_up_workspace(void* base, int64_t N) {
+  int32_t* ws = static_cast<int32_t*>(base);
+  return {ws, ws ? ws + N : nullptr, round256(2 * N * 4)};
+}
+
+// gate/up while estimating: [64 int32: the flag] [gate/up's] [the linear's, for the two-launch route]
+struct EstimatingWorkspace { int32_t* flag; GateUpWorkspace sums; void* linear; size_t linear_bytes; size_t bytes; };
+static EstimatingWorkspace estimating_workspace(void* base, int64_t M, int64_t N) {
+  char* p = static_cast<char*>(base);
+  const GateUpWorkspace sums = gate_up_workspace(p ? p + 256 : nullptr, N);
+  const size_t linear_bytes = linear_workspace(nullptr, M, N).bytes;
+  return {reinterpret_cast<int32_t*>(p), sums, p ? p + 256 + sums.bytes : nullptr, linear_bytes, 256 + sums.bytes + linear_bytes};
+}
+
+extern "C" size_t ffq_linear_w8a8_workspace_bytes(int64_t M, int64_t N, int64_t K) {
+  (void)K;
+  return M < 0 || N < 0 ? 0 : linear_workspace(nullptr, M, N).bytes;
+}
+
+// what an entry point adds to the plain linear; the defaults are ffq_linear_w8a8's
+struct LinearOptions {
+  const void* gate = nullptr;  // ffq_linear_w8a8_gated
+  uint32_t* extrema_words = nullptr; void* extrema_pair = nullptr;
+  const int32_t* run_if = nullptr; int run_when = 0;  // a launch of a device-side either / or
+  EarlierCodes earlier = {nullptr, nullptr, nullptr};  // ffq_linear_w8a8_earlier
+  int seg_count = 1; const int64_t* seg_ns = nullptr; void* const* seg_outs = nullptr;  // ffq_linear_w8a8_multi
+};
+
+static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w_rowsum, const float* x_scale,
+                            const float* x_offset, int x_per_row, const float* w_scale, const float* w_offset,
+                            int w_per_row, const void* bias, int bias_dt, void* out, int out_dt,
+                            const float* out_scale, const float* out_offset, double out_num_bits, int y_dt, int64_t M,
+                            int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream, const LinearOptions& o = {}) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool persistent = persistent_class(M, N, K), requant = out_scale != nullptr;
+  bool empty;
+  if (int rc = check_extents(1, M, N, K, &empty); rc || empty) return rc;
+  if (o.earlier.codes && (!o.earlier.scale || x_per_row || !aligned16(o.earlier.codes) || !persistent))
+    return fail(FFQ_ERR_DTYPE, "earlier codes: per-tensor activation parameters on the persistent kernel's shapes (ffq_linear_w8a8_takes_earlier)");
+  if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
+  if (int rc = check_contraction(M, N, K)) return rc;
+  if (int rc = check_codes("w8a8 linear", "code pointers", K, aligned16(xq) && aligned16(wq))) return rc;
+  if (bias && !dt_valid(bias_dt)) return fail(FFQ_ERR_ARG, "bad bias dtype");
+  if (int rc = check_output("linear", out_dt, requant, out_num_bits, y_dt)) return rc;
+  // what the workspace holds: the weight row sums of a persistent launch (the tail kernel sums its own), the activation row sums and
+  // the flag of a launch with weight offsets / earlier codes. A launch with none of them runs with workspace == NULL (include/ffq.h)
+  const LinearWorkspace ws = linear_workspace(workspace, M, N);
+  if (int rc = check_workspace((x_offset && !w_rowsum && persistent) || w_offset || o.earlier.codes, "w8a8 linear", ws.bytes, workspace, workspace_bytes)) return rc;
+
+  LinearArgs a = linear_args(M, N, K);
+  a.xq = xq; a.wq = wq;
+  a.x_scale = x_scale; a.x_offset = x_offset; a.x_per_row = x_per_row;
+  a.w_scale = w_scale; a.w_offset = w_offset; a.w_per_row = w_per_row;
+  a.bias = bias; a.bias_dt = bias_dt;
+  set_output(a, out, out_dt, out_scale, out_offset, out_num_bits, y_dt);
+  a.gate = static_cast<const bf16_t*>(o.gate);
+  a.run_if = o.run_if; a.run_when = o.run_when;
+  a.earlier = o.earlier;
+  a.extrema = {o.extrema_words, o.extrema_pair, FFQ_BF16};
+
   // the gated epilogue lives in the persistent kernel's whole-line store path: everything else is the caller's two launches
-  if (gate && !(persistent && N % 64 == 0 && out_dt == FFQ_BF16 && !requant && !bias && aligned16(gate) && aligned16(out)))
+  if (o.gate && !(persistent && N % 64 == 0 && out_dt == FFQ_BF16 && !requant && !bias && aligned16(o.gate) && aligned16(out)))
     return fail(FFQ_ERR_DTYPE, "gated w8a8 linear: outside the persistent kernel's whole-line path (bf16 out, N %% 64 == 0, >= 64 tiles of 256 x 256)");
-  if (seg_count > 1) {  // several weight matrices side by side (ffq_linear_w8a8_multi): whole tiles per matrix, the persistent kernel's plain epilogue
-    if (!persistent || requant || w_offset || gate || earlier.codes) return fail(FFQ_ERR_DTYPE, "w8a8 linears in one launch: the persistent kernel's plain form only (>= 64 tiles, no weight offsets, no output quantizer)");
+  if (o.seg_count > 1) {  // several weight matrices side by side (ffq_linear_w8a8_multi): whole tiles per matrix, the persistent kernel's plain epilogue
+    if (!persistent || requant || w_offset || o.gate || o.earlier.codes) return fail(FFQ_ERR_DTYPE, "w8a8 linears in one launch: the persistent kernel's plain form only (>= 64 tiles, no weight offsets, no output quantizer)");
     int64_t at = 0;
-    for (int i = 0; i + 1 < seg_count; ++i) {
-      if (seg_ns[i] % 256 != 0) return fail(FFQ_ERR_DTYPE, "w8a8 linears in one launch: every weight matrix but the last needs a multiple of 256 rows");
-      at += seg_ns[i];
+    for (int i = 0; i + 1 < o.seg_count; ++i) {
+      if (o.seg_ns[i] % 256 != 0) return fail(FFQ_ERR_DTYPE, "w8a8 linears in one launch: every weight matrix but the last needs a multiple of 256 rows");
+      at += o.seg_ns[i];
       a.seg_start[i] = (int)at;
-      a.seg_out[i] = seg_outs[i + 1];
+      a.seg_out[i] = o.seg_outs[i + 1];
     }
   }
   bool flag_written = false;
@@ -1166,90 +1240,70 @@ static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w
     } else if (!persistent) {
       a.rowsum_w_inside = 1;  // the tail kernel sums its own weight rows (no launch ahead of it)
     } else {
-      const bool with_flag = w_offset && persistent;  // the weight-offset decision rides in this launch
-      rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(wq, (int)N, (int)K, ws + M, nullptr, with_flag ? w_offset : nullptr,
-                                                               w_per_row ? (int)N : 1, with_flag ? ws + M + N : nullptr);
-      a.rowsum_w = ws + M;
-      flag_written = with_flag;
+      flag_written = w_offset != nullptr;  // the weight-offset decision rides in this launch
+      rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(wq, (int)N, (int)K, ws.rowsum_w, nullptr, w_offset, w_per_row ? (int)N : 1,
+                                                               flag_written ? ws.flag : nullptr);
+      a.rowsum_w = ws.rowsum_w;
     }
   }
   if (w_offset) {  // sum_k xq[m, k] for the ow term
     if (persistent) {  // ... only where an offset is really non-zero: decided and consumed on the device
-      int32_t* flag = ws + M + N;
-      if (!flag_written) offsets_nonzero_kernel<<<1, 1024, 0, s>>>(w_offset, w_per_row ? (int)N : 1, flag);
-      rowsum_i8_kernel<<<(unsigned)((M + 3) / 4), 256, 0, s>>>(xq, (int)M, (int)K, ws, flag, nullptr, 0, nullptr, earlier, x_scale, x_offset);
-      a.woff_live = flag;
+      if (!flag_written) offsets_nonzero_kernel<<<1, 1024, 0, s>>>(w_offset, w_per_row ? (int)N : 1, ws.flag);
+      rowsum_i8_kernel<<<(unsigned)((M + 3) / 4), 256, 0, s>>>(xq, (int)M, (int)K, ws.rowsum_x, ws.flag, nullptr, 0, nullptr, o.earlier, x_scale, x_offset);
+      a.woff_live = ws.flag;
     } else {
-      rowsum_i8_kernel<<<(unsigned)((M + 3) / 4), 256, 0, s>>>(xq, (int)M, (int)K, ws, nullptr);
+      rowsum_i8_kernel<<<(unsigned)((M + 3) / 4), 256, 0, s>>>(xq, (int)M, (int)K, ws.rowsum_x, nullptr);
     }
-    a.rowsum_x = ws;
+    a.rowsum_x = ws.rowsum_x;
   }
 
-  if (persistent) {
-    a.tiles_m = (int)((M + BM2 - 1) / BM2);
-    a.tiles_n = (int)((N + 255) / 256);
-    // 8 row tiles per group; 4 for long contractions (down_proj, K = 14336: +3 %; A/B of 2 / 3 / 4 / 6 / 8 / 16 / 32 on one
-    // box) — the group's A panels are 256 x K bytes each
-    a.group_m = K >= 8192 ? 4 : GROUP_M2;
+  if (!persistent) {
+    a.tiles_m = (int)tiles(M, BM);
+    a.tiles_n = (int)tiles(N, BN);
+    return launch_tile_kernel(a, dim3((unsigned)(a.tiles_m * a.tiles_n)), s, "w8a8_gemm_kernel");
+  }
+  a.tiles_m = (int)tiles(M, BM2);
+  a.tiles_n = (int)tiles(N, 256);
+  a.group_m = walk_group_m(K);
 #ifdef FFQ_I8_GROUP_COLS  // A/B builds (tools/build_variant.sh): column groups where the activation codes exceed ~200 MB
-    if ((size_t)M * (size_t)K > ((size_t)200 << 20)) { a.group_cols = 1; a.group_m = FFQ_I8_GROUP_COLS; }
+  if ((size_t)M * (size_t)K > ((size_t)200 << 20)) { a.group_cols = 1; a.group_m = FFQ_I8_GROUP_COLS; }
 #endif
-    const unsigned total = (unsigned)(a.tiles_m * a.tiles_n);
-    const unsigned grid = total < 256u ? total : 256u;  // persistent: one block per CU
-    if (gate) {  // bf16 out, no re-quantization (checked above); with or without weight offsets
-      const size_t lds_gated = (size_t)2 * (BM2 + 256) * 128 + kSiluBytes + 3 * 512 * 4;
-#define FFQ_FQ_GATED(WO)                                                                                                        \
-  do {                                                                                                                          \
-    static uint64_t attr_set = 0;                                                                                               \
-    ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<bf16_t, false, false, WO, true>), (int)lds_gated); \
-    w8a8_gemm256fq_kernel<bf16_t, false, false, WO, true><<<grid, 512, lds_gated, s>>>(a, (int)total);                          \
-  } while (0)
-      if (w_offset) FFQ_FQ_GATED(true); else FFQ_FQ_GATED(false);
-#undef FFQ_FQ_GATED
-      return check_launch("w8a8_gemm256fq_kernel (gated)");
-    }
-    const size_t lds = (size_t)2 * (BM2 + 256) * 128;
-#define FFQ_FQ_LAUNCH(T, RQ, WO)                                                                            \
-  do {                                                                                                      \
-    static uint64_t attr_set = 0;                                                                           \
-    ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<T, RQ, false, WO>), (int)lds); \
-    w8a8_gemm256fq_kernel<T, RQ, false, WO><<<grid, 512, lds, s>>>(a, (int)total);                          \
-  } while (0)
-    // a predicated launch without weight offsets takes the WOFF instantiation too (the forward's own instantiations carry no
-    // predicate): its "some offset is live" word is run_if[1], which the either / or's deciding kernel keeps at zero
-    if (run_if && !w_offset) a.woff_live = run_if + 1;
-    // ... and so does one that may read an earlier quantizer's codes: its word is the workspace's flag slot, zeroed here
-    if (earlier.codes && !w_offset && !run_if) {
-      hipError_t e = hipMemsetAsync(ws + M + N, 0, 4, s);
-      if (e != hipSuccess) return fail(FFQ_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
-      a.woff_live = ws + M + N;
-    }
-#define FFQ_FQ(T, RQ) do { if (w_offset || run_if || earlier.codes) FFQ_FQ_LAUNCH(T, RQ, true); else FFQ_FQ_LAUNCH(T, RQ, false); } while (0)
-    if (requant) {
-      switch (out_dt) {
-        case FFQ_I8: FFQ_FQ(int8_t, true); break;
-        case FFQ_BF16: FFQ_FQ(bf16_t, true); break;
-        case FFQ_F16: FFQ_FQ(f16_t, true); break;
-        case FFQ_F32: FFQ_FQ(float, true); break;
-        default: return fail(FFQ_ERR_DTYPE, "re-quantized output container must be i8, bf16, f16 or f32");
-      }
-    } else {
-      switch (out_dt) {
-        case FFQ_BF16: FFQ_FQ(bf16_t, false); break;
-        case FFQ_F16: FFQ_FQ(f16_t, false); break;
-        default: FFQ_FQ(float, false); break;
-      }
-    }
-#undef FFQ_FQ
-#undef FFQ_FQ_LAUNCH
-    return check_launch("w8a8_gemm256fq_kernel");
+  if (o.gate) {  // bf16 out, no re-quantization (checked above); with or without weight offsets
+    if (w_offset) launch_persistent<bf16_t, false, false, true, true>(a, s); else launch_persistent<bf16_t, false, false, false, true>(a, s);
+    return check_launch("w8a8_gemm256fq_kernel (gated)");
   }
-
-  a.tiles_m = (int)((M + BM - 1) / BM);
-  a.tiles_n = (int)((N + BN - 1) / BN);
-  const unsigned grid = (unsigned)(a.tiles_m * a.tiles_n);
+  // a predicated launch without weight offsets takes the WOFF instantiation too (the forward's own instantiations carry no
+  // predicate): its "some offset is live" word is run_if[1], which the either / or's deciding kernel keeps at zero
+  if (o.run_if && !w_offset) a.woff_live = o.run_if + 1;
+  // ... and so does one that may read an earlier quantizer's codes: its word is the workspace's flag slot, zeroed here
+  if (o.earlier.codes && !w_offset && !o.run_if) {
+    hipError_t e = hipMemsetAsync(ws.flag, 0, 4, s);
+    if (e != hipSuccess) return fail(FFQ_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
+    a.woff_live = ws.flag;
+  }
+#define FFQ_FQ(T, RQ) do { if (w_offset || o.run_if || o.earlier.codes) launch_persistent<T, RQ, false, true>(a, s); else launch_persistent<T, RQ, false, false>(a, s); } while (0)
   if (requant) {
     switch (out_dt) {
+      case FFQ_I8: FFQ_FQ(int8_t, true); break;
+      case FFQ_BF16: FFQ_FQ(bf16_t, true); break;
+      case FFQ_F16: FFQ_FQ(f16_t, true); break;
+      case FFQ_F32: FFQ_FQ(float, true); break;
+      default: return fail(FFQ_ERR_DTYPE, "re-quantized output container must be i8, bf16, f16 or f32");
+    }
+  } else {
+    switch (out_dt) {
+      case FFQ_BF16: FFQ_FQ(bf16_t, false); break;
+      case FFQ_F16: FFQ_FQ(f16_t, false); break;
+      default: FFQ_FQ(float, false); break;
+    }
+  }
+#undef FFQ_FQ
+  return check_launch("w8a8_gemm256fq_kernel");
+}
+
+static int launch_tile_kernel(const LinearArgs& a, dim3 grid, hipStream_t s, const char* what) {
+  if (a.out_scale) {
+    switch (a.out_dt) {
       case FFQ_I8: w8a8_gemm_kernel<int8_t, true><<<grid, 256, 0, s>>>(a); break;
       case FFQ_BF16: w8a8_gemm_kernel<bf16_t, true><<<grid, 256, 0, s>>>(a); break;
       case FFQ_F16: w8a8_gemm_kernel<f16_t, true><<<grid, 256, 0, s>>>(a); break;
@@ -1257,13 +1311,13 @@ static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w
       default: return fail(FFQ_ERR_DTYPE, "re-quantized output container must be i8, bf16, f16 or f32");
     }
   } else {
-    switch (out_dt) {
+    switch (a.out_dt) {
       case FFQ_BF16: w8a8_gemm_kernel<bf16_t, false><<<grid, 256, 0, s>>>(a); break;
       case FFQ_F16: w8a8_gemm_kernel<f16_t, false><<<grid, 256, 0, s>>>(a); break;
       default: w8a8_gemm_kernel<float, false><<<grid, 256, 0, s>>>(a); break;
     }
   }
-  return check_launch("w8a8_gemm_kernel");
+  return check_launch(what);
 }
 
 extern "C" int ffq_linear_w8a8(const int8_t* xq, const int8_t* wq, const int32_t* w_rowsum, const float* x_scale,
@@ -1272,10 +1326,9 @@ extern "C" int ffq_linear_w8a8(const int8_t* xq, const int8_t* wq, const int32_t
                                const float* out_scale, const float* out_offset, double out_num_bits, int y_dt, int64_t M,
                                int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream) {
   return linear_w8a8_impl(xq, wq, w_rowsum, x_scale, x_offset, x_per_row, w_scale, w_offset, w_per_row, bias, bias_dt, out, out_dt, out_scale,
-                          out_offset, out_num_bits, y_dt, M, N, K, workspace, workspace_bytes, stream, nullptr);
+                          out_offset, out_num_bits, y_dt, M, N, K, workspace, workspace_bytes, stream);
 }
 
-// ffq_linear_w8a8 whose activation codes may not have been written (ffq_quantize_by_tile_unless_same) — see include/ffq.h
 // q_proj / k_proj / v_proj of a W8A8 attention block (three QuantizedLinear modules on one quantized hidden state, reference nn/linear.py:32-39
 // three times over _gen/fallback.py:77-112) as ONE launch: `count` (2 or 3) weight matrices whose int8 codes, scales and (optional) row
 // sums lie matrix after matrix in ONE [N, K] / [N] run each (N = the sum of Ns), separate outputs outs[i] = [M, Ns[i]]. Exactly the values
@@ -1293,18 +1346,22 @@ extern "C" int ffq_linear_w8a8_multi(const int8_t* xq, const int8_t* wq, const i
     if (!aligned16(outs[i])) return fail(FFQ_ERR_DTYPE, "w8a8 linears in one launch need 16-byte aligned outputs");
     N += Ns[i];
   }
+  LinearOptions o;
+  o.seg_count = count; o.seg_ns = Ns; o.seg_outs = outs;
   return linear_w8a8_impl(xq, wq, w_rowsum, x_scale, x_offset, x_per_row, w_scale, nullptr, 1, nullptr, 0, outs[0], out_dt, nullptr, nullptr, 8.0, 0, M, N, K,
-                          workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, 0, EarlierCodes{nullptr, nullptr, nullptr}, count, Ns, outs);
+                          workspace, workspace_bytes, stream, o);
 }
 
+// ffq_linear_w8a8 whose activation codes may not have been written (ffq_quantize_by_tile_unless_same) — see include/ffq.h
 extern "C" int ffq_linear_w8a8_earlier(const int8_t* xq, const int8_t* earlier_xq, const float* earlier_scale, const float* earlier_offset,
                                        const int8_t* wq, const int32_t* w_rowsum, const float* x_scale, const float* x_offset,
                                        const float* w_scale, const float* w_offset, int w_per_row, void* out, int out_dt, int64_t M,
                                        int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream) {
   if (!earlier_xq || !earlier_scale) return fail(FFQ_ERR_ARG, "NULL earlier codes / scale");
+  LinearOptions o;
+  o.earlier = {earlier_xq, earlier_scale, earlier_offset};
   return linear_w8a8_impl(xq, wq, w_rowsum, x_scale, x_offset, 0, w_scale, w_offset, w_per_row, nullptr, 0, out, out_dt, nullptr, nullptr, 8.0, 0,
-                          M, N, K, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, 0,
-                          EarlierCodes{earlier_xq, earlier_scale, earlier_offset});
+                          M, N, K, workspace, workspace_bytes, stream, o);
 }
 
 // out = bf16(silu(gate)) * bf16(linear(x, w))  — see include/ffq.h
@@ -1314,8 +1371,10 @@ extern "C" int ffq_linear_w8a8_gated(const int8_t* xq, const int8_t* wq, const i
                                      void* workspace, size_t workspace_bytes, uint32_t* extrema_words, void* extrema_pair, void* stream) {
   if (!gate) return fail(FFQ_ERR_ARG, "NULL gate");
   if ((extrema_words == nullptr) != (extrema_pair == nullptr)) return fail(FFQ_ERR_ARG, "extrema_words and extrema_pair come together");
+  LinearOptions o;
+  o.gate = gate; o.extrema_words = extrema_words; o.extrema_pair = extrema_pair;
   return linear_w8a8_impl(xq, wq, w_rowsum, x_scale, x_offset, x_per_row, w_scale, w_offset, w_per_row, nullptr, 0, out, FFQ_BF16, nullptr,
-                          nullptr, 8.0, 0, M, N, K, workspace, workspace_bytes, stream, gate, extrema_words, extrema_pair);
+                          nullptr, 8.0, 0, M, N, K, workspace, workspace_bytes, stream, o);
 }
 
 // ---- bmm: `batch` independent [M, K] x [N, K]^T products with ONE parameter pair per operand, as ONE launch -----------------------
@@ -1324,8 +1383,7 @@ extern "C" int ffq_linear_w8a8_gated(const int8_t* xq, const int8_t* wq, const i
 // and a torch.stack). Row sums of both operands over the flattened [batch * rows, K] matrices: two launches for the whole batch.
 extern "C" size_t ffq_bmm_w8a8_workspace_bytes(int64_t batch, int64_t M, int64_t N, int64_t K) {
   (void)K;
-  if (batch < 0 || M < 0 || N < 0) return 0;
-  return (size_t)((batch * (M + N) * 4 + 255) & ~(int64_t)255);
+  return batch < 0 || M < 0 || N < 0 ? 0 : round256(batch * (M + N) * 4);
 }
 
 extern "C" int ffq_bmm_w8a8(const int8_t* xq, const int8_t* wq, const float* x_scale, const float* x_offset, const float* w_scale,
@@ -1333,139 +1391,87 @@ extern "C" int ffq_bmm_w8a8(const int8_t* xq, const int8_t* wq, const float* x_s
                             double out_num_bits, int y_dt, int64_t batch, int64_t M, int64_t N, int64_t K, void* workspace,
                             size_t workspace_bytes, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (batch < 0 || M < 0 || N < 0 || K < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (batch == 0 || M == 0 || N == 0) return FFQ_OK;
+  bool empty;
+  if (int rc = check_extents(batch, M, N, K, &empty); rc || empty) return rc;
   if (!xq || !wq || !x_scale || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
   if (batch > 65535 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || batch * M > INT32_MAX || batch * N > INT32_MAX)
-    return fail(FFQ_ERR_ARG, "extent out of range");
-  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
-  if (K % 16 != 0 || !aligned16(xq) || !aligned16(wq) || (M * K) % 16 != 0 || (N * K) % 16 != 0)
-    return fail(FFQ_ERR_DTYPE, "batched w8a8 matmul needs K %% 16 == 0 and 16-byte aligned matrices");
-  const bool requant = out_scale != nullptr;
-  if (requant) {
-    if (!ffq_can_support_bitwidth(out_dt, out_num_bits))
-      return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, out_num_bits);
-    if (!(y_dt == FFQ_F32 || y_dt == FFQ_BF16 || y_dt == FFQ_F16)) return fail(FFQ_ERR_DTYPE, "the re-quantized product's real-valued dtype must be f32, bf16 or f16");
-  } else if (!(out_dt == FFQ_F32 || out_dt == FFQ_BF16 || out_dt == FFQ_F16)) {
-    return fail(FFQ_ERR_DTYPE, "real-valued output must be f32, bf16 or f16");
-  }
-  const size_t need = ffq_bmm_w8a8_workspace_bytes(batch, M, N, K);
-  if (w_offset && (need > workspace_bytes || !workspace)) return fail(FFQ_ERR_WORKSPACE, "batched w8a8 matmul needs %zu workspace bytes, got %zu", need, workspace_bytes);
-  LinearArgs a;
+    return fail(FFQ_ERR_ARG, "extent out of range");  // (blockIdx.y selects the pair; the row sums run over the flattened batch)
+  if (int rc = check_contraction(M, N, K)) return rc;
+  // (K % 16 == 0 makes M * K and N * K multiples of 16 too: every pair's matrices start 16-byte aligned, not only the first)
+  if (int rc = check_codes("batched w8a8 matmul", "matrices", K, aligned16(xq) && aligned16(wq))) return rc;
+  if (int rc = check_output("product", out_dt, out_scale != nullptr, out_num_bits, y_dt)) return rc;
+  if (int rc = check_workspace(w_offset != nullptr, "batched w8a8 matmul", ffq_bmm_w8a8_workspace_bytes(batch, M, N, K), workspace, workspace_bytes)) return rc;
+  LinearArgs a = linear_args(M, N, K);
   a.xq = xq; a.wq = wq;
   a.x_scale = x_scale; a.x_offset = x_offset;
   a.w_scale = w_scale; a.w_offset = w_offset;
-  a.rowsum_x = nullptr; a.rowsum_w = nullptr; a.woff_live = nullptr; a.rowsum_w_inside = 0;
-  a.seg_start[0] = a.seg_start[1] = INT32_MAX; a.seg_out[0] = a.seg_out[1] = nullptr;
-  a.wq2 = nullptr; a.w_scale2 = nullptr; a.rowsum_w2 = nullptr;
   a.batch_x = M * K; a.batch_w = N * K; a.batch_out = M * N;
-  a.gate = nullptr; a.extrema.words = nullptr; a.extrema.pair = nullptr; a.extrema.pair_dt = 0; a.run_if = nullptr; a.run_when = 0;
-  a.bias = nullptr; a.bias_dt = 0;
-  a.out = out; a.out_dt = out_dt;
-  a.out_scale = out_scale; a.out_offset = out_offset;
-  const double lo = -pow(2.0, out_num_bits - 1.0);
-  a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
-  a.y_dt = y_dt;
-  a.x_per_row = 0; a.w_per_row = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.group_m = GROUP_M2;
-  a.group_cols = 0;
-  int32_t* ws = static_cast<int32_t*>(workspace);
+  set_output(a, out, out_dt, out_scale, out_offset, out_num_bits, y_dt);
   if (x_offset) a.rowsum_w_inside = 1;  // every block sums its own weight rows (w8a8_gemm_kernel)
   if (w_offset) {
-    rowsum_i8_kernel<<<(unsigned)((batch * M + 3) / 4), 256, 0, s>>>(xq, (int)(batch * M), (int)K, ws, nullptr);
-    a.rowsum_x = ws;
+    int32_t* sums = static_cast<int32_t*>(workspace);  // [batch * M] activation row sums
+    rowsum_i8_kernel<<<(unsigned)((batch * M + 3) / 4), 256, 0, s>>>(xq, (int)(batch * M), (int)K, sums, nullptr);
+    a.rowsum_x = sums;
   }
-  a.tiles_m = (int)((M + BM - 1) / BM);
-  a.tiles_n = (int)((N + BN - 1) / BN);
-  const dim3 grid((unsigned)(a.tiles_m * a.tiles_n), (unsigned)batch);
-  if (requant) {
-    switch (out_dt) {
-      case FFQ_I8: w8a8_gemm_kernel<int8_t, true><<<grid, 256, 0, s>>>(a); break;
-      case FFQ_BF16: w8a8_gemm_kernel<bf16_t, true><<<grid, 256, 0, s>>>(a); break;
-      case FFQ_F16: w8a8_gemm_kernel<f16_t, true><<<grid, 256, 0, s>>>(a); break;
-      case FFQ_F32: w8a8_gemm_kernel<float, true><<<grid, 256, 0, s>>>(a); break;
-      default: return fail(FFQ_ERR_DTYPE, "re-quantized output container must be i8, bf16, f16 or f32");
-    }
-  } else {
-    switch (out_dt) {
-      case FFQ_BF16: w8a8_gemm_kernel<bf16_t, false><<<grid, 256, 0, s>>>(a); break;
-      case FFQ_F16: w8a8_gemm_kernel<f16_t, false><<<grid, 256, 0, s>>>(a); break;
-      default: w8a8_gemm_kernel<float, false><<<grid, 256, 0, s>>>(a); break;
-    }
-  }
-  return check_launch("w8a8_gemm_kernel (batched)");
+  a.tiles_m = (int)tiles(M, BM);
+  a.tiles_n = (int)tiles(N, BN);
+  return launch_tile_kernel(a, dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)batch), s, "w8a8_gemm_kernel (batched)");
 }
 
 // ---- gate_proj + up_proj + SiLU * up + the down_proj input quantizer in one launch -----------------------------
 extern "C" size_t ffq_mlp_gate_up_w8a8_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   (void)M; (void)K;
-  if (N < 0) return 0;
-  return (size_t)((2 * N * 4 + 255) & ~(int64_t)255);
+  return N < 0 ? 0 : gate_up_workspace(nullptr, N).bytes;
 }
 
-// `product_out` (bf16 [M, N]) instead of `codes_out`: the launch leaves silu(gate) * up itself, unquantized (+ its extrema)
+// what ffq_mlp_gate_up_w8a8_estimating adds to ffq_mlp_gate_up_w8a8
+struct GateUpOptions {
+  void* product_out = nullptr;  // (bf16 [M, N]) instead of `codes_out`: the launch leaves silu(gate) * up itself, unquantized (+ its extrema)
+  uint32_t* extrema_words = nullptr; void* extrema_pair = nullptr;
+  const int32_t* run_if = nullptr; int run_when = 0;
+};
+
 static int mlp_gate_up_w8a8_impl(const int8_t* xq, const int8_t* gate_wq, const int8_t* up_wq, const int32_t* gate_rowsum,
                                  const int32_t* up_rowsum, const float* x_scale, const float* x_offset,
                                  const float* gate_w_scale, const float* up_w_scale, int8_t* codes_out,
                                  const float* out_scale, const float* out_offset, double out_num_bits, int64_t M,
-                                 int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream,
-                                 void* product_out, uint32_t* extrema_words, void* extrema_pair, const int32_t* run_if, int run_when) {
+                                 int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream, const GateUpOptions& o = {}) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool have_sums = gate_rowsum && up_rowsum;
-  if (M < 0 || N < 0 || K < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (M == 0 || N == 0) return FFQ_OK;
-  if (!xq || !gate_wq || !up_wq || !x_scale || !gate_w_scale || !up_w_scale || (!product_out && (!codes_out || !out_scale)))
+  void* const out = o.product_out ? o.product_out : (void*)codes_out;
+  bool empty;
+  if (int rc = check_extents(1, M, N, K, &empty); rc || empty) return rc;
+  if (!xq || !gate_wq || !up_wq || !x_scale || !gate_w_scale || !up_w_scale || (!o.product_out && (!codes_out || !out_scale)))
     return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
-  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
-  if (N % 128 != 0 || K % 128 != 0 || K < 256 || !aligned16(xq) || !aligned16(gate_wq) || !aligned16(up_wq) || !aligned16(product_out ? product_out : (void*)codes_out))
+  if (int rc = check_contraction(M, N, K)) return rc;
+  if (N % 128 != 0 || K % 128 != 0 || K < 256 || !aligned16(xq) || !aligned16(gate_wq) || !aligned16(up_wq) || !aligned16(out))
     return fail(FFQ_ERR_DTYPE, "fused gate/up kernel needs N %% 128 == 0, K %% 128 == 0, K >= 256 and 16-byte aligned buffers");
-  if (!product_out && !(out_num_bits >= 1 && out_num_bits <= 8 && out_num_bits == floor(out_num_bits)))
+  if (!o.product_out && !(out_num_bits >= 1 && out_num_bits <= 8 && out_num_bits == floor(out_num_bits)))
     return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", FFQ_I8, out_num_bits);
-  const size_t need = ffq_mlp_gate_up_w8a8_workspace_bytes(M, N, K);
-  if (x_offset && !have_sums && (need > workspace_bytes || !workspace)) return fail(FFQ_ERR_WORKSPACE, "fused gate/up needs %zu workspace bytes, got %zu", need, workspace_bytes);
-  LinearArgs a;
+  const GateUpWorkspace ws = gate_up_workspace(workspace, N);
+  const bool have_sums = gate_rowsum && up_rowsum;
+  if (int rc = check_workspace(x_offset && !have_sums, "fused gate/up", ws.bytes, workspace, workspace_bytes)) return rc;
+  LinearArgs a = linear_args(M, N, K);
   a.xq = xq; a.wq = gate_wq; a.wq2 = up_wq;
   a.x_scale = x_scale; a.x_offset = x_offset;
-  a.w_scale = gate_w_scale; a.w_scale2 = up_w_scale; a.w_offset = nullptr;
-  a.rowsum_x = nullptr; a.rowsum_w = nullptr; a.rowsum_w2 = nullptr; a.woff_live = nullptr; a.rowsum_w_inside = 0;
-  a.seg_start[0] = a.seg_start[1] = INT32_MAX; a.seg_out[0] = a.seg_out[1] = nullptr;
-  a.batch_x = a.batch_w = a.batch_out = 0;
-  a.gate = nullptr; a.extrema.words = extrema_words; a.extrema.pair = extrema_pair; a.extrema.pair_dt = FFQ_BF16;
-  a.run_if = run_if; a.run_when = run_when;
-  a.bias = nullptr; a.bias_dt = 0;
-  a.out = product_out ? product_out : (void*)codes_out; a.out_dt = product_out ? FFQ_BF16 : FFQ_I8;
-  a.out_scale = out_scale; a.out_offset = out_offset;
-  const double lo = -pow(2.0, out_num_bits - 1.0);
-  a.out_lo = (float)lo; a.out_hi = (float)(-lo - 1.0);
-  a.y_dt = FFQ_BF16;
-  a.x_per_row = 0; a.w_per_row = 1;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.tiles_m = (int)((M + BM2 - 1) / BM2);
+  a.w_scale = gate_w_scale; a.w_scale2 = up_w_scale; a.w_per_row = 1;
+  a.extrema = {o.extrema_words, o.extrema_pair, FFQ_BF16};
+  a.run_if = o.run_if; a.run_when = o.run_when;
+  set_output(a, out, o.product_out ? FFQ_BF16 : FFQ_I8, out_scale, out_offset, out_num_bits, FFQ_BF16);
+  a.tiles_m = (int)tiles(M, BM2);
   a.tiles_n = (int)(N / 128);
-  a.group_m = K >= 8192 ? 4 : GROUP_M2;
-  a.group_cols = 0;
+  a.group_m = walk_group_m(K);
   if (x_offset && have_sums) {
     a.rowsum_w = gate_rowsum; a.rowsum_w2 = up_rowsum;
   } else if (x_offset) {
-    int32_t* ws = static_cast<int32_t*>(workspace);
-    rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(gate_wq, (int)N, (int)K, ws, nullptr);
-    rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(up_wq, (int)N, (int)K, ws + N, nullptr);
-    a.rowsum_w = ws; a.rowsum_w2 = ws + N;
+    rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(gate_wq, (int)N, (int)K, ws.rowsum_gate, nullptr);
+    rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(up_wq, (int)N, (int)K, ws.rowsum_up, nullptr);
+    a.rowsum_w = ws.rowsum_gate; a.rowsum_w2 = ws.rowsum_up;
   }
-  const int total = a.tiles_m * a.tiles_n;
-  if (product_out) {
-    const size_t lds = (size_t)2 * (BM2 + 256) * 128 + kSiluBytes + 3 * 512 * 4;  // ... + the threads' running extrema
-    static uint64_t attr_set = 0;
-    ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<bf16_t, false, true>), (int)lds);
-    w8a8_gemm256fq_kernel<bf16_t, false, true><<<(unsigned)(total < 256 ? total : 256), 512, lds, s>>>(a, total);
+  if (o.product_out) {
+    launch_persistent<bf16_t, false, true>(a, s);
     return check_launch("w8a8_gemm256fq_kernel (mlp mode, product)");
   }
-  const size_t lds = (size_t)2 * (BM2 + 256) * 128 + kSiluBytes;  // two operand slots + the silu table
-  static uint64_t attr_set = 0;
-  ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<int8_t, true, true>), (int)lds);
-  w8a8_gemm256fq_kernel<int8_t, true, true><<<(unsigned)(total < 256 ? total : 256), 512, lds, s>>>(a, total);
+  launch_persistent<int8_t, true, true>(a, s);
   return check_launch("w8a8_gemm256fq_kernel (mlp mode)");
 }
 
@@ -1475,7 +1481,7 @@ extern "C" int ffq_mlp_gate_up_w8a8(const int8_t* xq, const int8_t* gate_wq, con
                                     const float* out_scale, const float* out_offset, double out_num_bits, int64_t M,
                                     int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream) {
   return mlp_gate_up_w8a8_impl(xq, gate_wq, up_wq, gate_rowsum, up_rowsum, x_scale, x_offset, gate_w_scale, up_w_scale, codes_out, out_scale,
-                               out_offset, out_num_bits, M, N, K, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, 0);
+                               out_offset, out_num_bits, M, N, K, workspace, workspace_bytes, stream);
 }
 
 // ---- the gated MLP up to its product while gate_proj's and up_proj's input quantizers are being calibrated ----------------------------
@@ -1509,10 +1515,9 @@ __global__ __launch_bounds__(1024) void mlp_inputs_agree_kernel(const float* __r
 }
 }  // namespace ffq
 
-// workspace: [64 int32: the flag] [N gate row sums] [N up row sums] [ffq_linear_w8a8_workspace_bytes(M, N, K) for the two-launch route]
 extern "C" size_t ffq_mlp_gate_up_w8a8_estimating_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (M < 0 || N < 0) return 0;
-  return 256 + (size_t)((2 * N * 4 + 255) & ~(int64_t)255) + ffq_linear_w8a8_workspace_bytes(M, N, K);
+  (void)K;
+  return M < 0 || N < 0 ? 0 : estimating_workspace(nullptr, M, N).bytes;
 }
 
 extern "C" int ffq_mlp_gate_up_w8a8_estimating(const int8_t* xq_gate, const int8_t* xq_up, const int8_t* gate_wq, const int8_t* up_wq,
@@ -1522,39 +1527,37 @@ extern "C" int ffq_mlp_gate_up_w8a8_estimating(const int8_t* xq_gate, const int8
                                                int64_t M, int64_t N, int64_t K, void* workspace, size_t workspace_bytes,
                                                uint32_t* extrema_words, void* extrema_pair, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (M < 0 || N < 0 || K < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (M == 0 || N == 0) return FFQ_OK;
+  bool empty;
+  if (int rc = check_extents(1, M, N, K, &empty); rc || empty) return rc;
   if (!xq_gate || !xq_up || !gate_wq || !up_wq || !x_scale_gate || !x_scale_up || !gate_w_scale || !up_w_scale || !gate_scratch || !product_out)
     return fail(FFQ_ERR_ARG, "NULL buffer");
   if ((extrema_words == nullptr) != (extrema_pair == nullptr)) return fail(FFQ_ERR_ARG, "extrema_words and extrema_pair come together");
-  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return fail(FFQ_ERR_ARG, "extent exceeds 2^31");
-  if (K > kMaxContraction) return fail(FFQ_ERR_DTYPE, "K = %lld exceeds %lld (the int32 accumulator's bound: 2^14 * K must stay below 2^31)", (long long)K, (long long)kMaxContraction);
-  const int64_t tiles256 = ((M + BM2 - 1) / BM2) * ((N + 255) / 256);
+  if (int rc = check_contraction(M, N, K)) return rc;
   // both routes must be able to run: the one-launch mode's shapes and the persistent kernel's whole-line path of the gated epilogue
-  if (N % 128 != 0 || K % 128 != 0 || K < 256 || M < 128 || tiles256 < 64 || !aligned16(xq_gate) || !aligned16(xq_up) || !aligned16(gate_wq) ||
-      !aligned16(up_wq) || !aligned16(gate_scratch) || !aligned16(product_out))
+  if (!persistent_class(M, N, K) || N % 128 != 0 || !aligned16(xq_gate) || !aligned16(xq_up) || !aligned16(gate_wq) || !aligned16(up_wq) ||
+      !aligned16(gate_scratch) || !aligned16(product_out))
     return fail(FFQ_ERR_DTYPE, "gate/up while estimating: needs N %% 128 == 0, K %% 128 == 0, K >= 256, >= 64 tiles of 256 x 256 and 16-byte aligned buffers");
-  const size_t need = ffq_mlp_gate_up_w8a8_estimating_workspace_bytes(M, N, K);
-  if (!workspace || workspace_bytes < need) return fail(FFQ_ERR_WORKSPACE, "gate/up while estimating needs %zu workspace bytes, got %zu", need, workspace_bytes);
-  char* base = static_cast<char*>(workspace);
-  int32_t* flag = reinterpret_cast<int32_t*>(base);
-  int32_t* rs_gate = reinterpret_cast<int32_t*>(base + 256);
-  int32_t* rs_up = rs_gate + N;
-  void* lin_ws = base + 256 + ((2 * N * 4 + 255) & ~(int64_t)255);
-  const size_t lin_bytes = ffq_linear_w8a8_workspace_bytes(M, N, K);
-  mlp_inputs_agree_kernel<<<1, 1024, 0, s>>>(x_scale_gate, x_offset_gate, x_scale_up, x_offset_up, gate_w_offset, up_w_offset, (int)N, flag);
+  const EstimatingWorkspace ws = estimating_workspace(workspace, M, N);
+  if (int rc = check_workspace(true, "gate/up while estimating", ws.bytes, workspace, workspace_bytes)) return rc;
+  mlp_inputs_agree_kernel<<<1, 1024, 0, s>>>(x_scale_gate, x_offset_gate, x_scale_up, x_offset_up, gate_w_offset, up_w_offset, (int)N, ws.flag);
   // the weight row sums serve both routes (the zero-point term of either x offset)
-  rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(gate_wq, (int)N, (int)K, rs_gate, nullptr);
-  rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(up_wq, (int)N, (int)K, rs_up, nullptr);
-  int rc = check_launch("mlp_inputs_agree_kernel / rowsum_i8_kernel");
-  if (rc) return rc;
-  rc = mlp_gate_up_w8a8_impl(xq_gate, gate_wq, up_wq, rs_gate, rs_up, x_scale_gate, x_offset_gate ? x_offset_gate : nullptr, gate_w_scale, up_w_scale,
-                             nullptr, nullptr, nullptr, 8.0, M, N, K, nullptr, 0, stream, product_out, extrema_words, extrema_pair, flag, 1);
-  if (rc) return rc;
-  rc = linear_w8a8_impl(xq_gate, gate_wq, rs_gate, x_scale_gate, x_offset_gate, 0, gate_w_scale, gate_w_offset, 1, nullptr, 0, gate_scratch, FFQ_BF16,
-                        nullptr, nullptr, 8.0, 0, M, N, K, lin_ws, lin_bytes, stream, nullptr, nullptr, nullptr, flag, 0);
-  if (rc) return rc;
-  return linear_w8a8_impl(xq_up, up_wq, rs_up, x_scale_up, x_offset_up, 0, up_w_scale, up_w_offset, 1, nullptr, 0, product_out, FFQ_BF16, nullptr, nullptr,
-                          8.0, 0, M, N, K, lin_ws, lin_bytes, stream, gate_scratch, extrema_words, extrema_pair, flag, 0,
-                          EarlierCodes{xq_gate, x_scale_gate, x_offset_gate});
+  rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(gate_wq, (int)N, (int)K, ws.sums.rowsum_gate, nullptr);
+  rowsum_i8_kernel<<<(unsigned)((N + 3) / 4), 256, 0, s>>>(up_wq, (int)N, (int)K, ws.sums.rowsum_up, nullptr);
+  if (int rc = check_launch("mlp_inputs_agree_kernel / rowsum_i8_kernel")) return rc;
+  GateUpOptions one_launch;  // flag == 1: gate + up + SiLU * up -> the product and its extrema
+  one_launch.product_out = product_out; one_launch.extrema_words = extrema_words; one_launch.extrema_pair = extrema_pair;
+  one_launch.run_if = ws.flag; one_launch.run_when = 1;
+  if (int rc = mlp_gate_up_w8a8_impl(xq_gate, gate_wq, up_wq, ws.sums.rowsum_gate, ws.sums.rowsum_up, x_scale_gate, x_offset_gate, gate_w_scale, up_w_scale,
+                                     nullptr, nullptr, nullptr, 8.0, M, N, K, nullptr, 0, stream, one_launch))
+    return rc;
+  LinearOptions gate_proj;  // flag == 0: gate_proj's linear into `gate_scratch` ...
+  gate_proj.run_if = ws.flag; gate_proj.run_when = 0;
+  if (int rc = linear_w8a8_impl(xq_gate, gate_wq, ws.sums.rowsum_gate, x_scale_gate, x_offset_gate, 0, gate_w_scale, gate_w_offset, 1, nullptr, 0, gate_scratch,
+                                FFQ_BF16, nullptr, nullptr, 8.0, 0, M, N, K, ws.linear, ws.linear_bytes, stream, gate_proj))
+    return rc;
+  LinearOptions up_proj = gate_proj;  // ... then up_proj's with the gated epilogue, on gate_proj's codes where the two input quantizers agree
+  up_proj.gate = gate_scratch; up_proj.extrema_words = extrema_words; up_proj.extrema_pair = extrema_pair;
+  up_proj.earlier = {xq_gate, x_scale_gate, x_offset_gate};
+  return linear_w8a8_impl(xq_up, up_wq, ws.sums.rowsum_up, x_scale_up, x_offset_up, 0, up_w_scale, up_w_offset, 1, nullptr, 0, product_out, FFQ_BF16, nullptr,
+                          nullptr, 8.0, 0, M, N, K, ws.linear, ws.linear_bytes, stream, up_proj);
 }

@@ -4,12 +4,33 @@ forms range estimation needs (earlier codes, gated epilogue, the device-decided 
 from __future__ import annotations
 
 import ctypes
+from typing import Sequence
 
 import torch
 
 from fastforward_amd import _native
+from fastforward_amd._cabi import Status
 from fastforward_amd.ops import _base
 from fastforward_amd.ops._base import _dense, _extrema_words, _native_route, _ptr, _tag, _workspace
+
+
+def _f32(t: torch.Tensor | None) -> torch.Tensor | None:
+    """A quantizer parameter as the C ABI reads it: flat, contiguous fp32."""
+    return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def _extents(xc: torch.Tensor, wc: torch.Tensor) -> tuple[int, int, int]:
+    """(M, N, K) of ``xc [..., K] @ wc [N, K]^T``; torch's error where the two do not multiply."""
+    K, N = xc.shape[-1], wc.shape[0]
+    M = xc.numel() // K if K else 0
+    if wc.dim() != 2 or wc.shape[1] != K:
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {tuple(wc.shape)}^T)")
+    return M, N, K
+
+
+def _check_rowsum(w_rowsum: torch.Tensor | None, N: int, wc: torch.Tensor) -> None:
+    if w_rowsum is not None and (w_rowsum.dtype != torch.int32 or w_rowsum.numel() != N or not w_rowsum.is_contiguous() or w_rowsum.device != wc.device):
+        raise RuntimeError(f"w_rowsum must be a contiguous int32 tensor with {N} entries on the codes' device")
 
 
 def linear_w8a8(
@@ -51,16 +72,8 @@ def _linear_w8a8(x_codes, w_codes, x_scale, x_offset, w_scale, w_offset, bias, o
         raise TypeError("linear_w8a8 expects int8 codes")
     xc = _dense(x_codes.detach())
     wc = _dense(w_codes.detach())
-    K = xc.shape[-1]
-    N = wc.shape[0]
-    M = xc.numel() // K if K else 0
-    if wc.dim() != 2 or wc.shape[1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {tuple(wc.shape)}^T)")
-
-    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
-        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
-
-    xs, xo, ws_, wo, os_, oo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(out_scale), f32(out_offset)
+    M, N, K = _extents(xc, wc)
+    xs, xo, ws_, wo, os_, oo = _f32(x_scale), _f32(x_offset), _f32(w_scale), _f32(w_offset), _f32(out_scale), _f32(out_offset)
     bias_c = None if bias is None else bias.detach().contiguous()
     lib, stream = _base._prepare(xc, wc, xs, xo, ws_, wo, bias_c, os_, oo)
     x_per_row = int(xs.numel() != 1)
@@ -72,8 +85,7 @@ def _linear_w8a8(x_codes, w_codes, x_scale, x_offset, w_scale, w_offset, bias, o
     out = torch.empty((*xc.shape[:-1], N), dtype=out_dtype, device=xc.device)
     nbytes = lib.ffq_linear_w8a8_workspace_bytes(M, N, K)
     ws = _workspace(nbytes, xc.device)
-    if w_rowsum is not None and (w_rowsum.dtype != torch.int32 or w_rowsum.numel() != N or not w_rowsum.is_contiguous() or w_rowsum.device != wc.device):
-        raise RuntimeError(f"w_rowsum must be a contiguous int32 tensor with {N} entries on the codes' device")
+    _check_rowsum(w_rowsum, N, wc)
     y_dt = _tag(requant_from or torch.bfloat16) if os_ is not None else 0
     lib.check(
         lib.ffq_linear_w8a8(
@@ -111,15 +123,10 @@ def linear_w8a8_multi(
     M = xc.numel() // K if K else 0
     if wc.dim() != 2 or wc.shape != (N, K) or any(int(r) <= 0 for r in rows) or any(int(r) % 256 for r in rows[:-1]):
         return None
-
-    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
-        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
-
-    xs, xo, ws_ = f32(x_scale), f32(x_offset), f32(w_scale)
+    xs, xo, ws_ = _f32(x_scale), _f32(x_offset), _f32(w_scale)
     if xs.numel() not in (1, M) or ws_.numel() != N:
         return None
-    if w_rowsum is not None and (w_rowsum.dtype != torch.int32 or w_rowsum.numel() != N or not w_rowsum.is_contiguous() or w_rowsum.device != wc.device):
-        raise RuntimeError(f"w_rowsum must be a contiguous int32 tensor with {N} entries on the codes' device")
+    _check_rowsum(w_rowsum, N, wc)
     lib, stream = _base._prepare(xc, wc, xs, xo, ws_)
     outs = [torch.empty((*xc.shape[:-1], int(r)), dtype=out_dtype, device=xc.device) for r in rows]
     nbytes = lib.ffq_linear_w8a8_workspace_bytes(M, N, K)
@@ -128,7 +135,7 @@ def linear_w8a8_multi(
         _ptr(xc), _ptr(wc), _ptr(w_rowsum), _ptr(xs), _ptr(xo), int(xs.numel() != 1), _ptr(ws_), count, (ctypes.c_void_p * count)(*[_ptr(o) for o in outs]),
         _tag(out_dtype), M, (ctypes.c_int64 * count)(*[int(r) for r in rows]), K, _ptr(ws), nbytes, stream,
     )
-    if status == 6:  # FFQ_ERR_DTYPE: not the persistent kernel's shape class
+    if status == Status.ERR_DTYPE:  # not the persistent kernel's shape class
         return None
     lib.check(status)
     return outs
@@ -158,21 +165,13 @@ def linear_w8a8_earlier(
     if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8 or earlier[0].dtype != torch.int8:
         raise TypeError("linear_w8a8_earlier expects int8 codes")
     xc, wc, ec = _dense(x_codes.detach()), _dense(w_codes.detach()), _dense(earlier[0].detach())
-    K, N = xc.shape[-1], wc.shape[0]
-    M = xc.numel() // K if K else 0
-    if wc.dim() != 2 or wc.shape[1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {tuple(wc.shape)}^T)")
+    M, N, K = _extents(xc, wc)
     if ec.shape != xc.shape:
         raise RuntimeError(f"earlier codes of shape {tuple(ec.shape)} for activation codes of shape {tuple(xc.shape)}")
-
-    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
-        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
-
-    xs, xo, ws_, wo, es, eo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(earlier[1]), f32(earlier[2])
+    xs, xo, ws_, wo, es, eo = _f32(x_scale), _f32(x_offset), _f32(w_scale), _f32(w_offset), _f32(earlier[1]), _f32(earlier[2])
     if xs.numel() != 1 or es.numel() != 1 or ws_.numel() not in (1, N) or out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return None
-    if w_rowsum is not None and (w_rowsum.dtype != torch.int32 or w_rowsum.numel() != N or not w_rowsum.is_contiguous() or w_rowsum.device != wc.device):
-        raise RuntimeError(f"w_rowsum must be a contiguous int32 tensor with {N} entries on the codes' device")
+    _check_rowsum(w_rowsum, N, wc)
     lib, stream = _base._prepare(xc, ec, wc, xs, xo, ws_, wo, es, eo)
     if not lib.ffq_linear_w8a8_takes_earlier(M, N, K):
         return None
@@ -209,21 +208,13 @@ def linear_w8a8_gated(
     if x_codes.dtype != torch.int8 or w_codes.dtype != torch.int8:
         raise TypeError("linear_w8a8_gated expects int8 codes")
     xc, wc, gc = _dense(x_codes.detach()), _dense(w_codes.detach()), _dense(gate.detach())
-    K, N = xc.shape[-1], wc.shape[0]
-    M = xc.numel() // K if K else 0
-    if wc.dim() != 2 or wc.shape[1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {tuple(wc.shape)}^T)")
+    M, N, K = _extents(xc, wc)
     if gc.dtype != torch.bfloat16 or gc.numel() != M * N or gc.shape[-1] != N or M == 0 or N == 0:
         return None
-
-    def f32(t: torch.Tensor | None) -> torch.Tensor | None:
-        return None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()
-
-    xs, xo, ws_, wo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset)
+    xs, xo, ws_, wo = _f32(x_scale), _f32(x_offset), _f32(w_scale), _f32(w_offset)
     if xs.numel() not in (1, M) or ws_.numel() not in (1, N):
         return None
-    if w_rowsum is not None and (w_rowsum.dtype != torch.int32 or w_rowsum.numel() != N or not w_rowsum.is_contiguous() or w_rowsum.device != wc.device):
-        raise RuntimeError(f"w_rowsum must be a contiguous int32 tensor with {N} entries on the codes' device")
+    _check_rowsum(w_rowsum, N, wc)
     lib, stream = _base._prepare(xc, wc, gc, xs, xo, ws_, wo)
     out = torch.empty((*xc.shape[:-1], N), dtype=torch.bfloat16, device=xc.device)
     nbytes = lib.ffq_linear_w8a8_workspace_bytes(M, N, K)
@@ -234,7 +225,7 @@ def linear_w8a8_gated(
         _ptr(xc), _ptr(wc), _ptr(w_rowsum), _ptr(xs), _ptr(xo), int(xs.numel() != 1), _ptr(ws_), _ptr(wo), int(ws_.numel() != 1),
         _ptr(gc), _ptr(out), M, N, K, _ptr(ws), nbytes, _ptr(words), _ptr(pair), stream,
     )
-    if status == 6:  # FFQ_ERR_DTYPE: outside the persistent kernel's whole-line path
+    if status == Status.ERR_DTYPE:  # outside the persistent kernel's whole-line path
         return None
     lib.check(status)
     return (out, pair) if want_extrema else out
@@ -270,8 +261,7 @@ def _bmm_w8a8(x_codes, w_codes, x_scale, x_offset, w_scale, w_offset, out_dtype,
     if wc.shape[0] != B or wc.shape[2] != K:
         raise RuntimeError(f"batch1 and batch2 shapes cannot be multiplied ({tuple(xc.shape)} and {tuple(wc.shape)}^T)")
     N = wc.shape[1]
-    f32 = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
-    xs, xo, ws_, wo, os_, oo = f32(x_scale), f32(x_offset), f32(w_scale), f32(w_offset), f32(out_scale), f32(out_offset)
+    xs, xo, ws_, wo, os_, oo = _f32(x_scale), _f32(x_offset), _f32(w_scale), _f32(w_offset), _f32(out_scale), _f32(out_offset)
     if xs.numel() != 1 or ws_.numel() != 1:
         raise RuntimeError("bmm_w8a8 takes per-tensor parameters (one scale per operand)")
     lib, stream = _base._prepare(xc, wc, xs, xo, ws_, wo, os_, oo)
@@ -309,18 +299,13 @@ def mlp_gate_up_w8a8(
     xc, gc, uc = _dense(x_codes.detach()), _dense(gate_codes.detach()), _dense(up_codes.detach())
     if not (xc.dtype == gc.dtype == uc.dtype == torch.int8) or gc.shape != uc.shape or gc.dim() != 2:
         raise TypeError("mlp_gate_up_w8a8 expects int8 codes and equally shaped gate / up weights")
-    K, N = xc.shape[-1], gc.shape[0]
-    M = xc.numel() // K if K else 0
-    if gc.shape[1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {tuple(gc.shape)}^T)")
+    M, N, K = _extents(xc, gc)
     if N % 128 or K % 128 or K < 256:
         return None
 
     def f32(t: torch.Tensor | None, n: int) -> torch.Tensor | None:
-        if t is None:
-            return None
-        t = t.detach().reshape(-1).to(torch.float32).contiguous()
-        if t.numel() != n:
+        t = _f32(t)
+        if t is not None and t.numel() != n:
             raise RuntimeError(f"expected {n} parameter entries, got {t.numel()}")
         return t
 
@@ -336,7 +321,7 @@ def mlp_gate_up_w8a8(
         _ptr(xc), _ptr(gc), _ptr(uc), _ptr(gate_rowsum), _ptr(up_rowsum), _ptr(xs), _ptr(xo), _ptr(gs), _ptr(us), _ptr(out), _ptr(os_), _ptr(oo),
         float(out_num_bits), M, N, K, _ptr(ws), nbytes, stream,
     )
-    if status == 6:
+    if status == Status.ERR_DTYPE:
         return None
     lib.check(status)
     return out
@@ -363,18 +348,13 @@ def mlp_gate_up_w8a8_estimating(
     gc, uc = _dense(gate_codes.detach()), _dense(up_codes.detach())
     if not (xg.dtype == xu.dtype == gc.dtype == uc.dtype == torch.int8) or gc.shape != uc.shape or gc.dim() != 2 or xg.shape != xu.shape:
         raise TypeError("mlp_gate_up_w8a8_estimating expects int8 codes, equally shaped gate / up weights and equally shaped activations")
-    K, N = xg.shape[-1], gc.shape[0]
-    M = xg.numel() // K if K else 0
-    if gc.shape[1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({M}x{K} and {tuple(gc.shape)}^T)")
-    if N % 128 or K % 128 or K < 256 or M < 128 or ((M + 255) // 256) * ((N + 255) // 256) < 64:
+    M, N, K = _extents(xg, gc)
+    if not linear_w8a8_takes_earlier(M, N, K) or N % 128:  # both routes must be able to run (include/ffq.h)
         return None
 
     def f32(t: torch.Tensor | None, n: int) -> torch.Tensor | None:
-        if t is None:
-            return None
-        t = t.detach().reshape(-1).to(torch.float32).contiguous()
-        return t if t.numel() == n else None
+        t = _f32(t)
+        return t if t is not None and t.numel() == n else None
 
     xsg, xsu, gs, us = f32(x_params_gate[0], 1), f32(x_params_up[0], 1), f32(gate_params[0], N), f32(up_params[0], N)
     if xsg is None or xsu is None or gs is None or us is None:
@@ -393,7 +373,7 @@ def mlp_gate_up_w8a8_estimating(
         _ptr(xg), _ptr(xu), _ptr(gc), _ptr(uc), _ptr(xsg), _ptr(xog), _ptr(xsu), _ptr(xou), _ptr(gs), _ptr(go), _ptr(us), _ptr(uo),
         _ptr(gate_scratch), _ptr(product), M, N, K, _ptr(ws), nbytes, _ptr(words), _ptr(pair), stream,
     )
-    if status == 6:
+    if status == Status.ERR_DTYPE:
         return None
     lib.check(status)
     return (product, pair) if want_extrema else product

@@ -345,12 +345,7 @@ def test_all_zero_weight_offsets_cost_no_row_sums_and_change_nothing():
 _REQUANT_SHAPES = [(40, 72, 256), (300, 200, 144), (2048, 2048, 512), (4099, 2304, 384)]
 
 
-@pytest.mark.parametrize("m,n,k", _REQUANT_SHAPES, ids=str)
-@pytest.mark.parametrize("container", [torch.int8, torch.bfloat16, torch.float32], ids=str)
-@pytest.mark.parametrize("y_dtype", [torch.bfloat16, torch.float16, torch.float32], ids=str)
-def test_requantizing_epilogue_is_a1_of_the_plain_output(m, n, k, container, y_dtype):
-    """codes == quantize_by_tile(y) where y is the linear's output in the dtype the reference's float GEMM returns, formed
-    from the EXACT accumulators (tail kernel and persistent kernel shapes, ragged edges, 8 and 4 bits, with / without offset)."""
+def _requantized_is_a1_of_the_plain_output(m, n, k, container, y_dtype, grids=3):
     g = torch.Generator(device=DEV).manual_seed(m + n + k)
     xq = torch.randint(-128, 128, (m, k), device=DEV, dtype=torch.int8, generator=g)
     wq = torch.randint(-128, 128, (n, k), device=DEV, dtype=torch.int8, generator=g)
@@ -358,12 +353,28 @@ def test_requantizing_epilogue_is_a1_of_the_plain_output(m, n, k, container, y_d
     sw = torch.rand(n, device=DEV, generator=g) * 1e-3 + 1e-4
     y = _epilogue(_accumulators(xq, wq), xq, wq, sx, ox, sw, None).to(y_dtype)
     spread = float(y.float().std())
-    for bits, so, oo in ((8, spread / 40, torch.tensor([-17.6], device=DEV)), (4, spread / 3, None), (8, spread * 30, torch.tensor([0.5], device=DEV))):
+    for bits, so, oo in ((8, spread / 40, torch.tensor([-17.6], device=DEV)), (4, spread / 3, None), (8, spread * 30, torch.tensor([0.5], device=DEV)))[:grids]:
         so = torch.tensor([so], device=DEV)
         want = ops.quantize_by_tile(y, so, y.shape, bits, container, oo)
         got = ops.linear_w8a8(xq, wq, sx, ox, sw, None, out_dtype=container, out_scale=so, out_offset=oo, out_num_bits=bits, requant_from=y_dtype)
         assert got.dtype == container and torch.equal(got, want), f"{bits} bits: {int((got != want).sum())} of {want.numel()} codes differ"
         assert int(want.float().max() - want.float().min()) >= (0 if so > spread else 7)  # the fine grids are real grids, not saturated tensors
+
+
+@pytest.mark.parametrize("m,n,k", _REQUANT_SHAPES, ids=str)
+@pytest.mark.parametrize("container", [torch.int8, torch.bfloat16, torch.float32], ids=str)
+@pytest.mark.parametrize("y_dtype", [torch.bfloat16, torch.float16, torch.float32], ids=str)
+def test_requantizing_epilogue_is_a1_of_the_plain_output(m, n, k, container, y_dtype):
+    """codes == quantize_by_tile(y) where y is the linear's output in the dtype the reference's float GEMM returns, formed
+    from the EXACT accumulators (tail kernel and persistent kernel shapes, ragged edges, 8 and 4 bits, with / without offset)."""
+    _requantized_is_a1_of_the_plain_output(m, n, k, container, y_dtype)
+
+
+@pytest.mark.parametrize("m,n,k", [(16, 128, 256), (1800, 2048, 256)], ids=str)
+def test_requantizing_epilogue_into_an_fp16_container(m, n, k):
+    """The fourth container of the re-quantizing epilogue (the cases above write int8, bf16 and fp32), on the tile kernel and on the
+    persistent kernel (ragged M, 64 tiles): the same reference, on the first (8-bit, with offset) grid."""
+    _requantized_is_a1_of_the_plain_output(m, n, k, torch.float16, torch.bfloat16, grids=1)
 
 
 def test_requantizing_epilogue_refuses_a_container_that_cannot_hold_the_codes():
