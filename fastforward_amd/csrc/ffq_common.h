@@ -48,6 +48,8 @@ int fail(int code, const char* fmt, ...);
 bool generic_kernels_forced();
 bool mid_register_form_forced();  // test hook (bit 2): the register-staged 128-column-tile kernel instead of the LDS-DMA one (ffq_wmid.hip)
 bool splitk_abandon_forced();  // test hook (bit 1 of ffq_force_generic_kernels): odd K slices of a split tile abandon their wait at once
+bool ring3_form_forced();  // test hooks (bits 3 / 4): the plain int8 launch on the persistent kernel's ring / two-slot form (ffq_linear.hip)
+bool two_slot_form_forced();
 int check_launch(const char* what);
 
 // ---------------------------------------------------------------------------------------------

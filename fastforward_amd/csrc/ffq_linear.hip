@@ -275,6 +275,10 @@ __global__ __launch_bounds__(256) void w8a8_gemm_kernel(LinearArgs a) {
 //     `group_m` row tiles deep). The K-loop runs straight across tile boundaries: the last iteration of a tile prefetches
 //     the first super-step of the next tile, which lands under the epilogue. The epilogue works in the slot the tile has
 //     just consumed.
+//   * Ring form (RING3; the plain mode, which has all 160 KiB to itself): three activation images and two weight images instead of
+//     the two slots. The weight pieces of super-step ks + 1 keep their place, the activation pieces of ks + 2 go out in the LOAD
+//     segments of phases 2 and 3, and phase 3 waits with a counted vmcnt(4): an activation piece has 1.5 - 2 super-steps to land
+//     instead of 0.5 - 1. For launches whose operands exceed the Infinity Cache (down_proj): the host's ring3_form. Same sums, same bits.
 //   * Accumulator layout (the weight is the MFMA's first operand, so a lane owns ONE output row): tile (mi, nj),
 //     register t: row m = 16 mi + lane % 16, column n = 16 nj + 4 (lane / 16) + t.
 //   * MLP mode (ffq_mlp_gate_up_w8a8): the B tile holds 128 gate rows and the same 128 up rows, interleaved so that a
@@ -724,12 +728,17 @@ __device__ __forceinline__ void mlp_epilogue16_product(const LinearArgs& a, v4i3
   }
 }
 
-template <typename TOut, bool REQUANT, bool MLP, bool WOFF = false, bool GATED = false>
+template <typename TOut, bool REQUANT, bool MLP, bool WOFF = false, bool GATED = false, bool RING3 = false>
 __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, int total_tiles) {
   constexpr int BN2 = 256, WAVES_N = 4;
   constexpr int BN_OUT = MLP ? 128 : 256;
   constexpr int SLOT_BYTES = (BM2 + BN2) * 128;
   constexpr int B_IMAGE = BM2 * 128;
+  // RING3 (the plain launch only: it takes all 160 KiB): three activation images, then two weight images, 32 KiB each. Super-step g of
+  // the block (counted across its tiles) is computed from activation image g % 3 and weight image g % 2.
+  constexpr int IMAGE = BM2 * 128, RING_B0 = 3 * IMAGE;
+  static_assert(!RING3 || (!REQUANT && !MLP && !WOFF && !GATED), "the ring form has no LDS for a table or the extrema");
+  static_assert(BN2 * 128 == IMAGE, "both operands' images are 256 rows of 128 bytes");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds2[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -831,6 +840,44 @@ __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, in
       }
     }
   };
+  // RING3: the two operands change tile one super-step apart (the activations run two super-steps ahead, the weights one)
+  [[maybe_unused]] auto set_sources_a = [&](int tm0) {
+    a_base = row_base(xq_in_force, tm0);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int row = (wave * 4 + c) * 8 + d_row;
+      const int d_slot = (lane & 7) ^ ((row >> 1) & 7);
+      const int ra = tm0 + row < a.M ? row : a.M - 1 - tm0;
+      a_voff[c] = (uint32_t)ra * (uint32_t)a.K + d_slot * 16;
+    }
+  };
+  [[maybe_unused]] auto set_sources_b = [&](int tn0) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int row = (wave * 4 + c) * 8 + d_row;
+      const int d_slot = (lane & 7) ^ ((row >> 1) & 7);
+      const int rb = tn0 + row < a.N ? row : a.N - 1 - tn0;
+      b_base[c] = row_base(a.wq, tn0);
+      b_voff[c] = (uint32_t)rb * (uint32_t)a.K + d_slot * 16;
+    }
+  };
+  // ... and a piece goes to image `img` of its operand's ring: pieces c0 .. c0 + n - 1 of the wave's four
+  [[maybe_unused]] auto issue_ring_a = [&](int ks, int img, int c0, int n) {
+    uint8_t* base = lds2 + img * IMAGE;
+#pragma unroll
+    for (int c = c0; c < c0 + n; ++c) {
+      asm volatile("" : "+v"(a_voff[c]));
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)((a_base + ks * 128) + a_voff[c]), (lds_void_t*)(base + (wave * 4 + c) * 1024), 16, 0, 0);
+    }
+  };
+  [[maybe_unused]] auto issue_ring_b = [&](int ks, int img, int c0, int n) {
+    uint8_t* base = lds2 + RING_B0 + img * IMAGE;
+#pragma unroll
+    for (int c = c0; c < c0 + n; ++c) {
+      asm volatile("" : "+v"(b_voff[c]));
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)((b_base[c] + ks * 128) + b_voff[c]), (lds_void_t*)(base + (wave * 4 + c) * 1024), 16, 0, 0);
+    }
+  };
   auto issue_a = [&](int ks, int slot, int c0) {
     uint8_t* base = lds2 + slot * SLOT_BYTES;
 #pragma unroll
@@ -859,7 +906,7 @@ __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, in
 #pragma unroll
     for (int kq = 0; kq < 2; ++kq) {
       a_off[kq] = arow * 128 + (((kq * 4 + g4) ^ ((arow >> 1) & 7u)) << 4);
-      b_off[kq] = B_IMAGE + brow * 128 + (((kq * 4 + g4) ^ ((brow >> 1) & 7u)) << 4);
+      b_off[kq] = (RING3 ? 0 : B_IMAGE) + brow * 128 + (((kq * 4 + g4) ^ ((brow >> 1) & 7u)) << 4);  // (RING3: inside a weight image)
     }
   }
 
@@ -873,6 +920,15 @@ __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, in
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) fa[q] = *reinterpret_cast<const v4i*>(st + a_off[kq] + (4 * mh + q) * 2048);
+  };
+  [[maybe_unused]] auto read_frags_ring = [&](const uint8_t* sa, const uint8_t* sb, int phase) {  // the same reads, an image per operand
+    const int kq = phase >> 1, mh = phase & 1;
+    if (mh == 0) {
+#pragma unroll
+      for (int nj = 0; nj < 4; ++nj) fb[nj] = *reinterpret_cast<const v4i*>(sb + b_off[kq] + nj * 2048);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) fa[q] = *reinterpret_cast<const v4i*>(sa + a_off[kq] + (4 * mh + q) * 2048);
   };
   auto cluster = [&](int mh) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -897,7 +953,13 @@ __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, in
   int slot = 0;  // slot of the super-step about to be computed
   tile_origin(0, m0, n0);
   set_sources(m0, n0);
-  issue_a(k_rot, 0, 0); issue_a(k_rot, 0, 2); issue_b(k_rot, 0, 0); issue_b(k_rot, 0, 2);
+  [[maybe_unused]] int ai = 0, bi = 0;  // RING3: the images of the super-step about to be computed
+  if constexpr (RING3) {  // A(0), B(0), A(1)
+    const int k1 = k_rot + 1 >= ksuper ? k_rot + 1 - ksuper : k_rot + 1;
+    issue_ring_a(k_rot, 0, 0, 4); issue_ring_b(k_rot, 0, 0, 4); issue_ring_a(k1, 1, 0, 4);
+  } else {
+    issue_a(k_rot, 0, 0); issue_a(k_rot, 0, 2); issue_b(k_rot, 0, 0); issue_b(k_rot, 0, 2);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
@@ -912,54 +974,127 @@ __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, in
     const bool has_next = it + 1 < my_tiles;
     if (has_next) tile_origin(it + 1, nm0, nn0);
     if (wm == 1) __builtin_amdgcn_s_barrier();  // the upper group runs one interval behind
-    for (int ks = 0; ks < ksuper; ++ks) {
-      const uint8_t* st = lds2 + slot * SLOT_BYTES;
-      // what the first two clusters fetch into the other slot: the next super-step of this tile, or the first one of
-      // the next tile (nothing after the block's last tile: a re-load of this super-step keeps the waits uniform)
-      int fetch = ks + 1;
-      if (ks == ksuper - 1) {
-        fetch = has_next ? 0 : ks;
-        if (has_next) set_sources(nm0, nn0);
+    if constexpr (RING3) {
+      // The ring form of the loop below. The wave's four weight pieces of super-step ks + 1 go out in the LOAD segments of phases 0
+      // and 1 as there; its four activation pieces of ks + 2 follow in phases 2 and 3, into the image read a whole super-step
+      // earlier (WAR as for the weights). Loads return in order, so the counted wait of phase 3 — at most the four youngest, the
+      // activation pieces just issued, outstanding — says that the weights AND the activations of ks + 1 have landed, whatever
+      // epilogue stores are in flight: an activation piece has one and a half to two super-steps to arrive instead of half to one.
+      // The last two super-steps of a tile fetch the first two activation images of the next tile, the last one its first weight
+      // image (after the block's last tile: re-loads of the current super-step, so that the waits stay uniform). Spreading the
+      // activation pieces 1 + 2 + 1 over phases 1 - 3 measured the same (docs/experiments.md, "three-image activation ring").
+      for (int ks = 0; ks < ksuper; ++ks) {
+        const uint8_t* sa = lds2 + ai * IMAGE;
+        const uint8_t* sb = lds2 + RING_B0 + bi * IMAGE;
+        const int a2 = ai == 0 ? 2 : ai - 1;  // (ai + 2) % 3
+        int fetch_b = ks + 1;
+        if (ks == ksuper - 1) {
+          fetch_b = has_next ? 0 : ks;
+          if (has_next) set_sources_b(nn0);
+        }
+        fetch_b += k_rot;
+        fetch_b = fetch_b >= ksuper ? fetch_b - ksuper : fetch_b;
+        int fetch_a = ks + 2;
+        if (fetch_a >= ksuper) {
+          fetch_a = has_next ? fetch_a - ksuper : ks;
+          if (has_next && ks == ksuper - 2) set_sources_a(nm0);
+        }
+        fetch_a += k_rot;
+        fetch_a = fetch_a >= ksuper ? fetch_a - ksuper : fetch_a;
+        read_frags_ring(sa, sb, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_ring_b(fetch_b, bi ^ 1, 0, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(0);
+        __builtin_amdgcn_s_barrier();
+        read_frags_ring(sa, sb, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_ring_b(fetch_b, bi ^ 1, 2, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(1);
+        __builtin_amdgcn_s_barrier();
+        read_frags_ring(sa, sb, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_ring_a(fetch_a, a2, 0, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(0);
+        __builtin_amdgcn_s_barrier();
+        read_frags_ring(sa, sb, 3);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_ring_a(fetch_a, a2, 2, 2);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // A(ks + 1) and B(ks + 1) landed; A(ks + 2) may still be on its way
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(1);
+        __builtin_amdgcn_s_barrier();
+        ai = ai == 2 ? 0 : ai + 1;
+        bi ^= 1;
       }
-      fetch += k_rot;  // the depth this XCD is at (see k_rot)
-      fetch = fetch >= ksuper ? fetch - ksuper : fetch;
-      // The eight LDS-DMA pieces of a wave are issued in the LOAD segments of phases 0 and 1 — by the group that is NOT
-      // computing, behind its own fragment reads (lgkmcnt(0)) and ahead of the barrier. An LDS-DMA instruction blocks its wave's
-      // instruction stream for 60+ cycles: inside a cluster (rounds 1-2) that let the matrix pipe run dry behind every piece
-      // (round 3, A/B on one box, bit-identical: layer mix 2.52 -> 2.61 POP/s, down_proj +4.3 %, MLP mode +2.1 %; round 2's
-      // "pieces in the LOAD segments: -6 %" had them AHEAD of the reads, where they delay the fragments). WAR on the target slot:
-      // its last readers, the other group's reads of the previous super-step, were issued a whole barrier interval earlier.
-      read_frags(st, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      issue_a(fetch, slot ^ 1, 0); issue_b(fetch, slot ^ 1, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      cluster(0);
-      __builtin_amdgcn_s_barrier();
-      read_frags(st, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      issue_a(fetch, slot ^ 1, 2); issue_b(fetch, slot ^ 1, 2);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      cluster(1);
-      __builtin_amdgcn_s_barrier();
-      read_frags(st, 2);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      cluster(0);
-      __builtin_amdgcn_s_barrier();
-      read_frags(st, 3);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the fetched super-step landed (and older epilogue stores)
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      cluster(1);
-      __builtin_amdgcn_s_barrier();
-      slot ^= 1;
+    } else {
+      for (int ks = 0; ks < ksuper; ++ks) {
+        const uint8_t* st = lds2 + slot * SLOT_BYTES;
+        // what the first two clusters fetch into the other slot: the next super-step of this tile, or the first one of
+        // the next tile (nothing after the block's last tile: a re-load of this super-step keeps the waits uniform)
+        int fetch = ks + 1;
+        if (ks == ksuper - 1) {
+          fetch = has_next ? 0 : ks;
+          if (has_next) set_sources(nm0, nn0);
+        }
+        fetch += k_rot;  // the depth this XCD is at (see k_rot)
+        fetch = fetch >= ksuper ? fetch - ksuper : fetch;
+        // The eight LDS-DMA pieces of a wave are issued in the LOAD segments of phases 0 and 1 — by the group that is NOT
+        // computing, behind its own fragment reads (lgkmcnt(0)) and ahead of the barrier. An LDS-DMA instruction blocks its wave's
+        // instruction stream for 60+ cycles: inside a cluster (rounds 1-2) that let the matrix pipe run dry behind every piece
+        // (round 3, A/B on one box, bit-identical: layer mix 2.52 -> 2.61 POP/s, down_proj +4.3 %, MLP mode +2.1 %; round 2's
+        // "pieces in the LOAD segments: -6 %" had them AHEAD of the reads, where they delay the fragments). WAR on the target slot:
+        // its last readers, the other group's reads of the previous super-step, were issued a whole barrier interval earlier.
+        read_frags(st, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_a(fetch, slot ^ 1, 0); issue_b(fetch, slot ^ 1, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(0);
+        __builtin_amdgcn_s_barrier();
+        read_frags(st, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_a(fetch, slot ^ 1, 2); issue_b(fetch, slot ^ 1, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(1);
+        __builtin_amdgcn_s_barrier();
+        read_frags(st, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(0);
+        __builtin_amdgcn_s_barrier();
+        read_frags(st, 3);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the fetched super-step landed (and older epilogue stores)
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        cluster(1);
+        __builtin_amdgcn_s_barrier();
+        slot ^= 1;
+      }
     }
     if (wm == 0) __builtin_amdgcn_s_barrier();  // same number of barriers for both groups
     uint8_t* scratch = lds2 + (slot ^ 1) * SLOT_BYTES;  // the consumed slot: epilogue scratch
+    [[maybe_unused]] int scratch_wave = wave;  // the wave's place in it
+    if constexpr (RING3) {
+      // the two images the tile's last super-step was computed from (not adjacent, 32 KiB each; the activation images of the next tile's
+      // first two super-steps are in flight into the other two): waves 0-3 work in the activation image, waves 4-7 in the weight image
+      const int last_a = ai == 0 ? 2 : ai - 1, last_b = bi ^ 1;
+      scratch = wave < 4 ? lds2 + last_a * IMAGE : lds2 + RING_B0 + last_b * IMAGE;
+      scratch_wave = wave & 3;
+    }
     __syncthreads();
     if constexpr (MLP) {
       int rsw[2] = {0, 0};
@@ -991,7 +1126,7 @@ __global__ __launch_bounds__(512, 2) void w8a8_gemm256fq_kernel(LinearArgs a, in
         if (sum == 0x7fffffff) static_cast<int8_t*>(a.out)[lane] = (int8_t)sum;
       }
 #else
-      gemm256_epilogue_slabs16<TOut, REQUANT, WOFF, GATED>(a, acc, scratch, wave, lane, wm, wn, m0, n0, silu_table, zext);
+      gemm256_epilogue_slabs16<TOut, REQUANT, WOFF, GATED>(a, acc, scratch, RING3 ? scratch_wave : wave, lane, wm, wn, m0, n0, silu_table, zext);
 #endif
     }
     __syncthreads();  // the scratch slot is the next tile's DMA target
@@ -1077,25 +1212,58 @@ static bool persistent_class(int64_t M, int64_t N, int64_t K) {
   return K % 128 == 0 && K >= 256 && M >= 128 && N >= 128 && tiles(M, BM2) * tiles(N, 256) >= 64;
 }
 
+// ... and what the kernel itself needs (the 64-tile floor above is where it pays): the test seam runs plain launches on it from here
+static bool persistent_kernel_can_run(int64_t M, int64_t N, int64_t K) { return K % 128 == 0 && K >= 256 && M >= 128 && N >= 128; }
+
 extern "C" int ffq_linear_w8a8_takes_earlier(int64_t M, int64_t N, int64_t K) { return persistent_class(M, N, K) ? 1 : 0; }
 
 // row tiles per group of the persistent kernel's tile walk: 8; 4 for long contractions (down_proj, K = 14336: +3 %; A/B of
 // 2 / 3 / 4 / 6 / 8 / 16 / 32 on one box) — the group's A panels are 256 x K bytes each
 static int walk_group_m(int64_t K) { return K >= 8192 ? 4 : GROUP_M2; }
 
-// the persistent kernel's dynamic LDS: two operand slots (SLOT_BYTES each), the silu table (MLP, GATED), the threads' running extrema
-constexpr size_t persistent_lds(bool silu_table, bool extrema) {
-  return (size_t)2 * (BM2 + 256) * 128 + (silu_table ? kSiluBytes : 0) + (extrema ? 3 * 512 * 4 : 0);
+// the plain launch's staging form: three activation images (RING3) where the contraction is deep (from the depth where the group height
+// is 4) AND the two operands together exceed the 256 MiB Infinity Cache, so that the LDS-DMA's misses go to HBM — down_proj (8B: K = 14336,
+// 235 + 59 MB, +4.5 %; 70B: K = 28672, +12.5 %), a plain gate / up at 70B (K = 8192, 134 + 235 MB: +2 %); one output matrix per launch.
+// Two slots everywhere else: q / o and k / v at K = 8192 (201 / 143 MB) and everything at K = 4096 measured inside the noise
+// (docs/experiments.md, round 7; profiles/r07_gemm_ring_ab.txt). The test seam overrides the rule in either direction
+// (ffq_force_generic_kernels, bits 3 and 4).
+#ifndef FFQ_RING3_MIN_K  // A/B builds (tools/build_variant.sh)
+#define FFQ_RING3_MIN_K 8192
+#endif
+#ifndef FFQ_RING3_MIN_BYTES
+#define FFQ_RING3_MIN_BYTES ((int64_t)256 << 20)
+#endif
+static bool ring3_form(int64_t M, int64_t N, int64_t K, bool plain, int segments) {
+  if (!plain) return false;  // every other mode keeps a table or its extrema behind the two slots
+  if (two_slot_form_forced()) return false;
+  if (ring3_form_forced()) return true;
+  return segments == 1 && K >= FFQ_RING3_MIN_K && (M + N) * K > FFQ_RING3_MIN_BYTES;
 }
 
+// the persistent kernel's dynamic LDS: two operand slots (SLOT_BYTES each) or the ring form's five images — all a workgroup may declare —,
+// the silu table (MLP, GATED), the threads' running extrema
+constexpr size_t persistent_lds(bool silu_table, bool extrema, bool ring3 = false) {
+  return (ring3 ? (size_t)5 * BM2 * 128 : (size_t)2 * (BM2 + 256) * 128) + (silu_table ? kSiluBytes : 0) + (extrema ? 3 * 512 * 4 : 0);
+}
+static_assert(persistent_lds(false, false, true) == 160 * 1024, "the ring form takes exactly the CU's LDS");
+
 // one instantiation of the persistent kernel over a.tiles_m x a.tiles_n tiles: one block per CU
-template <typename T, bool RQ, bool MLP, bool WO = false, bool GATED = false>
+template <typename T, bool RQ, bool MLP, bool WO = false, bool GATED = false, bool RING3 = false>
 static void launch_persistent(const LinearArgs& a, hipStream_t s) {
-  constexpr size_t lds = persistent_lds(MLP || GATED, GATED || (MLP && !RQ));
+  constexpr size_t lds = persistent_lds(MLP || GATED, GATED || (MLP && !RQ), RING3);
   const unsigned total = (unsigned)(a.tiles_m * a.tiles_n);
   static uint64_t attr_set = 0;
-  ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<T, RQ, MLP, WO, GATED>), (int)lds);
-  w8a8_gemm256fq_kernel<T, RQ, MLP, WO, GATED><<<total < 256u ? total : 256u, 512, lds, s>>>(a, (int)total);
+  ensure_dynamic_lds(&attr_set, reinterpret_cast<const void*>(&w8a8_gemm256fq_kernel<T, RQ, MLP, WO, GATED, RING3>), (int)lds);
+  w8a8_gemm256fq_kernel<T, RQ, MLP, WO, GATED, RING3><<<total < 256u ? total : 256u, 512, lds, s>>>(a, (int)total);
+}
+
+// the persistent kernel without weight offsets, a predicate or earlier codes; the real-valued output (the plain launch) has the ring form too
+template <typename T, bool RQ>
+static void launch_persistent_plain(const LinearArgs& a, hipStream_t s, bool ring3) {
+  if constexpr (!RQ) {
+    if (ring3) return launch_persistent<T, false, false, false, false, true>(a, s);
+  }
+  launch_persistent<T, RQ, false, false>(a, s);
 }
 
 // the tile kernel by output container and epilogue. Defined behind linear_w8a8_impl only so that the code object stays comparable byte for
@@ -1194,7 +1362,11 @@ static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w
                             const float* out_scale, const float* out_offset, double out_num_bits, int y_dt, int64_t M,
                             int64_t N, int64_t K, void* workspace, size_t workspace_bytes, void* stream, const LinearOptions& o = {}) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool persistent = persistent_class(M, N, K), requant = out_scale != nullptr;
+  const bool requant = out_scale != nullptr;
+  const bool plain = !requant && !w_offset && !o.gate && !o.run_if && !o.earlier.codes;  // the instantiation without a table, extrema or a predicate
+  // (the seam lifts the tile floor only where the launch needs no workspace the floor's callers do not bring: the row sums come with the call)
+  const bool persistent = persistent_class(M, N, K) ||
+                          (plain && (ring3_form_forced() || two_slot_form_forced()) && persistent_kernel_can_run(M, N, K) && (!x_offset || w_rowsum));
   bool empty;
   if (int rc = check_extents(1, M, N, K, &empty); rc || empty) return rc;
   if (o.earlier.codes && (!o.earlier.scale || x_per_row || !aligned16(o.earlier.codes) || !persistent))
@@ -1268,6 +1440,10 @@ static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w
 #ifdef FFQ_I8_GROUP_COLS  // A/B builds (tools/build_variant.sh): column groups where the activation codes exceed ~200 MB
   if ((size_t)M * (size_t)K > ((size_t)200 << 20)) { a.group_cols = 1; a.group_m = FFQ_I8_GROUP_COLS; }
 #endif
+  const bool ring3 = ring3_form(M, N, K, plain, o.seg_count);
+#ifdef FFQ_RING3_GROUP_M  // A/B builds: the group height under the ring form
+  if (ring3) a.group_m = FFQ_RING3_GROUP_M;
+#endif
   if (o.gate) {  // bf16 out, no re-quantization (checked above); with or without weight offsets
     if (w_offset) launch_persistent<bf16_t, false, false, true, true>(a, s); else launch_persistent<bf16_t, false, false, false, true>(a, s);
     return check_launch("w8a8_gemm256fq_kernel (gated)");
@@ -1281,7 +1457,7 @@ static int linear_w8a8_impl(const int8_t* xq, const int8_t* wq, const int32_t* w
     if (e != hipSuccess) return fail(FFQ_ERR_LAUNCH, "hipMemsetAsync: %s", hipGetErrorString(e));
     a.woff_live = ws.flag;
   }
-#define FFQ_FQ(T, RQ) do { if (w_offset || o.run_if || o.earlier.codes) launch_persistent<T, RQ, false, true>(a, s); else launch_persistent<T, RQ, false, false>(a, s); } while (0)
+#define FFQ_FQ(T, RQ) do { if (w_offset || o.run_if || o.earlier.codes) launch_persistent<T, RQ, false, true>(a, s); else launch_persistent_plain<T, RQ>(a, s, ring3); } while (0)
   if (requant) {
     switch (out_dt) {
       case FFQ_I8: FFQ_FQ(int8_t, true); break;

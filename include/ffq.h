@@ -954,6 +954,10 @@ int ffq_attention(const void* q, const void* k, const void* v, int dt, int64_t b
  * bf16-image form of ffq_linear_wq / ffq_mlp_gate_up_wq to its 8-wave kernel instead of the one-wave-per-SIMD one (bit-equal results),
  * and plain launches of up to 512 rows to the 256-row tiles. Bit 1 (2): odd K slices of a split tile abandon their wait at once.
  * Bit 2 (4): the 128-column tiles (up to 512 rows) take their register-staged kernel instead of the LDS-DMA one (bit-equal results).
+ * Bit 3 (8): every plain launch of ffq_linear_w8a8 / ffq_linear_w8a8_multi (no output quantizer, no weight offsets) that the persistent
+ * int8 kernel can run at all (K % 128 == 0, K >= 256, M >= 128, N >= 128) takes its three-image ring form, whatever the contraction
+ * depth and the number of tiles (below 64 tiles: where the weight row sums come with the call or there is no activation offset, so that
+ * the launch needs no workspace); bit 4 (16): the same launches take its two-slot form (bit-equal results; bit 4 wins over bit 3).
  * Returns the previous setting. Process-wide; the library reads no environment variables.
  */
 int ffq_force_generic_kernels(int on);
