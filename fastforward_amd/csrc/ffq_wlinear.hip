@@ -38,6 +38,8 @@
 
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include <type_traits>
 
 #ifndef FFQ_WL_LOOP_MODE
@@ -1191,6 +1193,9 @@ int ffq::wq_cus() {
   return n;
 }
 
+// the queries answer "no split, no scratch" for what is no problem of the family (the entry points decline it: ffq_linear_wq_supported)
+static bool wq_is_problem(int64_t M, int64_t N, int64_t K) { return M > 0 && N > 0 && K >= 2 * WL_BK; }
+
 static int64_t wq_tiles(int64_t M, int64_t N, bool mlp) {
   return ((M + WL_BM - 1) / WL_BM) * (mlp ? N / 128 : (N + WL_BN - 1) / WL_BN);
 }
@@ -1225,6 +1230,11 @@ static int wq_split(int64_t M, int64_t N, int64_t K, bool mlp) {
   return best;
 }
 
+// one unit's partial accumulators per (tile of the last round, slice)
+static size_t wq_slab_bytes(int64_t M, int64_t N, int64_t split, bool mlp) {
+  return split > 1 ? (size_t)wq_tail_tiles(M, N, mlp) * (size_t)split * WL_UNIT_SLAB : 0;
+}
+
 // Which form a plain launch of M rows takes (ffq_wq.h): the skinny form up to FFQ_MID_MIN_M - 1 rows, the 128-column tiles of
 // ffq_wmid.hip up to 512, the 256-row tiles beyond (and for every gate+up+SiLU*up launch, and under the test hook). The skinny form
 // declines some storage forms (packing blocks other than 128, K % 128 != 0): such a launch takes the 128-column tiles, which cover
@@ -1236,26 +1246,41 @@ enum { WQ_FORM_TILES = 0, WQ_FORM_SKINNY = 1, WQ_FORM_MID = 2 };
 static bool wq_prefers_skinny(int64_t M, int64_t N, int64_t K) {
   return (M < FFQ_MID_MIN_M || (M <= 32 && N < 8192)) && wq_skinny_tickets(M, 128, K) > 0;
 }
-static int wq_plan_form(int64_t M, int64_t N, int64_t K, int mlp) {
+// The preference is a function of the problem and the test hook alone: the queries and the launch both read it here.
+static int wq_preferred_form(int64_t M, int64_t N, int64_t K, bool mlp) {
   if (mlp || generic_kernels_forced()) return WQ_FORM_TILES;
   if (wq_prefers_skinny(M, N, K)) return WQ_FORM_SKINNY;
-  if (wq_mid_prefers(M, N, K)) return WQ_FORM_MID;
-  return wq_skinny_tickets(M, 128, K) > 0 ? WQ_FORM_SKINNY : WQ_FORM_TILES;
+  return wq_mid_prefers(M, N, K) ? WQ_FORM_MID : WQ_FORM_TILES;
+}
+// The form that takes over where the preferred one declines the weight's storage or the list of matrices (wq_skinny_applies,
+// wq_mid_applies: only the launch knows those). Wherever the skinny form is preferred the 128-column tiles cover the shape (M <= 128 and
+// K % 128 == 0 lie within wq_mid_shape_ok and below its 256 rows); the 256-row tiles cover everything.
+static int wq_next_form(int form) { return form == WQ_FORM_SKINNY ? WQ_FORM_MID : WQ_FORM_TILES; }
+
+static int64_t wq_form_split(int form, int64_t M, int64_t N, int64_t K, bool mlp) {
+  switch (form) {
+    case WQ_FORM_SKINNY: return wq_skinny_split(M, N, K);
+    case WQ_FORM_MID: return wq_mid_split(M, N, K);
+    default: return wq_split(M, N, K, mlp);
+  }
+}
+
+static size_t wq_form_slab_bytes(int form, int64_t M, int64_t N, int64_t K, bool mlp, int64_t split) {
+  switch (form) {
+    case WQ_FORM_SKINNY: return wq_skinny_slab_bytes(M, N, K, split);
+    case WQ_FORM_MID: return wq_mid_slab_bytes(M, N, K, split);
+    default: return wq_slab_bytes(M, N, split, mlp);
+  }
 }
 
 extern "C" int64_t ffq_linear_wq_split(int64_t M, int64_t N, int64_t K, int mlp) {
-  if (M <= 0 || N <= 0 || K < 2 * WL_BK) return 1;
-  switch (wq_plan_form(M, N, K, mlp)) {
-    case WQ_FORM_SKINNY: return wq_skinny_split(M, N, K);
-    case WQ_FORM_MID: return wq_mid_split(M, N, K);
-    default: return wq_split(M, N, K, mlp != 0);
-  }
+  return wq_is_problem(M, N, K) ? wq_form_split(wq_preferred_form(M, N, K, mlp != 0), M, N, K, mlp != 0) : 1;
 }
 
 // int32 counters the split-K exchange needs (0 = none): zero before the first launch that uses them, left zero by every launch — a
 // caller keeps ONE zeroed buffer per stream and never touches it. An upper bound over the forms the launch can take.
 extern "C" int64_t ffq_linear_wq_tickets(int64_t M, int64_t N, int64_t K, int mlp) {
-  if (M <= 0 || N <= 0 || K < 2 * WL_BK) return 0;
+  if (!wq_is_problem(M, N, K)) return 0;
   int64_t n = 2 * wq_tail_tiles(M, N, mlp != 0);
   if (!mlp) {
     const int64_t sk = wq_skinny_tickets(M, N, K), md = wq_mid_tickets(M, N, K);
@@ -1266,67 +1291,56 @@ extern "C" int64_t ffq_linear_wq_tickets(int64_t M, int64_t N, int64_t K, int ml
 }
 
 // bytes of partial-sum slabs a launch with `split` K slices needs at the front of its workspace (0: none). `split` = the value of
-// ffq_linear_wq_split (the plan) also covers the plan of the form that takes over where the preferred one declines the storage.
+// ffq_linear_wq_split (the plan) also covers the plan of the form that takes over where the skinny one declines the storage.
 extern "C" size_t ffq_linear_wq_slab_bytes(int64_t M, int64_t N, int64_t K, int mlp, int64_t split) {
-  if (M <= 0 || N <= 0 || K < 2 * WL_BK) return 0;
-  switch (wq_plan_form(M, N, K, mlp)) {
-    case WQ_FORM_SKINNY: {
-      size_t bytes = wq_skinny_slab_bytes(M, N, K, split);
-      if (wq_mid_prefers(M, N, K)) {
-        const size_t md = wq_mid_slab_bytes(M, N, K, split == wq_skinny_split(M, N, K) ? wq_mid_split(M, N, K) : split);
-        bytes = bytes > md ? bytes : md;
-      }
-      return bytes;
-    }
-    case WQ_FORM_MID: return wq_mid_slab_bytes(M, N, K, split);
-    default: return split <= 1 ? 0 : (size_t)wq_tail_tiles(M, N, mlp != 0) * (size_t)split * WL_UNIT_SLAB;
+  if (!wq_is_problem(M, N, K)) return 0;
+  const int form = wq_preferred_form(M, N, K, mlp != 0);
+  size_t bytes = wq_form_slab_bytes(form, M, N, K, mlp != 0, split);
+  if (form == WQ_FORM_SKINNY) {
+    const int next = wq_next_form(form);
+    const int64_t theirs = split == wq_form_split(form, M, N, K, false) ? wq_form_split(next, M, N, K, false) : split;
+    const size_t more = wq_form_slab_bytes(next, M, N, K, false, theirs);
+    bytes = bytes > more ? bytes : more;
   }
+  return bytes;
 }
 
-static size_t wq_slab_bytes(int64_t M, int64_t N, int split, bool mlp) {
-  return split > 1 ? (size_t)wq_tail_tiles(M, N, mlp) * (size_t)split * WL_UNIT_SLAB : 0;
-}
-
-// Where the two-pass form (A2 of the whole weight into a bf16 image, then the one-wave-per-SIMD GEMM) is the plan of a plain launch: from
-// 4096 tokens on, and from 1536 on where the 256 x 256 tiles make at least 144 — A2 costs N K 3 bytes whatever M is (26 % of the GEMM
+// Where the two-pass form (A2 of the whole weight into a bf16 image, then the one-wave-per-SIMD GEMM) is the plan: from 4096 tokens on,
+// and for a plain launch from 1536 on where the 256 x 256 tiles make at least 144 — A2 costs N K 3 bytes whatever M is (26 % of the GEMM
 // at 1536 tokens), the one-pass loop is ~25 % slower than the image loop, and below ~half a round of tiles the one-pass form's K split
 // is what fills the chip. Round 6 (profiles/r06_wq_twopass_sweep.txt, 8B shapes): q/k/v as one launch (N = 6144) at 1536 / 2048 / 3072
 // tokens 0.85 / 0.89 / 0.97 of the one-pass time, o_proj / down_proj at 3072 0.81 / 0.79; at 2048 (128 tiles) down_proj is 1.09: one-pass.
-static bool wq_two_pass_planned(int64_t M, int64_t N) {
+static bool wq_two_pass_planned(int64_t M, int64_t N, bool mlp) {
   if (M >= WL_TWO_PASS_MIN_TOKENS) return true;
-  return M >= 1536 && ((M + WL_BM - 1) / WL_BM) * ((N + WL_BN - 1) / WL_BN) >= 144;
+  return !mlp && M >= 1536 && wq_tiles(M, N, false) >= 144;
 }
 
 // workspace: [split-K slabs of the library's plan | bf16 image(s) of the two-pass form (A2 of the whole weight, then the GEMM on
-// that image): N * K * 2 bytes where wq_two_pass_planned]. The caller may pass less (or NULL): the launch then runs without the part
-// that does not fit (no split / conversion inside the GEMM) — never fails for lack of scratch.
-extern "C" size_t ffq_linear_wq_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || K < 2 * WL_BK) return 0;
-  if (wq_plan_form(M, N, K, 0) != WQ_FORM_TILES) return ffq_linear_wq_slab_bytes(M, N, K, 0, ffq_linear_wq_split(M, N, K, 0));
-  return wq_slab_bytes(M, N, wq_split(M, N, K, false), false) + (wq_two_pass_planned(M, N) ? (size_t)N * (size_t)K * 2u : 0);
+// that image): N * K * 2 bytes per matrix where wq_two_pass_planned (only the 256-row tiles see that many rows)]. The caller may pass
+// less (or NULL): the launch then runs without the part that does not fit (no split / conversion inside the GEMM) — never fails for
+// lack of scratch.
+static size_t wq_workspace_bytes(int64_t M, int64_t N, int64_t K, bool mlp) {
+  if (!wq_is_problem(M, N, K)) return 0;
+  const size_t images = wq_two_pass_planned(M, N, mlp) ? (size_t)(mlp ? 2 : 1) * (size_t)N * (size_t)K * 2u : 0;
+  return ffq_linear_wq_slab_bytes(M, N, K, mlp, ffq_linear_wq_split(M, N, K, mlp)) + images;
 }
 
-// resolves (requested split, scratch on offer) into what the launch uses; returns the bytes the slabs take at the front of `workspace`
-static size_t wq_resolve_split(WLinearArgs& a, int64_t split_request, bool mlp, void* workspace, size_t workspace_bytes, int32_t* tickets, int* rc) {
-  *rc = FFQ_OK;
+extern "C" size_t ffq_linear_wq_workspace_bytes(int64_t M, int64_t N, int64_t K) { return wq_workspace_bytes(M, N, K, false); }
+
+// the 256-row tiles: resolves (requested split, scratch on offer) into what the launch uses; `slab_bytes`: what the slabs take at the
+// front of `workspace`
+static int wq_resolve_split(WLinearArgs& a, int64_t split_request, bool mlp, void* workspace, size_t workspace_bytes, int32_t* tickets, size_t* slab_bytes) {
   const int most = wq_max_split(a.M, a.N, a.K, mlp);
-  if (split_request > most) {
-    *rc = fail(FFQ_ERR_ARG, "weight-only linear: split %lld exceeds %d (the units of the last round must be resident at once: tail tiles * split <= CUs, K / 64 >= 2 * split)", (long long)split_request, most);
-    return 0;
-  }
-  int split = split_request > 0 ? (int)split_request : wq_split(a.M, a.N, a.K, mlp);
-  size_t slab = wq_slab_bytes(a.M, a.N, split, mlp);
-  if (split > 1 && (!tickets || !workspace || workspace_bytes < slab || !aligned16(workspace))) {
-    if (split_request > 1) { *rc = fail(FFQ_ERR_ARG, "weight-only linear: split %d needs %zu bytes of workspace and a ticket buffer", split, slab); return 0; }
-    split = 1; slab = 0;  // the plan is a preference: without scratch every tile is one unit
-  }
+  if (split_request > most)
+    return fail(FFQ_ERR_ARG, "weight-only linear: split %lld exceeds %d (the units of the last round must be resident at once: tail tiles * split <= CUs, K / 64 >= 2 * split)", (long long)split_request, most);
+  const int64_t split = split_request > 0 ? split_request : wq_split(a.M, a.N, a.K, mlp);
+  const size_t slab = wq_slab_bytes(a.M, a.N, split, mlp);
+  if (int rc = wq_take_split("", split_request > 0, split, slab, workspace, workspace_bytes, tickets, &a.split, &a.slabs, &a.tickets)) return rc;
+  *slab_bytes = a.split > 1 ? slab : 0;  // without scratch every tile is one unit
   const int64_t tiles = wq_tiles(a.M, a.N, mlp);
-  a.split = split;
-  a.full_tiles = (int)(split > 1 ? tiles - wq_tail_tiles(a.M, a.N, mlp) : tiles);
-  a.slabs = split > 1 ? static_cast<float*>(workspace) : nullptr;
-  a.tickets = split > 1 ? tickets : nullptr;
+  a.full_tiles = (int)(a.split > 1 ? tiles - wq_tail_tiles(a.M, a.N, mlp) : tiles);
   a.abandon_test = splitk_abandon_forced() ? 1 : 0;
-  return slab;
+  return FFQ_OK;
 }
 
 template <int BKIND, bool GROUPED, bool OFFSET, typename TOut, bool MLP = false>
@@ -1375,41 +1389,137 @@ static bool wq_takes_4w(const WLinearArgs& a, bool mlp = false) {
 #endif
 }
 
-template <int BKIND, bool MLP = false>
-static void wq_dispatch(const WLinearArgs& a, bool grouped, bool offset, hipStream_t s) {
-  if constexpr (BKIND == WL_B_BF16) {
+// the 8-wave kernel into the output's dtype (the gate+up+SiLU*up launch writes bf16 only)
+template <int BKIND, bool GROUPED, bool OFFSET, bool MLP>
+static void wq_launch_out(const WLinearArgs& a, hipStream_t s) {
+  if (MLP || a.out_dt == FFQ_BF16) wq_launch<BKIND, GROUPED, OFFSET, bf16_t, MLP>(a, s);
+  else if constexpr (!MLP) wq_launch<BKIND, GROUPED, OFFSET, float, false>(a, s);
+}
+
+// `image`: the weight operand is the two-pass form's bf16 image; else the codes of container `w_dt`, converted inside the GEMM
+template <bool MLP>
+static void wq_dispatch(const WLinearArgs& a, bool image, int w_dt, hipStream_t s) {
+  if (image) {
     if (wq_takes_4w(a, MLP)) wq_launch4w<MLP>(a, s);
-    else if (MLP || a.out_dt == FFQ_BF16) wq_launch<BKIND, false, false, bf16_t, MLP>(a, s);
-    else if constexpr (!MLP) wq_launch<BKIND, false, false, float, false>(a, s);
-  } else {
-#define FFQ_WL_T(G, O) do { if (MLP || a.out_dt == FFQ_BF16) wq_launch<BKIND, G, O, bf16_t, MLP>(a, s); else if constexpr (!MLP) wq_launch<BKIND, G, O, float, false>(a, s); } while (0)
-    if (grouped) { if (offset) FFQ_WL_T(true, true); else FFQ_WL_T(true, false); }
-    else { if (offset) FFQ_WL_T(false, true); else FFQ_WL_T(false, false); }
-#undef FFQ_WL_T
+    else wq_launch_out<WL_B_BF16, false, false, MLP>(a, s);
+    return;
   }
+  wq_visit_storage(w_dt, a.groups > 1, a.w_offset != nullptr, [&](auto kind, auto grouped, auto offset) {
+    wq_launch_out<kind(), grouped(), offset(), MLP>(a, s);
+  });
+}
+
+// ---- the argument checks the three entry points share (each runs them in its own order, between its own) ------------------------------
+static int check_supported(int x_dt, int w_dt, int out_dt, int64_t M, int64_t N, int64_t K, int64_t group, int64_t pack_block) {
+  if (ffq_linear_wq_supported(x_dt, w_dt, out_dt, M, N, K, group, pack_block)) return FFQ_OK;
+  return fail(FFQ_ERR_DTYPE, "weight-only linear: needs bf16 activations, int8-container or packed 4-bit codes, bf16 / f32 output, K %% 64 == 0, K >= 128 and groups of a multiple of 64 input channels");
+}
+
+static int check_aligned(std::initializer_list<const void*> buffers) {
+  for (const void* p : buffers)
+    if (!aligned16(p)) return fail(FFQ_ERR_DTYPE, "weight-only linear needs 16-byte aligned buffers");
+  return FFQ_OK;
+}
+
+static int check_parameters(int64_t scale_numel, int64_t N, int64_t groups) {
+  if (!(scale_numel == 1 || scale_numel == N * groups))
+    return fail(FFQ_ERR_PARAM_NUMEL, "weight-only linear: %lld parameters for %lld x %lld tiles", (long long)scale_numel, (long long)N, (long long)groups);
+  if (scale_numel == 1 && groups != 1) return fail(FFQ_ERR_PARAM_NUMEL, "one parameter pair needs group == K");
+  return FFQ_OK;
+}
+
+// ---- the launch arguments ---------------------------------------------------------------------------------------------------------------
+// what every launch fills alike: no bias, no second or further matrix; the matrices' own fields are the entry point's
+static WLinearArgs wq_args(const void* x, void* out, int out_dt, int64_t M, int64_t N, int64_t K, int64_t group, int per_row, int64_t pack_block, bool mlp) {
+  WLinearArgs a{};
+  a.x = static_cast<const uint8_t*>(x);
+  a.out = out; a.out_dt = out_dt;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.seg_n[0] = (int)N;
+  a.seg_tile[0] = a.seg_tile[1] = INT32_MAX;
+  a.groups = (int)(K / group);
+  a.steps_per_group = (int)(group / WL_BK);
+  a.per_row = per_row;
+  for (int64_t b = pack_block; b > 1; b >>= 1) ++a.pack_shift;
+  a.tiles_m = (int)((M + WL_BM - 1) / WL_BM);
+  a.tiles_n = (int)(mlp ? N / 128 : (N + WL_BN - 1) / WL_BN);
+  a.group_m = K >= 4096 ? 4 : WL_GROUP_M;  // row tiles whose A panels (256 x 2 K bytes each) a group's column tiles share in their XCD's L2
+  // gate + up: both weight images together (2 N K x 2 B) against the activations (M K x 2 B): re-read the smaller one per group
+  a.group_cols = mlp && 2 * N > M ? 1 : 0;
+#ifdef FFQ_EXPERIMENTS  // tuning builds only (tools/): the shipped library reads no environment
+  if (const char* gm = getenv("FFQ_WQ_GROUP_M")) a.group_m = atoi(gm);
+  if (const char* gc = getenv("FFQ_WQ_GROUP_COLS")) a.group_cols = atoi(gc);
+#endif
+  return a;
+}
+
+// The two-pass form's first pass: A2 of `count` weight matrices of rows[i] x K codes into bf16 images, one behind the other from `image`
+// on; images[i] = where matrix i went. FFQ_ERR_DTYPE: a tiling the stand-alone dequantize kernels decline.
+static int wq_build_images(int count, const void* const* codes, int w_dt, int64_t pack_block, const float* const* scale, const float* const* offset,
+                           int per_row, int64_t group, const int64_t* rows, int64_t K, uint8_t* image, const uint8_t** images, void* stream) {
+  int rc = FFQ_OK;
+  for (int i = 0; i < count && rc == FFQ_OK; ++i) {
+    ffq_tiling t;
+    t.ndim = 2;
+    t.shape[0] = rows[i]; t.shape[1] = K;
+    t.tile[0] = per_row ? 1 : rows[i]; t.tile[1] = per_row ? group : K;
+    const int64_t numel = per_row ? rows[i] * (K / group) : 1;
+    if (w_dt == FFQ_U8)
+      rc = ffq_unpack_dequantize_int4(static_cast<const uint8_t*>(codes[i]), scale[i], numel, offset[i], offset[i] ? numel : 0, &t, pack_block, image, FFQ_BF16, stream);
+    else
+      rc = ffq_dequantize_by_tile(codes[i], FFQ_I8, scale[i], FFQ_F32, numel, offset[i], FFQ_F32, offset[i] ? numel : 0, &t, image, FFQ_BF16, stream);
+    images[i] = image;
+    image += (size_t)rows[i] * (size_t)K * 2u;
+  }
+  return rc;
+}
+
+// The launch on the 256-row tiles, behind the entry point's checks: `a` describes `count` matrices of rows[i] x K codes (MLP: gate, up).
+template <bool MLP>
+static int wq_tiles_launch(WLinearArgs& a, int count, const void* const* codes, int w_dt, int64_t pack_block, const float* const* scale,
+                           const float* const* offset, int64_t group, const int64_t* rows, void* workspace, size_t workspace_bytes, int32_t* tickets,
+                           int64_t split, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  size_t slab_bytes, image_bytes = 0;
+  if (int rc = wq_resolve_split(a, split, MLP, workspace, workspace_bytes, tickets, &slab_bytes)) return rc;
+  for (int i = 0; i < count; ++i) image_bytes += (size_t)rows[i] * (size_t)a.K * 2u;
+  uint8_t* image = workspace ? static_cast<uint8_t*>(workspace) + slab_bytes : nullptr;  // the image(s) (if any) lie behind the slabs
+  if (image && workspace_bytes >= slab_bytes + image_bytes && aligned16(image)) {  // the caller offered the images' scratch (ffq_linear_wq_workspace_bytes: from 4096 tokens on)
+    // two-pass form: A2 of the whole weight once (3 or 2.5 B/elem, ~2 % of the GEMM at 16 k tokens), then the GEMM with both
+    // operands by LDS-DMA — no conversion work per row tile
+    const uint8_t* images[3] = {nullptr, nullptr, nullptr};
+    const int rc = wq_build_images(count, codes, w_dt, pack_block, scale, offset, a.per_row, group, rows, a.K, image, images, stream);
+    if (rc == FFQ_OK) {
+      a.w = images[0];
+      if constexpr (MLP) a.w2 = images[1];
+      else for (int i = 1; i < count; ++i) a.seg_w[i - 1] = images[i];
+      // Activations that do not fit the 256 MiB Infinity Cache (down_proj at 16 k tokens: 470 MB) must come from HBM ONCE: groups of 8
+      // COLUMN tiles x all row tiles make the XCDs stream the same row panels at the same time (one HBM read, the other XCDs hit the
+      // Infinity Cache) and keep their column panels resident, where row groups give every XCD its own rows and read them once per
+      // batch of column tiles (round-4 A/B on one box, one-wave-per-SIMD kernel: down_proj 1.36 -> 1.42 PFLOP/s; q/o ±0, gate/up -1.3 %)
+      if (!MLP && count == 1 && (size_t)a.M * (size_t)a.K * 2u > ((size_t)200 << 20) && wq_takes_4w(a)) { a.group_cols = 1; a.group_m = 8; }
+      wq_dispatch<MLP>(a, true, w_dt, s);
+      return check_launch(MLP ? "wq_gemm256_kernel (mlp mode, bf16 images)" : "wq_gemm256_kernel (bf16 image)");
+    }
+    if (rc != FFQ_ERR_DTYPE) return rc;  // a tiling the stand-alone dequantize kernels decline: the one-pass kernel below covers it
+  }
+  wq_dispatch<MLP>(a, false, w_dt, s);
+  return check_launch(MLP ? "wq_gemm256_kernel (mlp mode)" : "wq_gemm256_kernel");
 }
 
 // `count` weight matrices side by side along N on the same activations (count == 1: ffq_linear_wq)
-static int wq_linear_impl(const void* x, int x_dt, int count, const void* const* w_codes, int w_dt, int64_t pack_block, const float* const* w_scale,
+static int wq_linear_impl(const void* x, int count, const void* const* w_codes, int w_dt, int64_t pack_block, const float* const* w_scale,
                           const float* const* w_offset, int per_row, int64_t group, const void* bias, int bias_dt, void* const* outs,
                           int out_dt, int64_t M, const int64_t* Ns, int64_t K, void* workspace, size_t workspace_bytes, int32_t* tickets,
                           int64_t split, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   int64_t N = 0;
   for (int i = 0; i < count; ++i) N += Ns[i];
-  const int64_t groups = K / group;
-
-  WLinearArgs a;
-  a.x = static_cast<const uint8_t*>(x);
+  WLinearArgs a = wq_args(x, outs[0], out_dt, M, N, K, group, per_row, pack_block, false);
   a.w = static_cast<const uint8_t*>(w_codes[0]);
   a.w_scale = w_scale[0]; a.w_offset = w_offset[0];
-  a.w2 = nullptr; a.w_scale2 = nullptr; a.w_offset2 = nullptr;
   a.bias = bias; a.bias_dt = bias_dt;
-  a.out = outs[0]; a.out_dt = out_dt;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.seg_n[0] = (int)Ns[0]; a.seg_n[1] = a.seg_n[2] = 0;
-  a.seg_tile[0] = a.seg_tile[1] = INT32_MAX;
-  for (int i = 0; i < 2; ++i) { a.seg_w[i] = nullptr; a.seg_scale[i] = nullptr; a.seg_offset[i] = nullptr; a.seg_out[i] = nullptr; }
+  a.seg_n[0] = (int)Ns[0];
   int64_t tile_edge = 0;
   for (int i = 1; i < count; ++i) {
     tile_edge += Ns[i - 1] / WL_BN;
@@ -1419,65 +1529,14 @@ static int wq_linear_impl(const void* x, int x_dt, int count, const void* const*
     a.seg_out[i - 1] = outs[i];
     a.seg_n[i] = (int)Ns[i];
   }
-  a.groups = (int)groups;
-  a.steps_per_group = (int)(group / WL_BK);
-  a.per_row = per_row;
-  a.pack_shift = 0;
-  for (int64_t b = pack_block; b > 1; b >>= 1) ++a.pack_shift;
-  a.tiles_m = (int)((M + WL_BM - 1) / WL_BM);
-  a.tiles_n = (int)((N + WL_BN - 1) / WL_BN);
-  a.group_m = K >= 4096 ? 4 : WL_GROUP_M;  // row tiles whose A panels (256 x 2 K bytes each) a group's column tiles share in their XCD's L2
-  a.group_cols = 0;
-#ifdef FFQ_EXPERIMENTS  // tuning builds only (tools/): the shipped library reads no environment
-  if (const char* gm = getenv("FFQ_WQ_GROUP_M")) a.group_m = atoi(gm);
-  if (const char* gc = getenv("FFQ_WQ_GROUP_COLS")) a.group_cols = atoi(gc);
-#endif
-  const bool grouped = groups > 1, offset = w_offset[0] != nullptr;
+  int form = wq_preferred_form(M, N, K, false);
+  if (form == WQ_FORM_SKINNY && !wq_skinny_applies(a, pack_block)) form = wq_next_form(form);
+  if (form == WQ_FORM_MID && !wq_mid_applies(a)) form = wq_next_form(form);
   // few rows: the contraction is a stream over the codes, bounded by HBM — 16-row MFMA tiles, no padding to 256 rows (ffq_wskinny.hip)
-  if (wq_prefers_skinny(M, N, K) && wq_skinny_applies(a, pack_block)) return wq_skinny_launch(a, w_dt, pack_block, group, split, workspace, workspace_bytes, tickets, s);
+  if (form == WQ_FORM_SKINNY) return wq_skinny_launch(a, w_dt, group, split, workspace, workspace_bytes, tickets, s);
   // a few hundred rows (and the storage forms the skinny kernel declines): 128-column tiles, codes converted once per block (ffq_wmid.hip)
-  if (wq_mid_prefers(M, N, K) && wq_mid_applies(a)) return wq_mid_launch(a, w_dt, group, split, workspace, workspace_bytes, tickets, s);
-  int rc_split;
-  const size_t slab_bytes = wq_resolve_split(a, split, false, workspace, workspace_bytes, tickets, &rc_split);
-  if (rc_split != FFQ_OK) return rc_split;
-  workspace = workspace ? static_cast<uint8_t*>(workspace) + slab_bytes : nullptr;  // the image(s) (if any) lie behind the slabs
-  workspace_bytes = workspace_bytes > slab_bytes ? workspace_bytes - slab_bytes : 0;
-  const size_t image_bytes = (size_t)N * (size_t)K * 2u;
-  if (workspace && workspace_bytes >= image_bytes && aligned16(workspace)) {  // the caller offered the image's scratch (ffq_linear_wq_workspace_bytes: from 4096 tokens on)
-    // two-pass form: A2 of the whole weight once (3 or 2.5 B/elem, ~2 % of the GEMM at 16 k tokens), then the GEMM with both
-    // operands by LDS-DMA — no conversion work per row tile
-    uint8_t* image = static_cast<uint8_t*>(workspace);
-    int rc = FFQ_OK;
-    const uint8_t* images[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < count && rc == FFQ_OK; ++i) {
-      ffq_tiling t;
-      t.ndim = 2;
-      t.shape[0] = Ns[i]; t.shape[1] = K;
-      t.tile[0] = per_row ? 1 : Ns[i]; t.tile[1] = per_row ? group : K;
-      const int64_t numel = per_row ? Ns[i] * groups : 1;
-      if (w_dt == FFQ_U8)
-        rc = ffq_unpack_dequantize_int4(static_cast<const uint8_t*>(w_codes[i]), w_scale[i], numel, w_offset[i], w_offset[i] ? numel : 0, &t, pack_block, image, FFQ_BF16, stream);
-      else
-        rc = ffq_dequantize_by_tile(w_codes[i], FFQ_I8, w_scale[i], FFQ_F32, numel, w_offset[i], FFQ_F32, w_offset[i] ? numel : 0, &t, image, FFQ_BF16, stream);
-      images[i] = image;
-      image += (size_t)Ns[i] * (size_t)K * 2u;
-    }
-    if (rc == FFQ_OK) {
-      a.w = images[0];
-      for (int i = 1; i < count; ++i) a.seg_w[i - 1] = images[i];
-      // Activations that do not fit the 256 MiB Infinity Cache (down_proj at 16 k tokens: 470 MB) must come from HBM ONCE: groups of 8
-      // COLUMN tiles x all row tiles make the XCDs stream the same row panels at the same time (one HBM read, the other XCDs hit the
-      // Infinity Cache) and keep their column panels resident, where row groups give every XCD its own rows and read them once per
-      // batch of column tiles (round-4 A/B on one box, one-wave-per-SIMD kernel: down_proj 1.36 -> 1.42 PFLOP/s; q/o ±0, gate/up -1.3 %)
-      if (count == 1 && (size_t)M * (size_t)K * 2u > ((size_t)200 << 20) && wq_takes_4w(a)) { a.group_cols = 1; a.group_m = 8; }
-      wq_dispatch<WL_B_BF16>(a, false, false, s);
-      return check_launch("wq_gemm256_kernel (bf16 image)");
-    }
-    if (rc != FFQ_ERR_DTYPE) return rc;  // a tiling the stand-alone dequantize kernels decline: the one-pass kernel below covers it
-  }
-  if (w_dt == FFQ_U8) wq_dispatch<WL_B_I4>(a, grouped, offset, s);
-  else wq_dispatch<WL_B_I8>(a, grouped, offset, s);
-  return check_launch("wq_gemm256_kernel");
+  if (form == WQ_FORM_MID) return wq_mid_launch(a, w_dt, group, split, workspace, workspace_bytes, tickets, s);
+  return wq_tiles_launch<false>(a, count, w_codes, w_dt, pack_block, w_scale, w_offset, group, Ns, workspace, workspace_bytes, tickets, split, stream);
 }
 
 extern "C" int ffq_linear_wq(const void* x, int x_dt, const void* w_codes, int w_dt, int64_t pack_block, const float* w_scale,
@@ -1487,15 +1546,11 @@ extern "C" int ffq_linear_wq(const void* x, int x_dt, const void* w_codes, int w
   if (M < 0 || N < 0 || K < 0 || split < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (M == 0 || N == 0) return FFQ_OK;
   if (!x || !w_codes || !w_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!ffq_linear_wq_supported(x_dt, w_dt, out_dt, M, N, K, group, pack_block))
-    return fail(FFQ_ERR_DTYPE, "weight-only linear: needs bf16 activations, int8-container or packed 4-bit codes, bf16 / f32 output, K %% 64 == 0, K >= 128 and groups of a multiple of 64 input channels");
-  if (!aligned16(x) || !aligned16(w_codes) || !aligned16(out)) return fail(FFQ_ERR_DTYPE, "weight-only linear needs 16-byte aligned buffers");
+  if (int rc = check_supported(x_dt, w_dt, out_dt, M, N, K, group, pack_block)) return rc;
+  if (int rc = check_aligned({x, w_codes, out})) return rc;
   if (bias && !dt_valid(bias_dt)) return fail(FFQ_ERR_ARG, "bad bias dtype");
-  const int64_t groups = K / group;
-  if (!(scale_numel == 1 || scale_numel == N * groups))
-    return fail(FFQ_ERR_PARAM_NUMEL, "weight-only linear: %lld parameters for %lld x %lld tiles", (long long)scale_numel, (long long)N, (long long)groups);
-  if (scale_numel == 1 && groups != 1) return fail(FFQ_ERR_PARAM_NUMEL, "one parameter pair needs group == K");
-  return wq_linear_impl(x, x_dt, 1, &w_codes, w_dt, pack_block, &w_scale, &w_offset, scale_numel != 1, group, bias, bias_dt, &out, out_dt, M, &N, K,
+  if (int rc = check_parameters(scale_numel, N, K / group)) return rc;
+  return wq_linear_impl(x, 1, &w_codes, w_dt, pack_block, &w_scale, &w_offset, scale_numel != 1, group, bias, bias_dt, &out, out_dt, M, &N, K,
                         workspace, workspace_bytes, tickets, split, stream);
 }
 
@@ -1517,99 +1572,43 @@ extern "C" int ffq_linear_wq_multi(const void* x, int x_dt, int count, const voi
     if (i + 1 < count && Ns[i] % WL_BN != 0) return fail(FFQ_ERR_DTYPE, "every weight matrix but the last needs a multiple of 256 rows");
     if (!w_codes[i] || !w_scale[i] || !outs[i]) return fail(FFQ_ERR_ARG, "NULL buffer");
     if ((w_offset[i] == nullptr) != (w_offset[0] == nullptr)) return fail(FFQ_ERR_ARG, "offsets for all weight matrices or for none");
-    if (!aligned16(w_codes[i]) || !aligned16(outs[i])) return fail(FFQ_ERR_DTYPE, "weight-only linear needs 16-byte aligned buffers");
+    if (int rc = check_aligned({w_codes[i], outs[i]})) return rc;
     N += Ns[i];
   }
   if (M == 0) return FFQ_OK;
   if (!x || !aligned16(x)) return fail(FFQ_ERR_ARG, "NULL or misaligned activations");
-  if (!ffq_linear_wq_supported(x_dt, w_dt, out_dt, M, N, K, group, pack_block))
-    return fail(FFQ_ERR_DTYPE, "weight-only linear: needs bf16 activations, int8-container or packed 4-bit codes, bf16 / f32 output, K %% 64 == 0, K >= 128 and groups of a multiple of 64 input channels");
+  if (int rc = check_supported(x_dt, w_dt, out_dt, M, N, K, group, pack_block)) return rc;
   if (!per_row && group != K) return fail(FFQ_ERR_PARAM_NUMEL, "one parameter pair per matrix needs group == K");
-  return wq_linear_impl(x, x_dt, count, w_codes, w_dt, pack_block, w_scale, w_offset, per_row, group, nullptr, 0, outs, out_dt, M, Ns, K, workspace,
+  return wq_linear_impl(x, count, w_codes, w_dt, pack_block, w_scale, w_offset, per_row, group, nullptr, 0, outs, out_dt, M, Ns, K, workspace,
                         workspace_bytes, tickets, split, stream);
 }
 
 // ---- gate_proj + up_proj + SiLU * up of a weight-only quantized MLP in one launch ---------------------------------------------------
 // workspace: [split-K slabs of the library's plan | the bf16 images of BOTH matrices (two-pass form, from 4096 tokens on)]
 extern "C" size_t ffq_mlp_gate_up_wq_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || N % 128 != 0 || K < 2 * WL_BK) return 0;
-  return wq_slab_bytes(M, N, wq_split(M, N, K, true), true) + (M >= WL_TWO_PASS_MIN_TOKENS ? (size_t)2 * (size_t)N * (size_t)K * 2u : 0);
+  return N % 128 == 0 ? wq_workspace_bytes(M, N, K, true) : 0;
 }
 
 extern "C" int ffq_mlp_gate_up_wq(const void* x, int x_dt, const void* gate_codes, const void* up_codes, int w_dt, int64_t pack_block,
                                   const float* gate_scale, const float* gate_offset, const float* up_scale, const float* up_offset,
                                   int64_t scale_numel, int64_t group, void* out, int64_t M, int64_t N, int64_t K, void* workspace,
                                   size_t workspace_bytes, int32_t* tickets, int64_t split, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
   if (M < 0 || N < 0 || K < 0 || split < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (M == 0 || N == 0) return FFQ_OK;
   if (!x || !gate_codes || !up_codes || !gate_scale || !up_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
   if ((gate_offset == nullptr) != (up_offset == nullptr)) return fail(FFQ_ERR_ARG, "gate and up need offsets both or neither");
   if (N % 128 != 0 || !ffq_linear_wq_supported(x_dt, w_dt, FFQ_BF16, M, N, K, group, pack_block))
     return fail(FFQ_ERR_DTYPE, "fused weight-only gate/up: needs N %% 128 == 0 and what ffq_linear_wq needs");
-  if (!aligned16(x) || !aligned16(gate_codes) || !aligned16(up_codes) || !aligned16(out)) return fail(FFQ_ERR_DTYPE, "weight-only linear needs 16-byte aligned buffers");
-  const int64_t groups = K / group;
-  if (!(scale_numel == 1 || scale_numel == N * groups))
-    return fail(FFQ_ERR_PARAM_NUMEL, "weight-only linear: %lld parameters for %lld x %lld tiles", (long long)scale_numel, (long long)N, (long long)groups);
-  if (scale_numel == 1 && groups != 1) return fail(FFQ_ERR_PARAM_NUMEL, "one parameter pair needs group == K");
+  if (int rc = check_aligned({x, gate_codes, up_codes, out})) return rc;
+  if (int rc = check_parameters(scale_numel, N, K / group)) return rc;
 
-  WLinearArgs a;
-  a.x = static_cast<const uint8_t*>(x);
+  WLinearArgs a = wq_args(x, out, FFQ_BF16, M, N, K, group, scale_numel != 1, pack_block, true);
   a.w = static_cast<const uint8_t*>(gate_codes); a.w2 = static_cast<const uint8_t*>(up_codes);
   a.w_scale = gate_scale; a.w_offset = gate_offset;
   a.w_scale2 = up_scale; a.w_offset2 = up_offset;
-  a.bias = nullptr; a.bias_dt = 0;
-  a.out = out; a.out_dt = FFQ_BF16;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.seg_n[0] = (int)N; a.seg_n[1] = a.seg_n[2] = 0;
-  a.seg_tile[0] = a.seg_tile[1] = INT32_MAX;
-  for (int i = 0; i < 2; ++i) { a.seg_w[i] = nullptr; a.seg_scale[i] = nullptr; a.seg_offset[i] = nullptr; a.seg_out[i] = nullptr; }
-  a.groups = (int)groups;
-  a.steps_per_group = (int)(group / WL_BK);
-  a.per_row = scale_numel != 1;
-  a.pack_shift = 0;
-  for (int64_t b = pack_block; b > 1; b >>= 1) ++a.pack_shift;
-  a.tiles_m = (int)((M + WL_BM - 1) / WL_BM);
-  a.tiles_n = (int)(N / 128);
-  a.group_m = K >= 4096 ? 4 : WL_GROUP_M;
-  // both weight images together (2 N K x 2 B) against the activations (M K x 2 B): re-read the smaller one per group
-  a.group_cols = 2 * N > M ? 1 : 0;
-#ifdef FFQ_EXPERIMENTS
-  if (const char* gm = getenv("FFQ_WQ_GROUP_M")) a.group_m = atoi(gm);
-  if (const char* gc = getenv("FFQ_WQ_GROUP_COLS")) a.group_cols = atoi(gc);
-#endif
-  const bool grouped = groups > 1, offset = gate_offset != nullptr;
-  int rc_split;
-  const size_t slab_bytes = wq_resolve_split(a, split, true, workspace, workspace_bytes, tickets, &rc_split);
-  if (rc_split != FFQ_OK) return rc_split;
-  workspace = workspace ? static_cast<uint8_t*>(workspace) + slab_bytes : nullptr;
-  workspace_bytes = workspace_bytes > slab_bytes ? workspace_bytes - slab_bytes : 0;
-
-  const size_t image_bytes = (size_t)N * (size_t)K * 2u;
-  if (workspace && workspace_bytes >= 2 * image_bytes && aligned16(workspace)) {
-    ffq_tiling t;
-    t.ndim = 2;
-    t.shape[0] = N; t.shape[1] = K;
-    t.tile[0] = scale_numel == 1 ? N : 1; t.tile[1] = scale_numel == 1 ? K : group;
-    uint8_t* image = static_cast<uint8_t*>(workspace);
-    int rc = FFQ_OK;
-    for (int which = 0; which < 2 && rc == FFQ_OK; ++which) {
-      const void* codes = which ? up_codes : gate_codes;
-      const float* sc = which ? up_scale : gate_scale;
-      const float* of = which ? up_offset : gate_offset;
-      if (w_dt == FFQ_U8)
-        rc = ffq_unpack_dequantize_int4(static_cast<const uint8_t*>(codes), sc, scale_numel, of, of ? scale_numel : 0, &t, pack_block, image + which * image_bytes, FFQ_BF16, stream);
-      else
-        rc = ffq_dequantize_by_tile(codes, FFQ_I8, sc, FFQ_F32, scale_numel, of, FFQ_F32, of ? scale_numel : 0, &t, image + which * image_bytes, FFQ_BF16, stream);
-    }
-    if (rc == FFQ_OK) {
-      a.w = image; a.w2 = image + image_bytes;
-      wq_dispatch<WL_B_BF16, true>(a, false, false, s);
-      return check_launch("wq_gemm256_kernel (mlp mode, bf16 images)");
-    }
-    if (rc != FFQ_ERR_DTYPE) return rc;
-  }
-  if (w_dt == FFQ_U8) wq_dispatch<WL_B_I4, true>(a, grouped, offset, s);
-  else wq_dispatch<WL_B_I8, true>(a, grouped, offset, s);
-  return check_launch("wq_gemm256_kernel (mlp mode)");
+  const void* const codes[2] = {gate_codes, up_codes};
+  const float* const scale[2] = {gate_scale, up_scale};
+  const float* const offset[2] = {gate_offset, up_offset};
+  const int64_t rows[2] = {N, N};
+  return wq_tiles_launch<true>(a, 2, codes, w_dt, pack_block, scale, offset, group, rows, workspace, workspace_bytes, tickets, split, stream);
 }

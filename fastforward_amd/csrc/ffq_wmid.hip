@@ -756,6 +756,12 @@ __global__ __launch_bounds__(64 * MDD_WAVES, 2) void wq_mid_dma_kernel(MidArgs a
 static int md_bm(int64_t M, int64_t K) { return (M <= 256 || K <= 8192) ? 64 : 128; }
 static int64_t md_tiles_m(int64_t M, int64_t K) { return (M + md_bm(M, K) - 1) / md_bm(M, K); }
 static int64_t md_tiles_n(int64_t N) { return (N + MD_BN - 1) / MD_BN; }
+// ... of the widest launch of N output columns, which the queries (they see N alone) have to cover: up to three matrices, each rounded up
+// to whole tiles, sum of ceil(n_i / 128) <= ceil(N / 128) + 2. (wq_mid_applies admits whole tiles only for every matrix but the last, so
+// a launch walks md_tiles_n(N) of them; the two spare tiles belong to the scratch figures callers have been given.)
+static int64_t md_tiles_n_bound(int64_t N) { return md_tiles_n(N) + 2; }
+// fp32 partial sums of `tiles` tiles of bm x 128 in S slices each
+static size_t md_slab_bytes(int64_t tiles, int64_t S, int bm) { return S > 1 ? (size_t)tiles * (size_t)S * (size_t)bm * MD_BN * 4u : 0; }
 
 bool wq_mid_shape_ok(int64_t M, int64_t K) { return M >= 1 && M <= WQ_MID_MAX_M && K % 64 == 0 && K >= 128; }
 
@@ -775,15 +781,15 @@ int wq_mid_split(int64_t M, int64_t N, int64_t K) {
   return S < 1 ? 1 : (int)S;
 }
 
-// ticket words: one per (tile, wave), for the widest launch of this (M, N, K): three matrices, each rounded up to whole tiles
+// ticket words: one per (tile, wave), up to 8 waves per tile
 int64_t wq_mid_tickets(int64_t M, int64_t N, int64_t K) {
   if (!wq_mid_shape_ok(M, K)) return 0;
-  return md_tiles_m(M, K) * (md_tiles_n(N) + 2) * 8;  // (tile, wave): up to 8 waves per tile
+  return md_tiles_m(M, K) * md_tiles_n_bound(N) * 8;
 }
 
 size_t wq_mid_slab_bytes(int64_t M, int64_t N, int64_t K, int64_t split) {
-  if (!wq_mid_shape_ok(M, K) || split <= 1) return 0;
-  return (size_t)(md_tiles_m(M, K) * (md_tiles_n(N) + 2)) * (size_t)split * (size_t)md_bm(M, K) * MD_BN * 4u;
+  if (!wq_mid_shape_ok(M, K)) return 0;
+  return md_slab_bytes(md_tiles_m(M, K) * md_tiles_n_bound(N), split, md_bm(M, K));
 }
 
 bool wq_mid_applies(const WLinearArgs& a) {
@@ -833,55 +839,25 @@ static void md_launch(const MidArgs& m, int bm, unsigned grid, hipStream_t strea
 int wq_mid_launch(const WLinearArgs& a, int w_dt, int64_t group, int64_t split, void* workspace, size_t workspace_bytes, int32_t* tickets,
                   hipStream_t stream) {
   MidArgs m;
-  m.x = a.x;
-  m.w[0] = a.w; m.scale[0] = a.w_scale; m.offset[0] = a.w_offset; m.out[0] = a.out;
-  int64_t N = 0, tiles_n = 0;
-  for (int i = 0; i < 3; ++i) {
-    m.seg_n[i] = a.seg_n[i];
-    m.seg_tile[i] = i == 0 ? 0 : (a.seg_n[i] > 0 ? (int)tiles_n : INT32_MAX);
-    if (i > 0) { m.w[i] = a.seg_w[i - 1]; m.scale[i] = a.seg_scale[i - 1]; m.offset[i] = a.seg_offset[i - 1]; m.out[i] = a.seg_out[i - 1]; }
-    N += a.seg_n[i];
-    tiles_n += md_tiles_n(a.seg_n[i]);
-  }
-  m.bias = a.bias; m.bias_dt = a.bias_dt; m.out_dt = a.out_dt;
-  m.M = a.M; m.K = a.K;
+  const int64_t tiles_n = wq_fill_segments(m, m.seg_tile, a, md_tiles_n);
   m.tiles_m = (int)md_tiles_m(a.M, a.K); m.tiles_n = (int)tiles_n;
-  m.groups = a.groups; m.steps_per_group = (int)(group / 64); m.per_row = a.per_row; m.pack_shift = a.pack_shift;
+  m.steps_per_group = (int)(group / 64);
   const int64_t ksuper = a.K / 64;
-  int64_t S = split > 0 ? split : wq_mid_split(a.M, N, a.K);
+  int64_t S = split > 0 ? split : wq_mid_split(a.M, a.N, a.K);
   if (S > ksuper) {
     if (split > 0) return fail(FFQ_ERR_ARG, "weight-only linear (128-column tiles): split %lld exceeds the %lld super-steps of 64 along K", (long long)split, (long long)ksuper);
     S = ksuper;
   }
   const int bm = md_bm(a.M, a.K);
   const int64_t tiles = (int64_t)m.tiles_m * tiles_n;
-  const size_t slab = S > 1 ? (size_t)tiles * (size_t)S * (size_t)bm * MD_BN * 4u : 0;
-  if (S > 1 && (!tickets || !workspace || workspace_bytes < slab || !aligned16(workspace))) {
-    if (split > 1) return fail(FFQ_ERR_ARG, "weight-only linear (128-column tiles): split %lld needs %zu bytes of workspace and a ticket buffer", (long long)S, slab);
-    S = 1;  // the plan is a preference: without scratch every block walks the whole K range
-  }
-  m.S = (int)S;
-  m.slabs = S > 1 ? static_cast<float*>(workspace) : nullptr;
-  m.tickets = S > 1 ? tickets : nullptr;
-  const unsigned grid = (unsigned)(tiles * S);
+  if (int rc = wq_take_split(" (128-column tiles)", split > 0, S, md_slab_bytes(tiles, S, bm), workspace, workspace_bytes, tickets, &m.S, &m.slabs, &m.tickets)) return rc;
+  const unsigned grid = (unsigned)(tiles * m.S);
   const bool grouped = a.groups > 1, offset = a.w_offset != nullptr;
-#define FFQ_MD_T(BK)                                                                                                                     \
-  do {                                                                                                                                   \
-    if (grouped) { if (offset) md_launch<BK, true, true>(m, bm, grid, stream); else md_launch<BK, true, false>(m, bm, grid, stream); }     \
-    else { if (offset) md_launch<BK, false, true>(m, bm, grid, stream); else md_launch<BK, false, false>(m, bm, grid, stream); }           \
-  } while (0)
   if (md_takes_dma(w_dt, a.pack_shift)) {
-#define FFQ_MDD_T(BK)                                                                                                                            \
-  do {                                                                                                                                           \
-    if (grouped) { if (offset) md_launch_dma<BK, true, true>(m, bm, grid, stream); else md_launch_dma<BK, true, false>(m, bm, grid, stream); }     \
-    else { if (offset) md_launch_dma<BK, false, true>(m, bm, grid, stream); else md_launch_dma<BK, false, false>(m, bm, grid, stream); }           \
-  } while (0)
-    if (w_dt == FFQ_U8) FFQ_MDD_T(WL_B_I4); else FFQ_MDD_T(WL_B_I8);
-#undef FFQ_MDD_T
+    wq_visit_storage(w_dt, grouped, offset, [&](auto kind, auto g, auto o) { md_launch_dma<kind(), g(), o()>(m, bm, grid, stream); });
     return check_launch("wq_mid_dma_kernel");
   }
-  if (w_dt == FFQ_U8) FFQ_MD_T(WL_B_I4); else FFQ_MD_T(WL_B_I8);
-#undef FFQ_MD_T
+  wq_visit_storage(w_dt, grouped, offset, [&](auto kind, auto g, auto o) { md_launch<kind(), g(), o()>(m, bm, grid, stream); });
   return check_launch("wq_mid_kernel");
 }
 

@@ -4,6 +4,8 @@
 #include "ffq_common.h"
 #include "ffq_vec.h"
 
+#include <type_traits>
+
 namespace ffq {
 
 typedef int wl_v4i __attribute__((ext_vector_type(4)));
@@ -67,13 +69,62 @@ __device__ __forceinline__ void dequantize4(uint32_t w, float s, float c, uint32
   hi = pack2<bf16_t>(f2 * s, f3 * s);
 }
 
+// ==== host side: what the launches of the three forms decide alike, stated once =======================================================
+// ---- the storage ladder: (container, parameters per group, offsets) -> the kernels' template arguments (BKIND, GROUPED, OFFSET) ------
+// `fn` is a generic lambda taking three std::integral_constant's; FFQ_U8 = packed nibbles, anything else the int8 container
+template <typename F>
+inline void wq_visit_storage(int w_dt, bool grouped, bool offset, F&& fn) {
+  auto flags = [&](auto kind) {
+    if (grouped) { if (offset) fn(kind, std::true_type{}, std::true_type{}); else fn(kind, std::true_type{}, std::false_type{}); }
+    else { if (offset) fn(kind, std::false_type{}, std::true_type{}); else fn(kind, std::false_type{}, std::false_type{}); }
+  };
+  if (w_dt == FFQ_U8) flags(std::integral_constant<int, WL_B_I4>{}); else flags(std::integral_constant<int, WL_B_I8>{});
+}
+
+// ---- the K slices a launch takes from the scratch on offer ---------------------------------------------------------------------------
+// `S` slices (the forced split, else the form's plan, already within the form's maximum) need `slab` bytes at the front of `workspace`
+// and the ticket buffer. Short of either a forced split is an error; the plan is a preference: the launch then walks the whole K range.
+// Sets the three fields of the form's kernel arguments; `form`: the form's name as the message carries it.
+inline int wq_take_split(const char* form, bool forced, int64_t S, size_t slab, void* workspace, size_t workspace_bytes, int32_t* tickets,
+                         int* slices, float** slabs, int** ticket_words) {
+  if (S > 1 && (!tickets || !workspace || workspace_bytes < slab || !aligned16(workspace))) {
+    if (forced) return fail(FFQ_ERR_ARG, "weight-only linear%s: split %lld needs %zu bytes of workspace and a ticket buffer", form, (long long)S, slab);
+    S = 1;
+  }
+  *slices = (int)S;
+  *slabs = S > 1 ? static_cast<float*>(workspace) : nullptr;
+  *ticket_words = S > 1 ? tickets : nullptr;
+  return FFQ_OK;
+}
+
+// ---- the matrices of a launch ---------------------------------------------------------------------------------------------------------
+// From the layout of WLinearArgs (matrix 0 in the main fields, 1 and 2 in seg_*[i - 1]) into the arrays of MidArgs / SkinnyArgs, with the
+// fields the two share. `first[i]`: the first column tile / n-block of matrix i on a running edge of `units(rows of the matrix)`;
+// returns the edge behind the last matrix = the launch's count of them.
+template <typename Args, typename Units>
+inline int64_t wq_fill_segments(Args& to, int* first, const WLinearArgs& a, Units units) {
+  to.x = a.x;
+  int64_t edge = 0;
+  for (int i = 0; i < 3; ++i) {
+    to.seg_n[i] = a.seg_n[i];
+    first[i] = i == 0 ? 0 : (a.seg_n[i] > 0 ? (int)edge : INT32_MAX);
+    to.w[i] = i ? a.seg_w[i - 1] : a.w; to.scale[i] = i ? a.seg_scale[i - 1] : a.w_scale;
+    to.offset[i] = i ? a.seg_offset[i - 1] : a.w_offset; to.out[i] = i ? a.seg_out[i - 1] : a.out;
+    edge += units(a.seg_n[i]);
+  }
+  to.bias = a.bias; to.bias_dt = a.bias_dt; to.out_dt = a.out_dt;
+  to.M = a.M; to.K = a.K;
+  to.groups = a.groups; to.per_row = a.per_row; to.pack_shift = a.pack_shift;
+  return edge;
+}
+
 // ---- the skinny form (ffq_wskinny.hip): M <= 128 rows, plain launches -------------------------------------------------------------
 bool wq_skinny_applies(const WLinearArgs& a, int64_t pack_block);
 int wq_skinny_split(int64_t M, int64_t N, int64_t K);                       // K slices across blocks the library's plan takes
 int64_t wq_skinny_tickets(int64_t M, int64_t N, int64_t K);                 // int32 counters (zero before, zero after)
 size_t wq_skinny_slab_bytes(int64_t M, int64_t N, int64_t K, int64_t split);
-int wq_skinny_launch(const WLinearArgs& a, int w_dt, int64_t pack_block, int64_t group, int64_t split, void* workspace, size_t workspace_bytes,
-                     int32_t* tickets, hipStream_t stream);
+int wq_skinny_launch(const WLinearArgs& a, int w_dt, int64_t group, int64_t split, void* workspace, size_t workspace_bytes, int32_t* tickets,
+                     hipStream_t stream);
 int wq_cus();
 
 // ---- 128-column tiles (ffq_wmid.hip): M <= 512 rows, plain launches, every storage form -------------------------------------------

@@ -577,16 +577,28 @@ static int sk_split_for(int64_t M, int64_t N, int64_t n_min, int64_t K) {
 // (the plan queries of the C ABI see M, N, K only: one matrix)
 int wq_skinny_split(int64_t M, int64_t N, int64_t K) { return sk_split_for(M, N, N, K); }
 
-// ticket words / slab bytes: upper bounds over the forms a launch of this (M, N, K) can take (one or two weight tiles per block, one
-// to three matrices, each rounded up to whole blocks)
+// partial strips of `blocks` n-blocks in S slices each
+static size_t sk_slab_bytes(int64_t M, int64_t K, int64_t n_min, int64_t blocks, int64_t S) {
+  return S > 1 ? (size_t)blocks * (size_t)S * (size_t)sk_strips(M, K, n_min) * (size_t)sk_strip_bytes(M, K) : 0;
+}
+
+// The queries see (M, N, K) alone and answer for the widest launch of N columns: one to three matrices, each rounded up to whole
+// n-blocks, of either form. Counted in weight tiles of 16 columns — an n-block is NT <= 2 of them in the rows form, 8 in the 128-column
+// form — the blocks of a launch hold at most N / 16 + 3 tiles-per-block of them: N / 16 + 6 and N / 16 + 24.
+//   ticket words = blocks x strips: rows form (blocks NT) MT <= (N / 16 + 6) MT with MT <= 4; 128-column form blocks x 8 <= N / 16 + 24;
+//                  both within (N / 16 + 6) x 8
+//   slab bytes per slice = blocks x strips x strip bytes: rows form (blocks NT) MT KiB <= (N / 16 + 6) MT KiB; 128-column form
+//                  (blocks x 8) MT KiB <= (N / 16 + 24) MT KiB
+static int64_t sk_tiles16_bound(int64_t N, int spare) { return (N + 15) / 16 + spare; }
+
 int64_t wq_skinny_tickets(int64_t M, int64_t N, int64_t K) {
   if (!sk_shape_ok(M, K)) return 0;
-  return ((N + 15) / 16 + 6) * SK_WAVES;
+  return sk_tiles16_bound(N, 6) * SK_WAVES;
 }
 
 size_t wq_skinny_slab_bytes(int64_t M, int64_t N, int64_t K, int64_t split) {
   if (!sk_shape_ok(M, K) || split <= 1) return 0;
-  return (size_t)((N + 15) / 16 + 24) * (size_t)split * (size_t)sk_mt(M) * 1024u;
+  return (size_t)sk_tiles16_bound(N, 24) * (size_t)split * (size_t)sk_mt(M) * 1024u;
 }
 
 bool wq_skinny_applies(const WLinearArgs& a, int64_t pack_block) {
@@ -629,57 +641,31 @@ static void sk_launch_rows(const SkinnyArgs& s, int mt, int nt, unsigned grid, h
 #undef FFQ_SKR
 }
 
-int wq_skinny_launch(const WLinearArgs& a, int w_dt, int64_t pack_block, int64_t group, int64_t split, void* workspace, size_t workspace_bytes,
-                     int32_t* tickets, hipStream_t stream) {
-  (void)pack_block;
+int wq_skinny_launch(const WLinearArgs& a, int w_dt, int64_t group, int64_t split, void* workspace, size_t workspace_bytes, int32_t* tickets,
+                     hipStream_t stream) {
   SkinnyArgs s;
-  s.x = a.x;
-  s.w[0] = a.w; s.scale[0] = a.w_scale; s.offset[0] = a.w_offset; s.out[0] = a.out;
-  int64_t N = 0, blocks = 0, n_min = INT64_MAX;
+  int64_t n_min = INT64_MAX;
   for (int i = 0; i < 3; ++i)
     if (a.seg_n[i] > 0 && a.seg_n[i] < n_min) n_min = a.seg_n[i];
-  for (int i = 0; i < 3; ++i) {
-    s.seg_n[i] = a.seg_n[i];
-    s.seg_block[i] = i == 0 ? 0 : (a.seg_n[i] > 0 ? (int)blocks : INT32_MAX);
-    if (i > 0) { s.w[i] = a.seg_w[i - 1]; s.scale[i] = a.seg_scale[i - 1]; s.offset[i] = a.seg_offset[i - 1]; s.out[i] = a.seg_out[i - 1]; }
-    N += a.seg_n[i];
-    blocks += sk_n_blocks(a.M, a.K, a.seg_n[i], n_min);
-  }
-  s.bias = a.bias; s.bias_dt = a.bias_dt; s.out_dt = a.out_dt;
-  s.M = a.M; s.K = a.K;
+  const int64_t blocks = wq_fill_segments(s, s.seg_block, a, [&](int64_t n) { return sk_n_blocks(a.M, a.K, n, n_min); });
   s.n_blocks = (int)blocks;
-  s.groups = a.groups; s.group_div = make_fastdiv((uint32_t)group); s.per_row = a.per_row; s.pack_shift = a.pack_shift;
+  s.group_div = make_fastdiv((uint32_t)group);
   const bool rows_form = sk_rows_form(a.M, a.K);
   const int mt = sk_mt(a.M), nt = sk_nt(a.M, a.K, n_min), kc = rows_form ? SK_KC : sk_cols_kc(a.M);
   s.chunks = (int)(a.K / kc);
-  int64_t S = split > 0 ? split : sk_split_for(a.M, N, n_min, a.K);
+  int64_t S = split > 0 ? split : sk_split_for(a.M, a.N, n_min, a.K);
   if (S > s.chunks) {
     if (split > 0) return fail(FFQ_ERR_ARG, "weight-only linear (skinny form): split %lld exceeds the %d chunks of %d along K", (long long)split, s.chunks, kc);
     S = s.chunks;
   }
-  const size_t slab = S > 1 ? (size_t)blocks * (size_t)S * (size_t)sk_strips(a.M, a.K, n_min) * (size_t)sk_strip_bytes(a.M, a.K) : 0;
-  if (S > 1 && (!tickets || !workspace || workspace_bytes < slab || !aligned16(workspace))) {
-    if (split > 1) return fail(FFQ_ERR_ARG, "weight-only linear (skinny form): split %lld needs %zu bytes of workspace and a ticket buffer", (long long)S, slab);
-    S = 1;  // the plan is a preference: without scratch every block walks the whole K range
-  }
-  s.S = (int)S;
-  s.slabs = S > 1 ? static_cast<float*>(workspace) : nullptr;
-  s.tickets = S > 1 ? tickets : nullptr;
-  const unsigned grid = (unsigned)(blocks * S);
+  if (int rc = wq_take_split(" (skinny form)", split > 0, S, sk_slab_bytes(a.M, a.K, n_min, blocks, S), workspace, workspace_bytes, tickets, &s.S, &s.slabs, &s.tickets)) return rc;
+  const unsigned grid = (unsigned)(blocks * s.S);
   const bool grouped = a.groups > 1, offset = a.w_offset != nullptr;
   if (rows_form) {
-#define FFQ_SKR_T(BK) do { if (grouped) { if (offset) sk_launch_rows<BK, true, true>(s, mt, nt, grid, stream); else sk_launch_rows<BK, true, false>(s, mt, nt, grid, stream); } else { if (offset) sk_launch_rows<BK, false, true>(s, mt, nt, grid, stream); else sk_launch_rows<BK, false, false>(s, mt, nt, grid, stream); } } while (0)
-    if (w_dt == FFQ_U8) FFQ_SKR_T(WL_B_I4); else FFQ_SKR_T(WL_B_I8);
-#undef FFQ_SKR_T
+    wq_visit_storage(w_dt, grouped, offset, [&](auto kind, auto g, auto o) { sk_launch_rows<kind(), g(), o()>(s, mt, nt, grid, stream); });
     return check_launch("wq_skinny_rows_kernel");
   }
-#define FFQ_SK_T(BK)                                                                              \
-  do {                                                                                            \
-    if (grouped) { if (offset) sk_launch_cols<BK, true, true>(s, mt, grid, stream); else sk_launch_cols<BK, true, false>(s, mt, grid, stream); } \
-    else { if (offset) sk_launch_cols<BK, false, true>(s, mt, grid, stream); else sk_launch_cols<BK, false, false>(s, mt, grid, stream); }        \
-  } while (0)
-  if (w_dt == FFQ_U8) FFQ_SK_T(WL_B_I4); else FFQ_SK_T(WL_B_I8);
-#undef FFQ_SK_T
+  wq_visit_storage(w_dt, grouped, offset, [&](auto kind, auto g, auto o) { sk_launch_cols<kind(), g(), o()>(s, mt, grid, stream); });
   return check_launch("wq_skinny_kernel");
 }
 

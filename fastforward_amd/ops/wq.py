@@ -13,6 +13,22 @@ import torch
 from fastforward_amd import _native
 from fastforward_amd.ops import _base
 from fastforward_amd.ops._base import _TAGS, _dense, _native_route, _ptr, _tag, _tickets, _workspace
+from fastforward_amd.ops.gemm import _f32
+
+_NOT_PACKED = "packed weights are the uint8 output of pack_int4 for an [N, K] weight"
+
+
+def _rows(codes: torch.Tensor, K: int, pack_block: int) -> int | None:
+    """N of an [N, K] weight as it is stored — [N, K] codes, or with ``pack_block`` > 0 the uint8 output of pack_int4 ([N * K / 2] or
+    [N, K / 2]) — and None where `codes` is no such weight."""
+    if pack_block > 0:
+        return None if codes.dtype != torch.uint8 or K == 0 or (codes.numel() * 2) % K else codes.numel() * 2 // K
+    return codes.shape[0] if codes.dim() == 2 and codes.shape[1] == K else None
+
+
+def _alike(w_codes: Sequence[torch.Tensor], w_offsets: Sequence[torch.Tensor | None]) -> bool:
+    """The weights of one launch: one container dtype, offsets for all of them or for none."""
+    return all(c.dtype == w_codes[0].dtype for c in w_codes) and all((o is None) == (w_offsets[0] is None) for o in w_offsets)
 
 
 def linear_wq(
@@ -42,18 +58,14 @@ def linear_wq(
     (``ffq_linear_wq_split``), >= 1 forces that many slices (tests, tuning).
     Returns None when the kernel does not cover the problem (dtypes, K % 64, group % 64): the caller dequantizes and runs a
     float GEMM as the reference does."""
-    packed = pack_block > 0
-    if packed:
-        K = x.shape[-1]
-        if w_codes.dtype != torch.uint8 or K == 0 or (w_codes.numel() * 2) % K:
-            raise RuntimeError("packed weights are the uint8 output of pack_int4 for an [N, K] weight")
-        N = w_codes.numel() * 2 // K
-    else:
+    K = x.shape[-1]
+    N = _rows(w_codes, K, pack_block)
+    if N is None:
+        if pack_block > 0:
+            raise RuntimeError(_NOT_PACKED)
         if w_codes.dim() != 2:
             raise RuntimeError("linear_wq expects a [N, K] weight")
-        N, K = w_codes.shape
-    if x.shape[-1] != K:
-        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({x.numel() // max(x.shape[-1], 1)}x{x.shape[-1]} and {N}x{K}^T)")
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({x.numel() // max(K, 1)}x{K} and {w_codes.shape[0]}x{w_codes.shape[1]}^T)")
     group = K if group is None else int(group)
     out_dtype = out_dtype or x.dtype
     if x.dtype not in _TAGS or w_codes.dtype not in _TAGS or out_dtype not in _TAGS:
@@ -71,12 +83,11 @@ def _linear_wq(x, w_codes, w_scale, w_offset, group, bias, out_dtype, pack_block
     """Python implementation of the ``linear_wq`` operator for a problem the kernel covers; arguments in schema order
     (`two_pass`: -1 = the library's rule, 0 = never, 1 = offer the image's scratch whatever M)."""
     K = x.shape[-1]
-    N = w_codes.numel() * 2 // K if pack_block > 0 else w_codes.shape[0]
+    N = _rows(w_codes, K, pack_block)
     M = x.numel() // K
     two_pass = None if two_pass < 0 else bool(two_pass)
     xc, wc = _dense(x.detach()), _dense(w_codes.detach())
-    sc = w_scale.detach().reshape(-1).to(torch.float32).contiguous()
-    of = None if w_offset is None else w_offset.detach().reshape(-1).to(torch.float32).contiguous()
+    sc, of = _f32(w_scale), _f32(w_offset)
     if of is not None and of.numel() != sc.numel():
         raise RuntimeError(f"scale has {sc.numel()} entries, offset {of.numel()}")
     bias_c = None if bias is None else bias.detach().contiguous()
@@ -114,30 +125,19 @@ def linear_wq_multi(
     if not (2 <= count <= 3) or len(w_scales) != count or len(w_offsets) != count:
         return None
     K = x.shape[-1]
-    packed = pack_block > 0
-    rows = []
-    for c in w_codes:
-        if packed:
-            if c.dtype != torch.uint8 or K == 0 or (c.numel() * 2) % K:
-                return None
-            rows.append(c.numel() * 2 // K)
-        else:
-            if c.dim() != 2 or c.shape[1] != K:
-                return None
-            rows.append(c.shape[0])
+    rows = [_rows(c, K, pack_block) for c in w_codes]
     group = K if group is None else int(group)
     out_dtype = out_dtype or x.dtype
-    if x.dtype not in _TAGS or any(c.dtype != w_codes[0].dtype for c in w_codes) or w_codes[0].dtype not in _TAGS or out_dtype not in _TAGS:
+    if None in rows or not _alike(w_codes, w_offsets) or x.dtype not in _TAGS or w_codes[0].dtype not in _TAGS or out_dtype not in _TAGS:
         return None
-    if any(n % 256 for n in rows[:-1]) or any((o is None) != (w_offsets[0] is None) for o in w_offsets):
+    if any(n % 256 for n in rows[:-1]):
         return None
     M = x.numel() // K if K else 0
     N = sum(rows)
     lib = _native.library()
     if not lib.ffq_linear_wq_supported(_tag(x.dtype), _tag(w_codes[0].dtype), _tag(out_dtype), M, N, K, group, int(pack_block)):
         return None
-    flat = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
-    scales, offsets = [flat(t) for t in w_scales], [flat(t) for t in w_offsets]
+    scales, offsets = [_f32(t) for t in w_scales], [_f32(t) for t in w_offsets]
     kinds = {int(s_.numel() != 1) for s_ in scales}
     if len(kinds) != 1:
         return None
@@ -199,14 +199,9 @@ def mlp_gate_up_wq(
     without the two bf16 projections in HBM. Operands as :func:`linear_wq` (both weights in the same form); bf16 only.
     None when the kernel does not cover the problem."""
     K = x.shape[-1]
-    if pack_block > 0:
-        if gate_codes.dtype != torch.uint8 or K == 0 or (gate_codes.numel() * 2) % K:
-            raise RuntimeError("packed weights are the uint8 output of pack_int4 for an [N, K] weight")
-        N = gate_codes.numel() * 2 // K
-    else:
-        if gate_codes.dim() != 2 or gate_codes.shape[1] != K:
-            raise RuntimeError("mlp_gate_up_wq expects [N, K] weights")
-        N = gate_codes.shape[0]
+    N = _rows(gate_codes, K, pack_block)
+    if N is None:
+        raise RuntimeError(_NOT_PACKED if pack_block > 0 else "mlp_gate_up_wq expects [N, K] weights")
     if gate_codes.shape != up_codes.shape or gate_codes.dtype != up_codes.dtype:
         raise RuntimeError("gate and up weights differ in shape or dtype")
     group = K if group is None else int(group)
@@ -217,8 +212,7 @@ def mlp_gate_up_wq(
     if not lib.ffq_linear_wq_supported(_tag(x.dtype), _tag(gate_codes.dtype), _tag(torch.bfloat16), M, N, K, group, int(pack_block)):
         return None
     xc, gc, uc = _dense(x.detach()), _dense(gate_codes.detach()), _dense(up_codes.detach())
-    flat = lambda t: None if t is None else t.detach().reshape(-1).to(torch.float32).contiguous()  # noqa: E731
-    gs, go, us, uo = flat(gate_scale), flat(gate_offset), flat(up_scale), flat(up_offset)
+    gs, go, us, uo = _f32(gate_scale), _f32(gate_offset), _f32(up_scale), _f32(up_offset)
     if gs.numel() != us.numel() or (go is not None and (go.numel() != gs.numel() or uo.numel() != gs.numel())):
         raise RuntimeError("gate and up parameters differ in count")
     lib, stream = _base._prepare(xc, gc, uc, gs, go, us, uo)

@@ -1198,6 +1198,11 @@ def test_weight_only_linears_on_one_input_as_one_launch(m, rows, k, group, bits,
         ref = x.double() @ ops.dequantize_by_tile(c, s_, (1, group), o, torch.bfloat16).double().t()
         torch.testing.assert_close(g.double(), ref, rtol=2.0**-8, atol=1e-5 * float(ref.abs().max()) + 1e-6 * k)
     assert torch.equal(ops.linear_wq_multi(x, codes, scales, offs, group=group, out_dtype=torch.float32)[1].to(torch.bfloat16), planned[1])
+    # a forced split above 1 (the 128-column tiles at 77 and 300 rows, the 256-row tiles beyond): the separate launches' bits under that split
+    forced = ops.linear_wq_multi(x, codes, scales, offs, group=group, two_pass=False, split=2)
+    for g, (c, s_, o) in zip(forced, cases):
+        alone = ops.linear_wq(x, c, s_, o, group=group, two_pass=False, split=2)
+        assert torch.equal(g, alone), "split 2: " + mismatch_report(g.cpu(), alone.cpu())
     # not this kernel's: a middle matrix that is no multiple of 256 rows, mixed offsets
     assert ops.linear_wq_multi(x, [codes[-1], codes[0]], [scales[-1], scales[0]], [offs[-1], offs[0]], group=group) is None or rows[-1] % 256 == 0
     assert ops.linear_wq_multi(x, codes[:2], scales[:2], [offs[0], None if offs[1] is not None else scales[1]], group=group) is None
