@@ -310,6 +310,22 @@ SIGNATURES_UNFOLD: dict[str, tuple[object, list[object]]] = {
     "ffq_unfold_quantize": (_i, [_vp, _i, _vp, _vp, _i, _i] + [_i64] * 12 + [_vp, _fp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ffq_sdpa_decode.h one to one: the sixth header's table (attention for a short query over
+# int8 K / V codes, split over the keys), bound as SIGNATURES_3D is (None on a library without the symbol).
+SIGNATURES_DECODE: dict[str, tuple[object, list[object]]] = {
+    "ffq_sdpa_decode_splits": (_i64, [_i64] * 5),
+    "ffq_sdpa_decode_workspace_bytes": (_sz, [_i64] * 5),
+    "ffq_sdpa_decode": (
+        _i,
+        [_vp, _i, _vp, _vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _vp, _i, _i,
+         ctypes.POINTER(_i64), _d, _vp, _vp, _d, _i64, _vp, _vp, _sz, _vp],
+    ),
+}
+
+SDPA_DECODE_MAX_ROWS = 32  # FFQ_SDPA_DECODE_MAX_ROWS
+SDPA_DECODE_KEY_TILE = 128  # FFQ_SDPA_DECODE_KEY_TILE
+SDPA_DECODE_MAX_SPLITS = 64  # FFQ_SDPA_DECODE_MAX_SPLITS
+
 
 class FFQLibrary:
     """A loaded implementation of the ``ffq_*`` ABI."""
@@ -338,7 +354,7 @@ class FFQLibrary:
         for name in missing:
             setattr(self, name, None)
         for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items(),
-                                          *SIGNATURES_UNFOLD.items()):
+                                          *SIGNATURES_UNFOLD.items(), *SIGNATURES_DECODE.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

@@ -1,0 +1,564 @@
+// ffq_sdpa_decode.hip — scaled_dot_product_attention for a short query over int8 K / V codes (a quantized KV cache), split over the
+// keys: two plain launches, no tickets, no spin waits, no grid barrier (include/ffq_sdpa_decode.h).
+//
+// sdpa_decode_partial_kernel: one workgroup = 4 waves = one (batch, kv head, key split). The rows = L * (H / HKV) <= 32 query rows
+// that read this kv head are the query side of ONE 32x32x16 MFMA tile (row r = g * L + l: query head kvh * G + g, position l), so
+// the codes of K and V are read once per (batch, kv head) whatever the GQA group is. A wave walks 32-key tiles of the split (wave w
+// takes keys [128 it + 32 w, +32) of it) with its own online softmax; the four waves' (m, l, O) are merged through LDS at the end.
+//   * K stays int8 in memory and goes from global memory straight into the MFMA's A operand: lane (key r32, half h) loads the 16
+//     codes of columns [(2u + h) * 16, +16) of its key row with one 16-byte load and dequantizes them in registers,
+//     (c + rne(o)) * s in fp32, rounded once to the data dtype (transform<F16> of ffq_sdpa.hip: the value the math path contracts).
+//     Their first 8 values are the lane's slice of MFMA step 2u, the last 8 of step 2u + 1; the Q fragments use the same slices, so
+//     the contraction runs over all of E in an order of its own (fp32 accumulation);
+//   * scores transposed, S^T[key][row] = mfma(A = K, B = Q): a lane holds 16 keys of one query row, the row statistics are
+//     lane-local plus one cross-half exchange. The raw q values enter the MFMA and sqrt(scale)^2 multiplies the fp32 sum;
+//   * V is loaded the same way, dequantized, and written to a wave-private V^T image in LDS ([d][key], 72-byte pitch), from which
+//     the A operand of O^T[d][row] = mfma(A = V^T, B = P) is read with two 8-byte loads (load_vt of ffq_sdpa.hip). The image is
+//     written ahead of the tile's score chain, so its stores land under the QK^T MFMAs and the softmax. bf16 P carries its rounding
+//     residue in a second MFMA, as there;
+//   * the next tile's K and V loads are issued before this tile's arithmetic: 8 KiB in flight per wave, 32 KiB per workgroup;
+//   * keys >= the split's end (and >= S) are never loaded and score -inf; rows >= `rows` hold zeros and are never stored.
+// It writes fp32 partials: O[rows][E], m[rows], l[rows] per (batch, kv head, split). m = -inf (l = 0, O = 0) for a row whose keys
+// in the split are all masked, and for a forced split without keys.
+//
+// sdpa_decode_combine_kernel: one workgroup per (batch, head, position), one lane per column:
+// m = max m_i, out = sum e^(m_i - m) O_i / sum e^(m_i - m) l_i in fp32; a split with m_i = -inf contributes nothing, a row with
+// every m_i = -inf gives exactly 0 (the safe softmax); then the optional output quantizer on the fp32 value (A1 then A2, QReg::fake
+// of ffq_sdpa.hip) and one rounding to the data dtype.
+//
+// The split plan is a pure function of (B, HKV, S, rows, E): no device state, graph-safe (docs/kernels.md has the sweep).
+#include "ffq_affine.h"
+#include "ffq_common.h"
+#include "ffq_vec.h"
+
+#include "../../include/ffq_sdpa_decode.h"
+
+#include <math.h>
+
+namespace ffq {
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 dc_bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 dc_f16x8;
+typedef __attribute__((ext_vector_type(16))) float dc_f32x16;
+typedef __attribute__((ext_vector_type(4))) short dc_s16x4;
+typedef __attribute__((ext_vector_type(4))) float dc_f32x4;
+
+constexpr int kWaves = 4;
+constexpr int kThreads = kWaves * 64;
+constexpr int kRows = FFQ_SDPA_DECODE_MAX_ROWS;   // query rows of the one MFMA tile
+constexpr int kWaveKeys = 32;                     // keys per wave step
+constexpr int kTile = FFQ_SDPA_DECODE_KEY_TILE;   // keys per workgroup step: the unit of a split
+constexpr int kVtPitch = 72;                      // bytes per column of a wave's V^T image (32 keys + 8 bytes of skew)
+static_assert(kTile == kWaves * kWaveKeys, "a workgroup step is one 32-key tile per wave");
+
+enum { MASK_NONE = 0, MASK_CAUSAL, MASK_BOOL, MASK_FLOAT };
+
+struct DecodeArgs {
+  const void* q;       // dt or int8 container
+  const int8_t* k;
+  const int8_t* v;
+  const float* deq_s[3];  // q (nullptr: plain) / k / v
+  const float* deq_o[3];
+  int64_t qs[3], ks[3], vs[3];  // element strides of (batch, head, row)
+  int32_t B, H, HKV, L, S;
+  int32_t rows, splits, tiles_per_split;
+  int32_t q_i8;
+  const void* mask;
+  int32_t mask_kind, mask_dt;
+  int64_t ms[4];
+  float c;  // float(sqrt(scale))
+  float* ws_o;
+  float* ws_m;
+  float* ws_l;
+};
+
+template <bool F16>
+__device__ __forceinline__ float to_f32(uint16_t h) {
+  return F16 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h);
+}
+template <bool F16>
+__device__ __forceinline__ uint16_t from_f32(float f) {
+  return F16 ? f32_to_f16_bits(f) : f32_to_bf16_bits(f);
+}
+template <bool F16>
+__device__ __forceinline__ uint32_t pack_pair(float a, float b) {
+  if constexpr (F16) return pack2<f16_t>(a, b);
+  else return pack2<bf16_t>(a, b);
+}
+
+// 4 int8 codes of one dword -> 4 dequantized values in the data dtype (two dwords): (c + o) * s in fp32, one rounding. `w` holds the
+// codes with their sign bits flipped (c + 128 as unsigned bytes: one conversion instruction each) and `o` is rne(offset) - 128, so
+// (c + 128) + (o - 128) is the one fp32 addition whose exact operands sum to c + rne(offset): the bits of (float)c + rne(offset)
+// for every |offset| < 2^31.
+template <bool F16>
+__device__ __forceinline__ void dequant4(uint32_t w, float s, float o, uint32_t& lo, uint32_t& hi) {
+  const float f0 = ((float)(w & 0xFFu) + o) * s;
+  const float f1 = ((float)((w >> 8) & 0xFFu) + o) * s;
+  const float f2 = ((float)((w >> 16) & 0xFFu) + o) * s;
+  const float f3 = ((float)(w >> 24) + o) * s;
+  lo = pack_pair<F16>(f0, f1);
+  hi = pack_pair<F16>(f2, f3);
+}
+
+// 16 codes -> the 8 values of MFMA step 2u (a) and of step 2u + 1 (b); `o` is rne(offset) - 128 (dequant4)
+template <bool F16>
+__device__ __forceinline__ void dequant16(u32x4 w, float s, float o, u32x4& a, u32x4& b) {
+  uint32_t p[8];
+  dequant4<F16>(w.x ^ 0x80808080u, s, o, p[0], p[1]);
+  dequant4<F16>(w.y ^ 0x80808080u, s, o, p[2], p[3]);
+  dequant4<F16>(w.z ^ 0x80808080u, s, o, p[4], p[5]);
+  dequant4<F16>(w.w ^ 0x80808080u, s, o, p[6], p[7]);
+  a = u32x4{p[0], p[1], p[2], p[3]};
+  b = u32x4{p[4], p[5], p[6], p[7]};
+}
+
+// 8 values of a value-dtype container: codes dequantized to dt, or the plain values as they are
+template <bool F16>
+__device__ __forceinline__ u32x4 dequant8(u32x4 w, bool deq, float s, float o) {
+  if (!deq) return w;
+  uint32_t word[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float x0 = (to_f32<F16>((uint16_t)(word[i] & 0xFFFFu)) + o) * s;
+    const float x1 = (to_f32<F16>((uint16_t)(word[i] >> 16)) + o) * s;
+    word[i] = pack_pair<F16>(x0, x1);
+  }
+  return u32x4{word[0], word[1], word[2], word[3]};
+}
+
+__device__ __forceinline__ dc_bf16x8 load_vt(const unsigned char* vt, uint32_t d, uint32_t key0) {
+  const dc_s16x4 a = *reinterpret_cast<const dc_s16x4*>(vt + d * kVtPitch + key0 * 2);
+  const dc_s16x4 b = *reinterpret_cast<const dc_s16x4*>(vt + d * kVtPitch + (key0 + 8) * 2);
+  return __builtin_bit_cast(dc_bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+template <bool F16>
+__device__ __forceinline__ dc_f32x16 mfma(dc_bf16x8 a, dc_bf16x8 b, dc_f32x16 c) {
+  if constexpr (F16)
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(dc_f16x8, a), __builtin_bit_cast(dc_f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+template <int E>
+struct Lds {
+  static constexpr int kVt = kWaves * E * kVtPitch;                        // the four V^T images
+  static constexpr int kMerge = (kWaves - 1) * (E / 32) * 16 * 64 * 4;     // waves 1..3 hand their O to wave 0
+  static constexpr int kBody = kVt > kMerge ? kVt : kMerge;
+  static constexpr int kStats = 2 * kWaves * kRows * 4;                    // m and l of every wave
+};
+
+template <int E, bool F16>
+__global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArgs a) {
+  constexpr int T = E / 16;   // MFMA k-steps of QK^T
+  constexpr int U = E / 32;   // 16-byte loads per key row and lane
+  constexpr int DB = E / 32;  // 32-column blocks of O^T
+  __shared__ __attribute__((aligned(16))) unsigned char body[Lds<E>::kBody];
+  __shared__ float stat_m[kWaves][kRows];
+  __shared__ float stat_l[kWaves][kRows];
+
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t r32 = lane & 31, h = lane >> 5;
+  const uint32_t sp = blockIdx.x % (uint32_t)a.splits, bk = blockIdx.x / (uint32_t)a.splits;
+  const uint32_t kvh = bk % (uint32_t)a.HKV, b = bk / (uint32_t)a.HKV;
+  const uint32_t G = (uint32_t)a.H / (uint32_t)a.HKV;
+
+  // the split's keys [k_begin, k_end): whole tiles but for the last split; a forced split may be empty
+  const int64_t first = (int64_t)sp * a.tiles_per_split * kTile;
+  const int32_t k_begin = first < a.S ? (int32_t)first : a.S;
+  const int64_t last = first + (int64_t)a.tiles_per_split * kTile;
+  const int32_t k_end = last < a.S ? (int32_t)last : a.S;
+  const int32_t iters = (k_end - k_begin + kTile - 1) / kTile;  // the same for the four waves: the barriers below are uniform
+
+  // this lane's query row
+  const bool row_ok = (int32_t)r32 < a.rows;
+  const uint32_t row = row_ok ? r32 : 0;
+  const uint32_t g = row / (uint32_t)a.L, l = row % (uint32_t)a.L;
+  const uint32_t head = kvh * G + g;
+
+  const bool deq_q = a.deq_s[0] != nullptr;
+  const float dqs = deq_q ? a.deq_s[0][0] : 1.0f, dqo = (deq_q && a.deq_o[0]) ? rne(a.deq_o[0][0]) : 0.0f;
+  const float dks = a.deq_s[1][0], dko = (a.deq_o[1] ? rne(a.deq_o[1][0]) : 0.0f) - 128.0f;  // (biased: dequant4)
+  const float dvs = a.deq_s[2][0], dvo = (a.deq_o[2] ? rne(a.deq_o[2][0]) : 0.0f) - 128.0f;
+  const float alpha = a.c * a.c;
+
+  // ---- Q fragments: step t = 2u + j takes columns [(2u + h) * 16 + 8j, +8) of row `row` (the slices of the K loads)
+  dc_bf16x8 qf[T];
+  {
+    const int64_t at = (int64_t)b * a.qs[0] + (int64_t)head * a.qs[1] + (int64_t)l * a.qs[2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      u32x4 lo, hi;
+      if (a.q_i8) {
+        const u32x4 w = *reinterpret_cast<const u32x4*>(static_cast<const int8_t*>(a.q) + at + (2 * u + h) * 16);
+        dequant16<F16>(w, dqs, dqo - 128.0f, lo, hi);
+      } else {
+        const uint16_t* p = static_cast<const uint16_t*>(a.q) + at + (2 * u + h) * 16;
+        lo = dequant8<F16>(*reinterpret_cast<const u32x4*>(p), deq_q, dqs, dqo);
+        hi = dequant8<F16>(*reinterpret_cast<const u32x4*>(p + 8), deq_q, dqs, dqo);
+      }
+      if (!row_ok) lo = hi = u32x4{0, 0, 0, 0};
+      qf[2 * u] = __builtin_bit_cast(dc_bf16x8, lo);
+      qf[2 * u + 1] = __builtin_bit_cast(dc_bf16x8, hi);
+    }
+  }
+
+  // ---- K / V rows of this lane: key (tile's first) + r32, 16 codes at column (2u + h) * 16; rows >= k_end read nothing
+  const int8_t* kbase = a.k + (int64_t)b * a.ks[0] + (int64_t)kvh * a.ks[1] + h * 16;
+  const int8_t* vbase = a.v + (int64_t)b * a.vs[0] + (int64_t)kvh * a.vs[1] + h * 16;
+  u32x4 sk[U], sv[U];
+  auto stage_load = [&](int32_t it) {
+    const int32_t key = k_begin + it * kTile + (int32_t)wave * kWaveKeys + (int32_t)r32;
+    const bool in = key < k_end;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      sk[u] = u32x4{0, 0, 0, 0};
+      sv[u] = u32x4{0, 0, 0, 0};
+      if (in) {
+        sk[u] = *reinterpret_cast<const u32x4*>(kbase + (int64_t)key * a.ks[2] + u * 32);
+        sv[u] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * a.vs[2] + u * 32);
+      }
+    }
+  };
+
+  unsigned char* vt = body + wave * (E * kVtPitch);
+  const unsigned char* mbase = static_cast<const unsigned char*>(a.mask);
+  const int64_t moff = (int64_t)b * a.ms[0] + (int64_t)head * a.ms[1] + (int64_t)l * a.ms[2];
+
+  dc_f32x16 o[DB];
+#pragma unroll
+  for (int i = 0; i < DB; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[i][e] = 0.0f;
+  float m_run = -INFINITY, l_run = 0.0f;  // l_run: this lane's half of the row sum
+
+  if (iters > 0) stage_load(0);
+  for (int32_t it = 0; it < iters; ++it) {
+    // this tile's operands out of the staging registers, the next tile's loads into them
+    dc_bf16x8 kf[T];
+    u32x4 vw[U][2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      u32x4 lo, hi;
+      dequant16<F16>(sk[u], dks, dko, lo, hi);
+      kf[2 * u] = __builtin_bit_cast(dc_bf16x8, lo);
+      kf[2 * u + 1] = __builtin_bit_cast(dc_bf16x8, hi);
+      dequant16<F16>(sv[u], dvs, dvo, vw[u][0], vw[u][1]);
+    }
+    const int32_t key0 = k_begin + it * kTile + (int32_t)wave * kWaveKeys;
+    if (it + 1 < iters) stage_load(it + 1);
+
+    // ---- V^T image of the wave's 32 keys: column d is a row of 32 keys. Written ahead of the score chain, whose MFMAs and softmax
+    // then run while the stores land; the barrier after the softmax publishes it
+    __syncthreads();  // (the previous tile's reads are done)
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const uint32_t words[4] = {vw[u][half].x, vw[u][half].y, vw[u][half].z, vw[u][half].w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t d = (2 * u + h) * 16 + 8 * half + j;
+          *reinterpret_cast<uint16_t*>(vt + d * kVtPitch + r32 * 2) = (uint16_t)(words[j >> 1] >> (16 * (j & 1)));
+        }
+      }
+
+    // ---- S^T of 32 keys x 32 rows
+    dc_f32x16 s, s_odd;  // two chains of T / 2 dependent MFMAs instead of one of T
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] = s_odd[e] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < T; t += 2) {
+      s = mfma<F16>(kf[t], qf[t], s);
+      s_odd = mfma<F16>(kf[t + 1], qf[t + 1], s_odd);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] += s_odd[e];
+    // the masked scores x (keys >= k_end -> -inf): the mask's kind is launch-uniform, so each form is a straight run of 16 elements;
+    // a key beyond the split reads the mask at the split's last key (in bounds) and is then discarded
+    const bool whole = key0 + kWaveKeys <= k_end;
+    auto key_of = [&](int e) { return key0 + (e & 3) + 8 * (e >> 2) + 4 * (int32_t)h; };
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] *= alpha;
+    if (a.mask_kind == MASK_CAUSAL) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[e] = key_of(e) <= (int32_t)l ? s[e] : -INFINITY;
+    } else if (a.mask_kind == MASK_BOOL) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int32_t key = key_of(e) < k_end ? key_of(e) : k_end - 1;
+        s[e] = mbase[moff + (int64_t)key * a.ms[3]] ? s[e] : -INFINITY;
+      }
+    } else if (a.mask_kind == MASK_FLOAT) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int32_t key = key_of(e) < k_end ? key_of(e) : k_end - 1;
+        const int64_t at = moff + (int64_t)key * a.ms[3];
+        float mv;
+        if (a.mask_dt == FFQ_F32) mv = reinterpret_cast<const float*>(mbase)[at];
+        else if (a.mask_dt == FFQ_BF16) mv = bf16_bits_to_f32(reinterpret_cast<const uint16_t*>(mbase)[at]);
+        else mv = f16_bits_to_f32(reinterpret_cast<const uint16_t*>(mbase)[at]);
+        s[e] = s[e] + mv;
+      }
+    }
+    if (!whole) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[e] = key_of(e) < k_end ? s[e] : -INFINITY;
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[e]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_use = m_new == -INFINITY ? 0.0f : m_new;
+    const float scale_old = m_run == -INFINITY ? 0.0f : __expf(m_run - m_use);
+    m_run = m_new;
+    l_run *= scale_old;
+    if (__any(scale_old != 1.0f)) {  // (wave-uniform: once the running maxima have settled, nothing is rescaled)
+#pragma unroll
+      for (int i = 0; i < DB; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[i][e] *= scale_old;
+    }
+    // P in the data dtype, two per conversion; pl: (bf16) the rounding residue of P, a second MFMA term
+    uint32_t pw[8], lw[8];
+    float rs = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; e += 2) {
+      const float p0 = __expf(s[e] - m_use), p1 = __expf(s[e + 1] - m_use);
+      rs += p0;
+      rs += p1;
+      const uint32_t w = pack_pair<F16>(p0, p1);
+      pw[e >> 1] = w;
+      if constexpr (!F16) lw[e >> 1] = pack_pair<false>(p0 - bf16_bits_to_f32((uint16_t)(w & 0xFFFFu)), p1 - bf16_bits_to_f32((uint16_t)(w >> 16)));
+    }
+    l_run += rs;
+    dc_bf16x8 pf[2], pl[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      pf[u] = __builtin_bit_cast(dc_bf16x8, u32x4{pw[4 * u], pw[4 * u + 1], pw[4 * u + 2], pw[4 * u + 3]});
+      if constexpr (!F16) pl[u] = __builtin_bit_cast(dc_bf16x8, u32x4{lw[4 * u], lw[4 * u + 1], lw[4 * u + 2], lw[4 * u + 3]});
+    }
+
+    __syncthreads();  // (the V^T image is complete)
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const dc_bf16x8 vf = load_vt(vt, 32 * db + r32, 16 * u + 4 * h);
+        o[db] = mfma<F16>(vf, pf[u], o[db]);
+        if constexpr (!F16) o[db] = mfma<F16>(vf, pl[u], o[db]);
+      }
+  }
+
+  // ---- merge the four waves: m = max m_w, O = sum e^(m_w - m) O_w, l = sum e^(m_w - m) l_w
+  const float l_wave = l_run + __shfl_xor(l_run, 32);
+  if (h == 0) {
+    stat_m[wave][r32] = m_run;
+    stat_l[wave][r32] = l_wave;
+  }
+  __syncthreads();  // (also: every wave is done with its V^T image, which the merge buffer overlays)
+  float m_all = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) m_all = fmaxf(m_all, stat_m[w][r32]);
+  const float m_use = m_all == -INFINITY ? 0.0f : m_all;
+  float l_all = 0.0f;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const float mw = stat_m[w][r32];
+    l_all += mw == -INFINITY ? 0.0f : __expf(mw - m_use) * stat_l[w][r32];
+  }
+  const float mine = m_run == -INFINITY ? 0.0f : __expf(m_run - m_use);
+  float* merge = reinterpret_cast<float*>(body);
+  if (wave != 0) {
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) merge[(((wave - 1) * DB + db) * 16 + e) * 64 + lane] = o[db][e] * mine;
+  }
+  __syncthreads();
+  if (wave != 0 || !row_ok) return;
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      float acc = o[db][e] * mine;
+#pragma unroll
+      for (int w = 0; w < kWaves - 1; ++w) acc += merge[((w * DB + db) * 16 + e) * 64 + lane];
+      o[db][e] = acc;
+    }
+  // O^T lane (r32 = row, h): d = 32 db + (e & 3) + 8 (e >> 2) + 4 h
+  const int64_t part = (int64_t)blockIdx.x * a.rows + r32;
+  if (h == 0) {
+    a.ws_m[part] = m_all;
+    a.ws_l[part] = l_all;
+  }
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const dc_f32x4 w = {o[db][4 * rr], o[db][4 * rr + 1], o[db][4 * rr + 2], o[db][4 * rr + 3]};
+      *reinterpret_cast<dc_f32x4*>(a.ws_o + part * E + 32 * db + 8 * rr + 4 * (int)h) = w;
+    }
+}
+
+struct CombineArgs {
+  const float* ws_o;
+  const float* ws_m;
+  const float* ws_l;
+  uint16_t* out;
+  int32_t H, HKV, L, E, rows, splits;
+  const float* out_scale;   // nullptr: no output quantizer
+  const float* out_offset;  // nullable
+  float lo, hi;
+};
+
+template <bool F16>
+__global__ __launch_bounds__(128) void sdpa_decode_combine_kernel(CombineArgs a) {
+  const uint32_t d = threadIdx.x;
+  if ((int32_t)d >= a.E) return;
+  const uint32_t l = blockIdx.x % (uint32_t)a.L, bh = blockIdx.x / (uint32_t)a.L;
+  const uint32_t head = bh % (uint32_t)a.H, b = bh / (uint32_t)a.H;
+  const uint32_t G = (uint32_t)a.H / (uint32_t)a.HKV;
+  const uint32_t kvh = head / G, r = (head % G) * (uint32_t)a.L + l;
+  const int64_t first = ((int64_t)b * a.HKV + kvh) * a.splits;
+  float m = -INFINITY;
+  for (int32_t i = 0; i < a.splits; ++i) m = fmaxf(m, a.ws_m[(first + i) * a.rows + r]);
+  float x = 0.0f;
+  if (m != -INFINITY) {
+    float num = 0.0f, den = 0.0f;
+    for (int32_t i = 0; i < a.splits; ++i) {
+      const int64_t part = (first + i) * a.rows + r;
+      const float mi = a.ws_m[part];
+      if (mi == -INFINITY) continue;
+      const float f = expf(mi - m);
+      num += f * a.ws_o[part * a.E + d];
+      den += f * a.ws_l[part];
+    }
+    x = num / den;
+  }
+  if (a.out_scale) {  // A1 then A2 on the fp32 value
+    const float s = a.out_scale[0], o = a.out_offset ? rne(a.out_offset[0]) : 0.0f;
+    const float code = __builtin_amdgcn_fmed3f(rne(x / s - o), a.lo, a.hi);
+    x = (code + o) * s;
+  }
+  a.out[(((int64_t)b * a.H + head) * a.L + l) * a.E + d] = from_f32<F16>(x);
+}
+
+// ---- the split plan ----------------------------------------------------------------------------------------------------------
+constexpr int64_t kCap = FFQ_SDPA_DECODE_MAX_SPLITS;
+constexpr int64_t kTargetGroups = 256;    // workgroups wanted: one per CU (E = 128 holds one workgroup per CU; docs/kernels.md: the sweep)
+constexpr int64_t kMinTilesPerSplit = 2;  // a split shorter than 256 keys pays more for its merge and its partial than it streams
+
+int64_t tiles_of(int64_t S) { return (S + kTile - 1) / kTile; }
+
+int64_t plan_splits(int64_t batch, int64_t kv_heads, int64_t S) {
+  const int64_t tiles = tiles_of(S), groups = batch * kv_heads;
+  if (tiles <= 0 || groups <= 0) return 1;
+  int64_t want = (kTargetGroups + groups - 1) / groups;
+  const int64_t most = tiles / kMinTilesPerSplit;
+  if (want > most) want = most;
+  if (want > kCap) want = kCap;
+  if (want < 1) want = 1;
+  const int64_t per = (tiles + want - 1) / want;
+  return (tiles + per - 1) / per;  // no split without a key
+}
+
+size_t workspace_bytes(int64_t batch, int64_t kv_heads, int64_t rows, int64_t E, int64_t splits) {
+  return (size_t)(batch * kv_heads * splits * rows * (E + 2)) * sizeof(float);
+}
+
+template <int E>
+void launch_partial(const DecodeArgs& a, bool f16, unsigned blocks, hipStream_t s) {
+  if (f16) sdpa_decode_partial_kernel<E, true><<<blocks, kThreads, 0, s>>>(a);
+  else sdpa_decode_partial_kernel<E, false><<<blocks, kThreads, 0, s>>>(a);
+}
+
+}  // namespace
+}  // namespace ffq
+
+using namespace ffq;
+
+extern "C" int64_t ffq_sdpa_decode_splits(int64_t batch, int64_t kv_heads, int64_t S, int64_t rows, int64_t E) {
+  (void)rows;
+  (void)E;  // (in the signature so that the rule can come to depend on them without a new entry point)
+  return plan_splits(batch, kv_heads, S);
+}
+
+extern "C" size_t ffq_sdpa_decode_workspace_bytes(int64_t batch, int64_t kv_heads, int64_t rows, int64_t E, int64_t splits) {
+  if (batch <= 0 || kv_heads <= 0 || rows <= 0 || E <= 0 || splits <= 0) return 0;
+  return workspace_bytes(batch, kv_heads, rows, E, splits);
+}
+
+extern "C" int ffq_sdpa_decode(const void* q, int q_dt, const void* k, const void* v, int dt, const float* const* deq_scale,
+                               const float* const* deq_offset, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L, int64_t S,
+                               int64_t E, const int64_t* strides, const void* mask, int mask_kind, int mask_dt, const int64_t* mask_strides,
+                               double sqrt_scale, const float* out_scale, const float* out_offset, double out_num_bits, int64_t splits,
+                               void* out, void* workspace, size_t workspace_bytes_given, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "sdpa_decode: bf16 or fp16 values");
+  if (q_dt != dt && q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "sdpa_decode: q is held in the value dtype or in int8");
+  if (!strides || !deq_scale || !deq_offset) return fail(FFQ_ERR_ARG, "sdpa_decode: NULL argument table");
+  if (q_dt == FFQ_I8 && !deq_scale[0]) return fail(FFQ_ERR_DTYPE, "sdpa_decode: int8 q codes need their scale");
+  if (!deq_scale[1] || !deq_scale[2]) return fail(FFQ_ERR_ARG, "sdpa_decode: k and v are int8 codes and need their scales");
+  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "sdpa_decode: E must be 64 or 128");
+  if (batch < 0 || L < 0 || S < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return fail(FFQ_ERR_ARG, "sdpa_decode: bad extent");
+  if (L > kRows || L * (q_heads / kv_heads) > kRows) return fail(FFQ_ERR_ARG, "sdpa_decode: L * (q_heads / kv_heads) must be <= %d", kRows);
+  if (mask_kind < MASK_NONE || mask_kind > MASK_FLOAT) return fail(FFQ_ERR_ARG, "sdpa_decode: bad mask kind");
+  if (mask_kind == MASK_FLOAT && mask_dt != FFQ_F32 && mask_dt != FFQ_BF16 && mask_dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "sdpa_decode: float mask dtype");
+  if (!out_scale && out_offset) return fail(FFQ_ERR_ARG, "sdpa_decode: an output offset needs its scale");
+  if (out_scale && !(out_num_bits >= 1.0 && out_num_bits <= 8.0 && out_num_bits == (double)(int)out_num_bits))
+    return fail(FFQ_ERR_ARG, "sdpa_decode: the output quantizer needs an integral bit-width in 1..8");
+  if (splits < 0 || splits > kCap) return fail(FFQ_ERR_ARG, "sdpa_decode: splits must be 0 (the rule) or 1..%d", (int)kCap);
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (S == 0) return fail(FFQ_ERR_ARG, "sdpa_decode: S must be >= 1");
+  if (S >= ((int64_t)1 << 30) || batch * kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "sdpa_decode: too large");
+  if (!q || !k || !v || !out) return fail(FFQ_ERR_ARG, "sdpa_decode: NULL buffer");
+  if (mask_kind >= MASK_BOOL && (!mask || !mask_strides)) return fail(FFQ_ERR_ARG, "sdpa_decode: the mask needs its data and strides");
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) return fail(FFQ_ERR_ARG, "sdpa_decode: buffers must be 16-byte aligned");
+  const int64_t q_unit = q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
+  for (int i = 0; i < 9; ++i)
+    if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "sdpa_decode: strides must be non-negative multiples of 16 bytes");
+  const int64_t rows = L * (q_heads / kv_heads);
+  const int64_t tiles = tiles_of(S);
+  const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, S);
+  const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
+  if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
+    return fail(FFQ_ERR_WORKSPACE, "sdpa_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
+
+  DecodeArgs a;
+  a.q = q; a.k = static_cast<const int8_t*>(k); a.v = static_cast<const int8_t*>(v);
+  for (int i = 0; i < 3; ++i) {
+    a.deq_s[i] = deq_scale[i];
+    a.deq_o[i] = deq_scale[i] ? deq_offset[i] : nullptr;
+    a.qs[i] = strides[i]; a.ks[i] = strides[3 + i]; a.vs[i] = strides[6 + i];
+  }
+  a.B = (int32_t)batch; a.H = (int32_t)q_heads; a.HKV = (int32_t)kv_heads; a.L = (int32_t)L; a.S = (int32_t)S;
+  a.rows = (int32_t)rows; a.splits = (int32_t)nsplit; a.tiles_per_split = (int32_t)((tiles + nsplit - 1) / nsplit);
+  a.q_i8 = q_dt == FFQ_I8;
+  a.mask = mask; a.mask_kind = mask_kind; a.mask_dt = mask_dt;
+  for (int i = 0; i < 4; ++i) a.ms[i] = mask_kind >= MASK_BOOL ? mask_strides[i] : 0;
+  a.c = (float)sqrt_scale;
+  const int64_t parts = batch * kv_heads * nsplit;
+  a.ws_o = static_cast<float*>(workspace);
+  a.ws_m = a.ws_o + parts * rows * E;
+  a.ws_l = a.ws_m + parts * rows;
+  const bool f16 = dt == FFQ_F16;
+  if (E == 64) launch_partial<64>(a, f16, (unsigned)parts, s);
+  else launch_partial<128>(a, f16, (unsigned)parts, s);
+  int rc = check_launch("sdpa_decode_partial_kernel");
+  if (rc != FFQ_OK) return rc;
+
+  CombineArgs c;
+  c.ws_o = a.ws_o; c.ws_m = a.ws_m; c.ws_l = a.ws_l;
+  c.out = static_cast<uint16_t*>(out);
+  c.H = a.H; c.HKV = a.HKV; c.L = a.L; c.E = (int32_t)E; c.rows = a.rows; c.splits = a.splits;
+  c.out_scale = out_scale; c.out_offset = out_scale ? out_offset : nullptr;
+  const double half = out_scale ? ldexp(1.0, (int)out_num_bits - 1) : 1.0;
+  c.lo = (float)-half; c.hi = (float)(half - 1.0);
+  const unsigned cblocks = (unsigned)(batch * q_heads * L);
+  if (f16) sdpa_decode_combine_kernel<true><<<cblocks, 128, 0, s>>>(c);
+  else sdpa_decode_combine_kernel<false><<<cblocks, 128, 0, s>>>(c);
+  return check_launch("sdpa_decode_combine_kernel");
+}

@@ -1,0 +1,142 @@
+"""``scaled_dot_product_attention`` for a short query over int8 K / V codes — a quantized KV cache — split over the keys
+(csrc/ffq_sdpa_decode.hip, include/ffq_sdpa_decode.h): two plain launches. The partial kernel gives one workgroup to every (batch,
+kv head, key split), with the ``rows = L * (H_q / H)`` query rows of that kv head on one MFMA tile, so the codes are read once per
+(batch, kv head); the combine kernel merges the splits' fp32 partials, applies the optional output quantizer and rounds once.
+
+k / v are int8 codes with per-tensor ``(scale, offset)`` in ``dequant[1]`` / ``dequant[2]``; q is plain bf16 / fp16 (``dequant[0]``
+None) or per-tensor codes of it in that dtype or in int8. Returns the value [B, H_q, L, E] in the data dtype."""
+
+from __future__ import annotations
+
+import ctypes
+import math
+
+from typing import Sequence
+
+import torch
+
+from fastforward_amd import _cabi
+from fastforward_amd.ops import _base
+from fastforward_amd.ops._base import _ptr, _tag
+from fastforward_amd.ops.modules import _entry
+from fastforward_amd.ops.sdpa import MASK_KINDS, _scalar, _strides
+
+MAX_ROWS = _cabi.SDPA_DECODE_MAX_ROWS
+KEY_TILE = _cabi.SDPA_DECODE_KEY_TILE
+MAX_SPLITS = _cabi.SDPA_DECODE_MAX_SPLITS
+TARGET_GROUPS = 256  # workgroups the rule asks for: one per compute unit (docs/kernels.md has the sweep)
+MIN_TILES_PER_SPLIT = 2
+
+Dequant = tuple[torch.Tensor, torch.Tensor | None]
+
+
+def sdpa_decode_plan(B: int, HKV: int, S: int, rows: int = 1, E: int = 128) -> int:
+    """The number of key splits the kernel takes at ``splits=0``: ``ffq_sdpa_decode_splits`` restated (a pure function of the
+    shape, so the same under graph capture). Every split takes ``ceil(tiles / splits)`` tiles of ``KEY_TILE`` keys, the last one
+    what is left; none is empty."""
+    tiles, groups = -(-S // KEY_TILE), B * HKV
+    if tiles <= 0 or groups <= 0:
+        return 1
+    want = max(1, min(-(-TARGET_GROUPS // groups), tiles // MIN_TILES_PER_SPLIT, MAX_SPLITS))
+    per = -(-tiles // want)
+    return -(-tiles // per)
+
+
+def sdpa_decode_split_ranges(S: int, splits: int) -> list[tuple[int, int]]:
+    """The keys ``[begin, end)`` of each of `splits` splits (a forced split may be empty)."""
+    per = -(-(-(-S // KEY_TILE)) // splits) * KEY_TILE
+    return [(min(i * per, S), min((i + 1) * per, S)) for i in range(splits)]
+
+
+def sdpa_decode_workspace_bytes(B: int, HKV: int, rows: int, E: int, splits: int) -> int:
+    """``ffq_sdpa_decode_workspace_bytes`` restated: O[rows][E], m[rows] and l[rows] in fp32 for every (batch, kv head, split)."""
+    return 0 if min(B, HKV, rows, E, splits) <= 0 else B * HKV * splits * rows * (E + 2) * 4
+
+
+def sdpa_decode(
+    query: torch.Tensor,
+    key: torch.Tensor,
+    value: torch.Tensor,
+    attn_mask: torch.Tensor | None = None,
+    is_causal: bool = False,
+    scale: float | None = None,
+    output_quantizer: tuple[torch.Tensor, torch.Tensor | None, float] | None = None,
+    dequant: Sequence[Dequant | None] = (None, None, None),
+    dtype: torch.dtype | None = None,
+    splits: int = 0,
+) -> torch.Tensor:
+    """One call of ``ffq_sdpa_decode``. query [B, H_q, L, E] in `dtype` (bf16 / fp16; plain, or codes with ``dequant[0]``) or int8
+    codes; key / value [B, H, S, E] int8 codes with ``dequant[1]`` / ``dequant[2]``; ``L * (H_q / H) <= 32``; E in {64, 128}; the last
+    dimension contiguous and rows 16-byte aligned, any other strides. `attn_mask` (bool or float, last two dims [L, S]) broadcasts over
+    the leading dims and excludes `is_causal` (top-left). `output_quantizer` is ``(scale, offset, num_bits)``. ``splits=0`` takes the
+    rule (:func:`sdpa_decode_plan`); ``1 .. MAX_SPLITS`` forces a count."""
+    if query.dim() != 4 or key.dim() != 4 or value.dim() != 4:
+        raise RuntimeError("sdpa_decode: q / k / v are 4-D [B, H, L|S, E]")
+    if key.dtype != torch.int8 or value.dtype != torch.int8 or dequant[1] is None or dequant[2] is None:
+        raise RuntimeError(f"sdpa_decode: k / v are int8 codes with their (scale, offset), got {key.dtype}, {value.dtype}")
+    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
+    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
+        raise RuntimeError(f"sdpa_decode: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
+    if query.dtype == torch.int8 and dequant[0] is None:
+        raise RuntimeError("sdpa_decode: int8 q codes need their (scale, offset)")
+    B, H, L, E = query.shape
+    _, HKV, S, _ = key.shape
+    if key.shape[0] != B or key.shape[3] != E or tuple(value.shape) != (B, HKV, S, E):
+        raise RuntimeError(f"sdpa_decode: shapes {tuple(query.shape)}, {tuple(key.shape)}, {tuple(value.shape)} do not fit")
+    if E not in (64, 128):
+        raise RuntimeError(f"sdpa_decode: E must be 64 or 128, got {E}")
+    if HKV < 1 or H % HKV:
+        raise RuntimeError(f"sdpa_decode: {H} query heads are not a multiple of {HKV} kv heads")
+    rows = L * (H // HKV)
+    if rows > MAX_ROWS:
+        raise RuntimeError(f"sdpa_decode: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
+    if min(B, L, S) < 1:
+        raise RuntimeError(f"sdpa_decode: empty operands {tuple(query.shape)}, {tuple(key.shape)}")
+    if not 0 <= splits <= MAX_SPLITS:
+        raise RuntimeError(f"sdpa_decode: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
+    for t in (query, key, value):
+        if t.stride(-1) != 1 or any(st * t.element_size() % 16 for st in _strides(t)) or t.data_ptr() % 16:
+            raise RuntimeError("sdpa_decode: the last dimension must be contiguous with 16-byte aligned rows")
+    if attn_mask is not None and is_causal:
+        raise ValueError("Explicit attn_mask should not be set when is_causal=True")
+    mask, mask_kind, mask_dt, mask_strides = None, MASK_KINDS["causal" if is_causal else "none"], _tag(torch.float32), None
+    if attn_mask is not None:
+        if not 2 <= attn_mask.dim() <= 4 or tuple(attn_mask.shape[-2:]) != (L, S):
+            raise RuntimeError(f"sdpa_decode: the mask's last two dims must be [{L}, {S}], got {tuple(attn_mask.shape)}")
+        mask = attn_mask.detach().expand(B, H, L, S)
+        if mask.dtype == torch.bool:
+            mask_kind = MASK_KINDS["bool"]
+        elif mask.dtype in (torch.float32, torch.bfloat16, torch.float16):
+            mask_kind, mask_dt = MASK_KINDS["float"], _tag(mask.dtype)
+        else:
+            raise RuntimeError(f"sdpa_decode: a mask is bool or float, got {mask.dtype}")
+        mask_strides = (ctypes.c_int64 * 4)(*mask.stride())
+    keep: list[torch.Tensor] = []
+    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
+    for i, d in enumerate(dequant):
+        if d is not None:
+            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
+            keep += [t for t in (s, o) if t is not None]
+            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
+    out_s = out_o = None
+    bits = 8.0
+    if output_quantizer is not None:
+        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
+        bits = float(output_quantizer[2])
+        keep += [t for t in (out_s, out_o) if t is not None]
+    lib, stream = _base._prepare(query, key, value, mask, *keep)
+    entry = _entry(lib, "ffq_sdpa_decode")
+    count = splits or int(_entry(lib, "ffq_sdpa_decode_splits")(B, HKV, S, rows, E))
+    nbytes = int(_entry(lib, "ffq_sdpa_decode_workspace_bytes")(B, HKV, rows, E, count))
+    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(key), *_strides(value))
+    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
+    lib.check(
+        entry(
+            _ptr(query), _tag(query.dtype), _ptr(key), _ptr(value), _tag(dt), deq_s, deq_o, B, H, HKV, L, S, E, strides, _ptr(mask), mask_kind,
+            mask_dt, mask_strides, sqrt_scale, _ptr(out_s), _ptr(out_o), bits, count, _ptr(out), _ptr(workspace), nbytes, stream,
+        )
+    )
+    del keep
+    return out
