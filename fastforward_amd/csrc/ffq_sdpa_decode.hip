@@ -90,7 +90,9 @@ __device__ __forceinline__ uint32_t pack_pair(float a, float b) {
 // 4 int8 codes of one dword -> 4 dequantized values in the data dtype (two dwords): (c + o) * s in fp32, one rounding. `w` holds the
 // codes with their sign bits flipped (c + 128 as unsigned bytes: one conversion instruction each) and `o` is rne(offset) - 128, so
 // (c + 128) + (o - 128) is the one fp32 addition whose exact operands sum to c + rne(offset): the bits of (float)c + rne(offset)
-// for every |offset| < 2^31.
+// for every |rne(offset)| < 2^24 - 127, where both operands and the sum are integers below 2^24. At rne(offset) = -(2^24 - 127) the
+// bias term -(2^24 + 1) is itself rounded, and from there on the sum may differ from (float)c + rne(offset) by one fp32 ulp before
+// the product and the rounding to the data dtype (docs/numerics.md; tests/test_sdpa_decode_cases_cpu.py holds the bound).
 template <bool F16>
 __device__ __forceinline__ void dequant4(uint32_t w, float s, float o, uint32_t& lo, uint32_t& hi) {
   const float f0 = ((float)(w & 0xFFu) + o) * s;
