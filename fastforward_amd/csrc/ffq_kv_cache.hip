@@ -1,0 +1,168 @@
+// ffq_kv_cache.hip — the new K and V rows of a decode step (or of a prompt) quantized and written into a preallocated int8 cache, one
+// launch for both tensors (include/ffq_kv_cache.h). ffq_kv_decode, the attention over such a cache, lives beside the kernels it runs
+// (ffq_sdpa_decode.hip).
+//
+// kv_append_kernel: one lane = 16 elements of one new row (batch b, kv head, l) of K and the same 16 of V. The row's position is
+// pos = lens[b] - L + l: `lens` is read, never written (the caller has advanced it with an ordinary add on the stream), so no
+// workgroup races another on it; a row whose position falls outside [0, S_max) is dropped before any load.
+//   * plain: the lane takes columns [16 j, +16) of both tensors: two 16-byte loads and one 16-byte store each;
+//   * rotary: for K the lane takes [8 j, +8) of BOTH halves (rope_kernel's split, ffq_producers.hip), so it holds x1 and x2 of the
+//     eight rotations it computes: rd(rd(x1 cos_lo) + rd(-x2 sin_lo)), rd(rd(x2 cos_hi) + rd(x1 sin_hi)) with the table row `pos`,
+//     rd rounding to the data dtype; 16-byte loads, two 8-byte stores. V goes the plain way.
+// A1 is quantize_chunk_to_bytes (ffq_affine.h): the codes of ffq_quantize_by_tile, NaN and +-Inf included. Every index is 64-bit.
+// No LDS, no scratch.
+#include "ffq_affine.h"
+#include "ffq_common.h"
+#include "ffq_vec.h"
+
+#include "../../include/ffq_kv_cache.h"
+
+#include <math.h>
+
+namespace ffq {
+namespace {
+
+struct AppendArgs {
+  const void* kn;
+  const void* vn;
+  int8_t* kc;
+  int8_t* vc;
+  const int32_t* lens;
+  const void* cos;
+  const void* sin;
+  const float* ks;
+  const float* ko;  // nullable
+  const float* vs;
+  const float* vo;  // nullable
+  int64_t kns[3], vns[3], kcs[3], vcs[3];  // element strides of (batch, head, row)
+  int64_t items;                           // batch * kv_heads * L * (E / 16)
+  int64_t L;                               // (not capped: a prompt goes through the same call)
+  int32_t HKV, S_max, E, chunk_shift;      // E / 16 = 1 << chunk_shift
+  float klo, khi, vlo, vhi;
+};
+
+template <typename T>
+__device__ __forceinline__ float rd(float v) {
+  return to_f32(from_f32<T>(v));
+}
+
+// 16 contiguous values -> 16 codes
+template <typename T>
+__device__ __forceinline__ void append16(const T* src, int8_t* dst, float s, float o, float lo, float hi) {
+  Chunk<T, 16> x;
+  x.load(src);
+  float xf[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) xf[i] = x.get(i);
+  Chunk<int8_t, 16> y;
+  quantize_chunk_to_bytes<16>(xf, s, o, lo, hi, y);
+  y.store(dst);
+}
+
+template <typename T, bool ROPE>
+__global__ __launch_bounds__(kBlock) void kv_append_kernel(AppendArgs a) {
+  const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (item >= a.items) return;
+  const int64_t j = item & (((int64_t)1 << a.chunk_shift) - 1);
+  const int64_t row = item >> a.chunk_shift;
+  const int64_t l = row % a.L, bh = row / a.L;
+  const int64_t kvh = bh % a.HKV, b = bh / a.HKV;
+  const int64_t pos = (int64_t)a.lens[b] - a.L + l;
+  if (pos < 0 || pos >= a.S_max) return;
+
+  const T* kn = static_cast<const T*>(a.kn) + b * a.kns[0] + kvh * a.kns[1] + l * a.kns[2];
+  const T* vn = static_cast<const T*>(a.vn) + b * a.vns[0] + kvh * a.vns[1] + l * a.vns[2];
+  int8_t* kc = a.kc + b * a.kcs[0] + kvh * a.kcs[1] + pos * a.kcs[2];
+  int8_t* vc = a.vc + b * a.vcs[0] + kvh * a.vcs[1] + pos * a.vcs[2];
+  const float ks = a.ks[0], ko = a.ko ? rne(a.ko[0]) : 0.0f;
+  const float vs = a.vs[0], vo = a.vo ? rne(a.vo[0]) : 0.0f;
+
+  append16<T>(vn + j * 16, vc + j * 16, vs, vo, a.vlo, a.vhi);
+  if constexpr (!ROPE) {
+    append16<T>(kn + j * 16, kc + j * 16, ks, ko, a.klo, a.khi);
+  } else {
+    const int64_t half = a.E / 2;
+    const T* cr = static_cast<const T*>(a.cos) + pos * a.E;
+    const T* sr = static_cast<const T*>(a.sin) + pos * a.E;
+    Chunk<T, 8> x1c, x2c, cl, ch, sl, sh;
+    x1c.load(kn + j * 8);
+    x2c.load(kn + half + j * 8);
+    cl.load(cr + j * 8);
+    ch.load(cr + half + j * 8);
+    sl.load(sr + j * 8);
+    sh.load(sr + half + j * 8);
+    float ol[8], oh[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float x1 = x1c.get(i), x2 = x2c.get(i);
+      const float p = rd<T>(x1 * cl.get(i)), q = rd<T>((-x2) * sl.get(i));
+      const float r = rd<T>(x2 * ch.get(i)), t = rd<T>(x1 * sh.get(i));
+      ol[i] = rd<T>(p + q);
+      oh[i] = rd<T>(r + t);
+    }
+    Chunk<int8_t, 8> yl, yh;
+    quantize_chunk_to_bytes<8>(ol, ks, ko, a.klo, a.khi, yl);
+    quantize_chunk_to_bytes<8>(oh, ks, ko, a.klo, a.khi, yh);
+    yl.store(kc + j * 8);
+    yh.store(kc + half + j * 8);
+  }
+}
+
+bool bits_ok(double bits) { return bits >= 2.0 && bits <= 8.0 && bits == (double)(int)bits; }
+
+template <typename T>
+void launch_append(const AppendArgs& a, bool rope, unsigned blocks, hipStream_t s) {
+  if (rope) kv_append_kernel<T, true><<<blocks, kBlock, 0, s>>>(a);
+  else kv_append_kernel<T, false><<<blocks, kBlock, 0, s>>>(a);
+}
+
+}  // namespace
+}  // namespace ffq
+
+using namespace ffq;
+
+extern "C" int ffq_kv_append(const void* k_new, const void* v_new, int dt, void* k_cache, void* v_cache, const void* lens, int64_t batch,
+                             int64_t kv_heads, int64_t L, int64_t S_max, int64_t E, const int64_t* strides, const float* k_scale,
+                             const float* k_offset, double k_num_bits, const float* v_scale, const float* v_offset, double v_num_bits,
+                             const void* cos_table, const void* sin_table, int64_t table_rows, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_append: bf16 or fp16 values");
+  if (!strides) return fail(FFQ_ERR_ARG, "kv_append: NULL strides table");
+  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_append: E must be 64 or 128");
+  if (batch < 0 || L < 0 || S_max < 0 || kv_heads <= 0) return fail(FFQ_ERR_ARG, "kv_append: bad extent");
+  if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "kv_append: the quantizers need an integral bit-width in 2..8");
+  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "kv_append: a quantizer (and its offset) needs its scale");
+  if (!cos_table != !sin_table) return fail(FFQ_ERR_ARG, "kv_append: the rotary tables come as a pair");
+  if (cos_table && table_rows < S_max) return fail(FFQ_ERR_ARG, "kv_append: the rotary tables need a row for every cache position (%lld < %lld)", (long long)table_rows, (long long)S_max);
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (S_max >= ((int64_t)1 << 30) || batch >= ((int64_t)1 << 31) || kv_heads >= ((int64_t)1 << 31) || L >= ((int64_t)1 << 40) ||
+      (double)batch * (double)kv_heads * (double)L * (double)E >= 0x1p40)
+    return fail(FFQ_ERR_ARG, "kv_append: too large");
+  if (!aligned16(k_new) || !aligned16(v_new) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(cos_table) || !aligned16(sin_table) ||
+      (reinterpret_cast<uintptr_t>(lens) & 3u))
+    return fail(FFQ_ERR_ARG, "kv_append: buffers must be 16-byte aligned (lens: 4-byte)");
+  for (int i = 0; i < 12; ++i)
+    if (strides[i] < 0 || strides[i] % (i < 6 ? 8 : 16)) return fail(FFQ_ERR_ARG, "kv_append: strides must be non-negative multiples of 16 bytes");
+  if (!k_new || !v_new || !k_cache || !v_cache || !lens) return fail(FFQ_ERR_ARG, "kv_append: NULL buffer");
+  if (S_max == 0) return FFQ_OK;  // (no position to write to)
+
+  AppendArgs a;
+  a.kn = k_new; a.vn = v_new;
+  a.kc = static_cast<int8_t*>(k_cache); a.vc = static_cast<int8_t*>(v_cache);
+  a.lens = static_cast<const int32_t*>(lens);
+  a.cos = cos_table; a.sin = sin_table;
+  a.ks = k_scale; a.ko = k_offset; a.vs = v_scale; a.vo = v_offset;
+  for (int i = 0; i < 3; ++i) {
+    a.kns[i] = strides[i]; a.vns[i] = strides[3 + i]; a.kcs[i] = strides[6 + i]; a.vcs[i] = strides[9 + i];
+  }
+  a.L = L; a.HKV = (int32_t)kv_heads; a.S_max = (int32_t)S_max; a.E = (int32_t)E;
+  a.chunk_shift = E == 64 ? 2 : 3;
+  a.items = batch * kv_heads * L * (E / 16);
+  const double khalf = ldexp(1.0, (int)k_num_bits - 1), vhalf = ldexp(1.0, (int)v_num_bits - 1);
+  a.klo = (float)-khalf; a.khi = (float)(khalf - 1.0);
+  a.vlo = (float)-vhalf; a.vhi = (float)(vhalf - 1.0);
+  const unsigned blocks = (unsigned)((a.items + kBlock - 1) / kBlock);
+  if (dt == FFQ_F16) launch_append<f16_t>(a, cos_table != nullptr, blocks, s);
+  else launch_append<bf16_t>(a, cos_table != nullptr, blocks, s);
+  return check_launch("kv_append_kernel");
+}

@@ -27,10 +27,15 @@
 // of ffq_sdpa.hip) and one rounding to the data dtype.
 //
 // The split plan is a pure function of (B, HKV, S, rows, E): no device state, graph-safe (docs/kernels.md has the sweep).
+//
+// ffq_kv_decode (include/ffq_kv_cache.h) runs the same two kernels over a preallocated cache: the split COUNT is still a host
+// integer, but every batch reads its own key count from `lens` on the device and cuts it over that count by the same rule, and the
+// causal mask is bottom-right. Both entry points share the kernels' instantiations: the difference is a launch-uniform null check.
 #include "ffq_affine.h"
 #include "ffq_common.h"
 #include "ffq_vec.h"
 
+#include "../../include/ffq_kv_cache.h"
 #include "../../include/ffq_sdpa_decode.h"
 
 #include <math.h>
@@ -71,6 +76,10 @@ struct DecodeArgs {
   float* ws_o;
   float* ws_m;
   float* ws_l;
+  // ffq_kv_decode (include/ffq_kv_cache.h): the key count of every batch on the device. nullptr: S and tiles_per_split above hold
+  // for every batch. Else S is S_max, batch b has S_b = clamp(lens[b], 0, S) keys, cut over `splits` by the same rule, and
+  // MASK_CAUSAL is bottom-right: row l sees key <= l + (S_b - L)
+  const int32_t* lens;
 };
 
 template <bool F16>
@@ -166,11 +175,19 @@ __global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArg
   const uint32_t kvh = bk % (uint32_t)a.HKV, b = bk / (uint32_t)a.HKV;
   const uint32_t G = (uint32_t)a.H / (uint32_t)a.HKV;
 
+  // this batch's keys, tiles per split and causal diagonal: the launch's, or (a cache with device-side lengths) its own
+  int32_t S = a.S, per = a.tiles_per_split, diag = 0;
+  if (a.lens != nullptr) {
+    const int32_t n = a.lens[b];
+    S = n < 0 ? 0 : (n < a.S ? n : a.S);
+    per = ((S + kTile - 1) / kTile + a.splits - 1) / a.splits;
+    diag = S - a.L;
+  }
   // the split's keys [k_begin, k_end): whole tiles but for the last split; a forced split may be empty
-  const int64_t first = (int64_t)sp * a.tiles_per_split * kTile;
-  const int32_t k_begin = first < a.S ? (int32_t)first : a.S;
-  const int64_t last = first + (int64_t)a.tiles_per_split * kTile;
-  const int32_t k_end = last < a.S ? (int32_t)last : a.S;
+  const int64_t first = (int64_t)sp * per * kTile;
+  const int32_t k_begin = first < S ? (int32_t)first : S;
+  const int64_t last = first + (int64_t)per * kTile;
+  const int32_t k_end = last < S ? (int32_t)last : S;
   const int32_t iters = (k_end - k_begin + kTile - 1) / kTile;  // the same for the four waves: the barriers below are uniform
 
   // this lane's query row
@@ -285,7 +302,7 @@ __global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArg
     for (int e = 0; e < 16; ++e) s[e] *= alpha;
     if (a.mask_kind == MASK_CAUSAL) {
 #pragma unroll
-      for (int e = 0; e < 16; ++e) s[e] = key_of(e) <= (int32_t)l ? s[e] : -INFINITY;
+      for (int e = 0; e < 16; ++e) s[e] = key_of(e) <= (int32_t)l + diag ? s[e] : -INFINITY;
     } else if (a.mask_kind == MASK_BOOL) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
@@ -477,6 +494,49 @@ void launch_partial(const DecodeArgs& a, bool f16, unsigned blocks, hipStream_t 
   else sdpa_decode_partial_kernel<E, false><<<blocks, kThreads, 0, s>>>(a);
 }
 
+// the two launches, after an entry point's checks. `lens` nullptr: S keys for every batch (ffq_sdpa_decode); else S is S_max
+int enqueue(const void* q, int q_dt, const void* k, const void* v, int dt, const float* const* deq_scale, const float* const* deq_offset,
+            const int32_t* lens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L, int64_t S, int64_t E, const int64_t* strides,
+            const void* mask, int mask_kind, int mask_dt, const int64_t* mask_strides, double sqrt_scale, const float* out_scale,
+            const float* out_offset, double out_num_bits, int64_t nsplit, void* out, void* workspace, hipStream_t s) {
+  const int64_t rows = L * (q_heads / kv_heads);
+  DecodeArgs a;
+  a.q = q; a.k = static_cast<const int8_t*>(k); a.v = static_cast<const int8_t*>(v);
+  for (int i = 0; i < 3; ++i) {
+    a.deq_s[i] = deq_scale[i];
+    a.deq_o[i] = deq_scale[i] ? deq_offset[i] : nullptr;
+    a.qs[i] = strides[i]; a.ks[i] = strides[3 + i]; a.vs[i] = strides[6 + i];
+  }
+  a.B = (int32_t)batch; a.H = (int32_t)q_heads; a.HKV = (int32_t)kv_heads; a.L = (int32_t)L; a.S = (int32_t)S;
+  a.rows = (int32_t)rows; a.splits = (int32_t)nsplit; a.tiles_per_split = (int32_t)((tiles_of(S) + nsplit - 1) / nsplit);
+  a.q_i8 = q_dt == FFQ_I8;
+  a.mask = mask; a.mask_kind = mask_kind; a.mask_dt = mask_dt;
+  for (int i = 0; i < 4; ++i) a.ms[i] = mask_kind >= MASK_BOOL ? mask_strides[i] : 0;
+  a.c = (float)sqrt_scale;
+  a.lens = lens;
+  const int64_t parts = batch * kv_heads * nsplit;
+  a.ws_o = static_cast<float*>(workspace);
+  a.ws_m = a.ws_o + parts * rows * E;
+  a.ws_l = a.ws_m + parts * rows;
+  const bool f16 = dt == FFQ_F16;
+  if (E == 64) launch_partial<64>(a, f16, (unsigned)parts, s);
+  else launch_partial<128>(a, f16, (unsigned)parts, s);
+  int rc = check_launch("sdpa_decode_partial_kernel");
+  if (rc != FFQ_OK) return rc;
+
+  CombineArgs c;
+  c.ws_o = a.ws_o; c.ws_m = a.ws_m; c.ws_l = a.ws_l;
+  c.out = static_cast<uint16_t*>(out);
+  c.H = a.H; c.HKV = a.HKV; c.L = a.L; c.E = (int32_t)E; c.rows = a.rows; c.splits = a.splits;
+  c.out_scale = out_scale; c.out_offset = out_scale ? out_offset : nullptr;
+  const double half = out_scale ? ldexp(1.0, (int)out_num_bits - 1) : 1.0;
+  c.lo = (float)-half; c.hi = (float)(half - 1.0);
+  const unsigned cblocks = (unsigned)(batch * q_heads * L);
+  if (f16) sdpa_decode_combine_kernel<true><<<cblocks, 128, 0, s>>>(c);
+  else sdpa_decode_combine_kernel<false><<<cblocks, 128, 0, s>>>(c);
+  return check_launch("sdpa_decode_combine_kernel");
+}
+
 }  // namespace
 }  // namespace ffq
 
@@ -523,44 +583,49 @@ extern "C" int ffq_sdpa_decode(const void* q, int q_dt, const void* k, const voi
   for (int i = 0; i < 9; ++i)
     if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "sdpa_decode: strides must be non-negative multiples of 16 bytes");
   const int64_t rows = L * (q_heads / kv_heads);
-  const int64_t tiles = tiles_of(S);
   const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, S);
   const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
   if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
     return fail(FFQ_ERR_WORKSPACE, "sdpa_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
+  return enqueue(q, q_dt, k, v, dt, deq_scale, deq_offset, nullptr, batch, q_heads, kv_heads, L, S, E, strides, mask, mask_kind, mask_dt,
+                 mask_strides, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out, workspace, s);
+}
 
-  DecodeArgs a;
-  a.q = q; a.k = static_cast<const int8_t*>(k); a.v = static_cast<const int8_t*>(v);
-  for (int i = 0; i < 3; ++i) {
-    a.deq_s[i] = deq_scale[i];
-    a.deq_o[i] = deq_scale[i] ? deq_offset[i] : nullptr;
-    a.qs[i] = strides[i]; a.ks[i] = strides[3 + i]; a.vs[i] = strides[6 + i];
-  }
-  a.B = (int32_t)batch; a.H = (int32_t)q_heads; a.HKV = (int32_t)kv_heads; a.L = (int32_t)L; a.S = (int32_t)S;
-  a.rows = (int32_t)rows; a.splits = (int32_t)nsplit; a.tiles_per_split = (int32_t)((tiles + nsplit - 1) / nsplit);
-  a.q_i8 = q_dt == FFQ_I8;
-  a.mask = mask; a.mask_kind = mask_kind; a.mask_dt = mask_dt;
-  for (int i = 0; i < 4; ++i) a.ms[i] = mask_kind >= MASK_BOOL ? mask_strides[i] : 0;
-  a.c = (float)sqrt_scale;
-  const int64_t parts = batch * kv_heads * nsplit;
-  a.ws_o = static_cast<float*>(workspace);
-  a.ws_m = a.ws_o + parts * rows * E;
-  a.ws_l = a.ws_m + parts * rows;
-  const bool f16 = dt == FFQ_F16;
-  if (E == 64) launch_partial<64>(a, f16, (unsigned)parts, s);
-  else launch_partial<128>(a, f16, (unsigned)parts, s);
-  int rc = check_launch("sdpa_decode_partial_kernel");
-  if (rc != FFQ_OK) return rc;
-
-  CombineArgs c;
-  c.ws_o = a.ws_o; c.ws_m = a.ws_m; c.ws_l = a.ws_l;
-  c.out = static_cast<uint16_t*>(out);
-  c.H = a.H; c.HKV = a.HKV; c.L = a.L; c.E = (int32_t)E; c.rows = a.rows; c.splits = a.splits;
-  c.out_scale = out_scale; c.out_offset = out_scale ? out_offset : nullptr;
-  const double half = out_scale ? ldexp(1.0, (int)out_num_bits - 1) : 1.0;
-  c.lo = (float)-half; c.hi = (float)(half - 1.0);
-  const unsigned cblocks = (unsigned)(batch * q_heads * L);
-  if (f16) sdpa_decode_combine_kernel<true><<<cblocks, 128, 0, s>>>(c);
-  else sdpa_decode_combine_kernel<false><<<cblocks, 128, 0, s>>>(c);
-  return check_launch("sdpa_decode_combine_kernel");
+extern "C" int ffq_kv_decode(const void* q, int q_dt, const void* k, const void* v, int dt, const float* const* deq_scale,
+                             const float* const* deq_offset, const void* lens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L,
+                             int64_t S_max, int64_t E, const int64_t* strides, int causal, double sqrt_scale, const float* out_scale,
+                             const float* out_offset, double out_num_bits, int64_t splits, int64_t plan_len, void* out, void* workspace,
+                             size_t workspace_bytes_given, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_decode: bf16 or fp16 values");
+  if (q_dt != dt && q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "kv_decode: q is held in the value dtype or in int8");
+  if (!strides || !deq_scale || !deq_offset) return fail(FFQ_ERR_ARG, "kv_decode: NULL argument table");
+  if (q_dt == FFQ_I8 && !deq_scale[0]) return fail(FFQ_ERR_DTYPE, "kv_decode: int8 q codes need their scale");
+  if (!deq_scale[1] || !deq_scale[2]) return fail(FFQ_ERR_ARG, "kv_decode: k and v are int8 codes and need their scales");
+  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_decode: E must be 64 or 128");
+  if (batch < 0 || L < 0 || S_max < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return fail(FFQ_ERR_ARG, "kv_decode: bad extent");
+  if (L > kRows || L * (q_heads / kv_heads) > kRows) return fail(FFQ_ERR_ARG, "kv_decode: L * (q_heads / kv_heads) must be <= %d", kRows);
+  if (causal != 0 && causal != 1) return fail(FFQ_ERR_ARG, "kv_decode: causal is 0 (every key) or 1 (bottom-right)");
+  if (!out_scale && out_offset) return fail(FFQ_ERR_ARG, "kv_decode: an output offset needs its scale");
+  if (out_scale && !(out_num_bits >= 1.0 && out_num_bits <= 8.0 && out_num_bits == (double)(int)out_num_bits))
+    return fail(FFQ_ERR_ARG, "kv_decode: the output quantizer needs an integral bit-width in 1..8");
+  if (splits < 0 || splits > kCap) return fail(FFQ_ERR_ARG, "kv_decode: splits must be 0 (the rule) or 1..%d", (int)kCap);
+  if (plan_len < 0 || plan_len > S_max) return fail(FFQ_ERR_ARG, "kv_decode: plan_len must be 0 (S_max) or 1..S_max");
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (S_max == 0) return fail(FFQ_ERR_ARG, "kv_decode: S_max must be >= 1");
+  if (S_max >= ((int64_t)1 << 30) || batch * kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "kv_decode: too large");
+  if (!q || !k || !v || !out || !lens) return fail(FFQ_ERR_ARG, "kv_decode: NULL buffer");
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (reinterpret_cast<uintptr_t>(lens) & 3u))
+    return fail(FFQ_ERR_ARG, "kv_decode: buffers must be 16-byte aligned (lens: 4-byte)");
+  const int64_t q_unit = q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
+  for (int i = 0; i < 9; ++i)
+    if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "kv_decode: strides must be non-negative multiples of 16 bytes");
+  const int64_t rows = L * (q_heads / kv_heads);
+  const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, plan_len ? plan_len : S_max);
+  const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
+  if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
+    return fail(FFQ_ERR_WORKSPACE, "kv_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
+  return enqueue(q, q_dt, k, v, dt, deq_scale, deq_offset, static_cast<const int32_t*>(lens), batch, q_heads, kv_heads, L, S_max, E, strides,
+                 nullptr, causal ? MASK_CAUSAL : MASK_NONE, FFQ_F32, nullptr, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out,
+                 workspace, s);
 }

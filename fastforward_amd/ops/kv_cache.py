@@ -1,0 +1,177 @@
+"""A preallocated int8 KV cache on the kernels of csrc/ffq_kv_cache.hip and csrc/ffq_sdpa_decode.hip (include/ffq_kv_cache.h).
+
+``kv_append`` is one launch: the new K / V rows quantized (A1, per-tensor static quantizers) and written into the two cache buffers at
+every sequence's own position, K optionally rotated on the way. ``kv_decode`` is ``sdpa_decode`` with the key count of every
+sequence read on the device: the split count stays a host integer (so the call is the same under graph capture whatever the lengths
+become), each batch cuts its own keys over it, and ``causal`` is bottom-right. `lens` (int32 ``[B]``) is read by both and written by
+neither: the caller advances it with ``lens.add_(L)`` on the stream ahead of ``kv_append``."""
+
+from __future__ import annotations
+
+import ctypes
+import math
+
+from typing import Sequence
+
+import torch
+
+from fastforward_amd.ops import _base
+from fastforward_amd.ops._base import _ptr, _tag
+from fastforward_amd.ops.decode import MAX_ROWS, MAX_SPLITS, Dequant
+from fastforward_amd.ops.modules import _entry
+from fastforward_amd.ops.sdpa import _scalar, _strides
+
+Quantizer = tuple[torch.Tensor, "torch.Tensor | None", float]
+
+
+def _rows_ok(t: torch.Tensor) -> bool:
+    return t.stride(-1) == 1 and not any(st * t.element_size() % 16 for st in _strides(t)) and t.data_ptr() % 16 == 0
+
+
+def _lens_ok(lens: torch.Tensor, B: int) -> bool:
+    return lens.dtype == torch.int32 and tuple(lens.shape) == (B,) and lens.is_contiguous()
+
+
+def kv_append(
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    lens: torch.Tensor,
+    k_quantizer: Quantizer,
+    v_quantizer: Quantizer,
+    rope: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> None:
+    """One call of ``ffq_kv_append``. k_new / v_new [B, H, L, E] plain bf16 / fp16; k_cache / v_cache int8 [B, H, S_max, E]; E in
+    {64, 128}; the last dimension contiguous and rows 16-byte aligned, any other strides. `lens` int32 [B] holds every sequence's length
+    INCLUDING these L rows: row l goes to position ``lens[b] - L + l``, and a row outside ``[0, S_max)`` is skipped. The quantizers are
+    ``(scale, offset, num_bits)``, per-tensor, 2..8 bits. ``rope=(cos, sin)``, [P, E] tables in the data dtype with ``P >= S_max``: K is
+    rotated with the row of its position before it is quantized."""
+    if k_new.dim() != 4 or v_new.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise RuntimeError("kv_append: the new rows and the caches are 4-D [B, H, L|S_max, E]")
+    dt = k_new.dtype
+    if dt not in (torch.bfloat16, torch.float16) or v_new.dtype != dt:
+        raise RuntimeError(f"kv_append: the new rows are bf16 or fp16, both the same, got {k_new.dtype} and {v_new.dtype}")
+    if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8:
+        raise RuntimeError(f"kv_append: the caches hold int8 codes, got {k_cache.dtype}, {v_cache.dtype}")
+    B, HKV, L, E = k_new.shape
+    S_max = k_cache.shape[2]
+    if tuple(v_new.shape) != (B, HKV, L, E) or tuple(k_cache.shape) != (B, HKV, S_max, E) or tuple(v_cache.shape) != (B, HKV, S_max, E):
+        raise RuntimeError(f"kv_append: shapes {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)} do not fit")
+    if E not in (64, 128):
+        raise RuntimeError(f"kv_append: E must be 64 or 128, got {E}")
+    if HKV < 1:
+        raise RuntimeError("kv_append: no kv head")
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"kv_append: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    for t in (k_new, v_new, k_cache, v_cache):
+        if not _rows_ok(t):
+            raise RuntimeError("kv_append: the last dimension must be contiguous with 16-byte aligned rows")
+    cos = sin = None
+    if rope is not None:
+        cos, sin = rope
+        for t in (cos, sin):
+            if t.dtype != dt or t.dim() != 2 or t.shape[1] != E or t.shape[0] < S_max or tuple(t.shape) != tuple(cos.shape) or not t.is_contiguous() or t.data_ptr() % 16:
+                raise RuntimeError(f"kv_append: the rotary tables are contiguous [P >= {S_max}, {E}] in {dt}, got {tuple(t.shape)} {t.dtype}")
+    keep: list[torch.Tensor] = []
+    params = []
+    for quantizer, what in ((k_quantizer, "key"), (v_quantizer, "value")):
+        s, o = _scalar(quantizer[0], f"{what} scale"), _scalar(quantizer[1], f"{what} offset")
+        bits = float(quantizer[2])
+        if s is None or not (2 <= bits <= 8 and bits == int(bits)):
+            raise RuntimeError(f"kv_append: the {what} quantizer needs a scale and an integral bit-width in 2..8, got {bits}")
+        keep += [t for t in (s, o) if t is not None]
+        params += [_ptr(s), _ptr(o), bits]
+    lib, stream = _base._prepare(k_new, v_new, k_cache, v_cache, lens, cos, sin, *keep)
+    entry = _entry(lib, "ffq_kv_append")
+    strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_cache), *_strides(v_cache))
+    lib.check(
+        entry(
+            _ptr(k_new), _ptr(v_new), _tag(dt), _ptr(k_cache), _ptr(v_cache), _ptr(lens), B, HKV, L, S_max, E, strides, *params, _ptr(cos), _ptr(sin),
+            0 if cos is None else cos.shape[0], stream,
+        )
+    )
+    del keep
+    # written through raw pointers: tell the version counters
+    torch.autograd.graph.increment_version(k_cache)
+    torch.autograd.graph.increment_version(v_cache)
+
+
+def kv_decode(
+    query: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    lens: torch.Tensor,
+    is_causal: bool = False,
+    scale: float | None = None,
+    output_quantizer: tuple[torch.Tensor, torch.Tensor | None, float] | None = None,
+    dequant: Sequence[Dequant | None] = (None, None, None),
+    dtype: torch.dtype | None = None,
+    splits: int = 0,
+    plan_len: int | None = None,
+) -> torch.Tensor:
+    """One call of ``ffq_kv_decode``: :func:`~fastforward_amd.ops.decode.sdpa_decode` over caches [B, H, S_max, E] of which sequence b
+    holds ``clamp(lens[b], 0, S_max)`` keys (`lens` int32 [B], read on the device). ``is_causal`` is BOTTOM-RIGHT: row l sees
+    ``key <= l + (S_b - L)``; a row without a visible key, and every row of a sequence without keys, is exact zeros. ``splits=0`` takes
+    ``sdpa_decode_plan(B, H, plan_len, rows, E)`` with ``plan_len`` (a host hint in ``1..S_max``) defaulting to ``S_max``;
+    ``1 .. MAX_SPLITS`` forces a count. Each batch cuts its own keys over that count (``sdpa_decode_split_ranges(S_b, splits)``)."""
+    if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise RuntimeError("kv_decode: q / k / v are 4-D [B, H, L|S_max, E]")
+    if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8 or dequant[1] is None or dequant[2] is None:
+        raise RuntimeError(f"kv_decode: k / v are int8 codes with their (scale, offset), got {k_cache.dtype}, {v_cache.dtype}")
+    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
+    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
+        raise RuntimeError(f"kv_decode: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
+    if query.dtype == torch.int8 and dequant[0] is None:
+        raise RuntimeError("kv_decode: int8 q codes need their (scale, offset)")
+    B, H, L, E = query.shape
+    _, HKV, S_max, _ = k_cache.shape
+    if k_cache.shape[0] != B or k_cache.shape[3] != E or tuple(v_cache.shape) != (B, HKV, S_max, E):
+        raise RuntimeError(f"kv_decode: shapes {tuple(query.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)} do not fit")
+    if E not in (64, 128):
+        raise RuntimeError(f"kv_decode: E must be 64 or 128, got {E}")
+    if HKV < 1 or H % HKV:
+        raise RuntimeError(f"kv_decode: {H} query heads are not a multiple of {HKV} kv heads")
+    rows = L * (H // HKV)
+    if rows > MAX_ROWS:
+        raise RuntimeError(f"kv_decode: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
+    if min(B, L, S_max) < 1:
+        raise RuntimeError(f"kv_decode: empty operands {tuple(query.shape)}, {tuple(k_cache.shape)}")
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"kv_decode: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    if not 0 <= splits <= MAX_SPLITS:
+        raise RuntimeError(f"kv_decode: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
+    if plan_len is not None and not 1 <= plan_len <= S_max:
+        raise RuntimeError(f"kv_decode: plan_len is a key count in 1..{S_max}, got {plan_len}")
+    for t in (query, k_cache, v_cache):
+        if not _rows_ok(t):
+            raise RuntimeError("kv_decode: the last dimension must be contiguous with 16-byte aligned rows")
+    keep: list[torch.Tensor] = []
+    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
+    for i, d in enumerate(dequant):
+        if d is not None:
+            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
+            keep += [t for t in (s, o) if t is not None]
+            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
+    out_s = out_o = None
+    bits = 8.0
+    if output_quantizer is not None:
+        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
+        bits = float(output_quantizer[2])
+        keep += [t for t in (out_s, out_o) if t is not None]
+    lib, stream = _base._prepare(query, k_cache, v_cache, lens, *keep)
+    entry = _entry(lib, "ffq_kv_decode")
+    count = splits or int(_entry(lib, "ffq_sdpa_decode_splits")(B, HKV, plan_len or S_max, rows, E))
+    nbytes = int(_entry(lib, "ffq_sdpa_decode_workspace_bytes")(B, HKV, rows, E, count))
+    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(k_cache), *_strides(v_cache))
+    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
+    lib.check(
+        entry(
+            _ptr(query), _tag(query.dtype), _ptr(k_cache), _ptr(v_cache), _tag(dt), deq_s, deq_o, _ptr(lens), B, H, HKV, L, S_max, E, strides,
+            int(bool(is_causal)), sqrt_scale, _ptr(out_s), _ptr(out_o), bits, splits, plan_len or 0, _ptr(out), _ptr(workspace), nbytes, stream,
+        )
+    )
+    del keep
+    return out
