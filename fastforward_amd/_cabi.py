@@ -334,6 +334,22 @@ SIGNATURES_KV: dict[str, tuple[object, list[object]]] = {
     ),
 }
 
+# name -> (restype, argtypes); mirrors include/ffq_kv_paged.h one to one: the eighth header's table (the append and the decode
+# attention of ffq_kv_cache.h over K / V held in fixed-size pages behind a per-sequence block table), bound as SIGNATURES_3D is (None
+# on a library without the symbol).
+SIGNATURES_PAGED: dict[str, tuple[object, list[object]]] = {
+    "ffq_kv_paged_append": (
+        _i,
+        [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _vp, _vp, _d, _vp, _vp, _d, _vp, _vp,
+         _i64, _vp],
+    ),
+    "ffq_kv_paged_decode": (
+        _i,
+        [_vp, _i, _vp, _vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+         ctypes.POINTER(_i64), _i, _d, _vp, _vp, _d, _i64, _i64, _vp, _vp, _sz, _vp],
+    ),
+}
+
 SDPA_DECODE_MAX_ROWS = 32  # FFQ_SDPA_DECODE_MAX_ROWS
 SDPA_DECODE_KEY_TILE = 128  # FFQ_SDPA_DECODE_KEY_TILE
 SDPA_DECODE_MAX_SPLITS = 64  # FFQ_SDPA_DECODE_MAX_SPLITS
@@ -366,7 +382,7 @@ class FFQLibrary:
         for name in missing:
             setattr(self, name, None)
         for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items(),
-                                          *SIGNATURES_UNFOLD.items(), *SIGNATURES_DECODE.items(), *SIGNATURES_KV.items()):
+                                          *SIGNATURES_UNFOLD.items(), *SIGNATURES_DECODE.items(), *SIGNATURES_KV.items(), *SIGNATURES_PAGED.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

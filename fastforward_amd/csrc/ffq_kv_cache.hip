@@ -11,11 +11,17 @@
 //     rd rounding to the data dtype; 16-byte loads, two 8-byte stores. V goes the plain way.
 // A1 is quantize_chunk_to_bytes (ffq_affine.h): the codes of ffq_quantize_by_tile, NaN and +-Inf included. Every index is 64-bit.
 // No LDS, no scratch.
+//
+// kv_paged_store_kernel (ffq_kv_paged_append, include/ffq_kv_paged.h) is the same body with the caches held in fixed-size pages of two
+// pools: the lane reads the sequence's block table once (page table[b][pos / P]) and writes row pos % P of that page; a table entry
+// outside [0, num_pages) drops the row. The codes, the rotation (table row `pos`) and the resources are the dense kernel's.
 #include "ffq_affine.h"
 #include "ffq_common.h"
+#include "ffq_paging.h"
 #include "ffq_vec.h"
 
 #include "../../include/ffq_kv_cache.h"
+#include "../../include/ffq_kv_paged.h"
 
 #include <math.h>
 
@@ -59,8 +65,16 @@ __device__ __forceinline__ void append16(const T* src, int8_t* dst, float s, flo
   y.store(dst);
 }
 
-template <typename T, bool ROPE>
-__global__ __launch_bounds__(kBlock) void kv_append_kernel(AppendArgs a) {
+// Paged caches (include/ffq_kv_paged.h, ffq_paging.h): kc / vc are the pools, kcs / vcs their (page, head, row) strides, S_max the
+// capacity max_pages * P of a sequence
+struct PagedStoreArgs : AppendArgs {
+  Paging pg;
+};
+
+// The body of both kernels. PAGED changes where a row's codes go: page table[b][pos / P], row pos % P of the pools; a row whose table
+// entry lies outside the pool is dropped like one outside [0, S_max), before any load
+template <typename T, bool ROPE, bool PAGED, typename Args>
+__device__ __forceinline__ void append_rows(const Args& a) {
   const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (item >= a.items) return;
   const int64_t j = item & (((int64_t)1 << a.chunk_shift) - 1);
@@ -72,8 +86,14 @@ __global__ __launch_bounds__(kBlock) void kv_append_kernel(AppendArgs a) {
 
   const T* kn = static_cast<const T*>(a.kn) + b * a.kns[0] + kvh * a.kns[1] + l * a.kns[2];
   const T* vn = static_cast<const T*>(a.vn) + b * a.vns[0] + kvh * a.vns[1] + l * a.vns[2];
-  int8_t* kc = a.kc + b * a.kcs[0] + kvh * a.kcs[1] + pos * a.kcs[2];
-  int8_t* vc = a.vc + b * a.vcs[0] + kvh * a.vcs[1] + pos * a.vcs[2];
+  int64_t slot = b, at = pos;  // the cache's first and third index
+  if constexpr (PAGED) {
+    slot = page_of(a.pg, b, pos);
+    if (slot < 0) return;
+    at = pos & (((int64_t)1 << a.pg.page_shift) - 1);
+  }
+  int8_t* kc = a.kc + slot * a.kcs[0] + kvh * a.kcs[1] + at * a.kcs[2];
+  int8_t* vc = a.vc + slot * a.vcs[0] + kvh * a.vcs[1] + at * a.vcs[2];
   const float ks = a.ks[0], ko = a.ko ? rne(a.ko[0]) : 0.0f;
   const float vs = a.vs[0], vo = a.vo ? rne(a.vo[0]) : 0.0f;
 
@@ -108,12 +128,49 @@ __global__ __launch_bounds__(kBlock) void kv_append_kernel(AppendArgs a) {
   }
 }
 
+template <typename T, bool ROPE>
+__global__ __launch_bounds__(kBlock) void kv_append_kernel(AppendArgs a) {
+  append_rows<T, ROPE, false>(a);
+}
+
+// (its name does not hold "kv_append": tests count the dense kernels by that)
+template <typename T, bool ROPE>
+__global__ __launch_bounds__(kBlock) void kv_paged_store_kernel(PagedStoreArgs a) {
+  append_rows<T, ROPE, true>(a);
+}
+
 bool bits_ok(double bits) { return bits >= 2.0 && bits <= 8.0 && bits == (double)(int)bits; }
 
 template <typename T>
 void launch_append(const AppendArgs& a, bool rope, unsigned blocks, hipStream_t s) {
   if (rope) kv_append_kernel<T, true><<<blocks, kBlock, 0, s>>>(a);
   else kv_append_kernel<T, false><<<blocks, kBlock, 0, s>>>(a);
+}
+
+template <typename T>
+void launch_paged_store(const PagedStoreArgs& a, bool rope, unsigned blocks, hipStream_t s) {
+  if (rope) kv_paged_store_kernel<T, true><<<blocks, kBlock, 0, s>>>(a);
+  else kv_paged_store_kernel<T, false><<<blocks, kBlock, 0, s>>>(a);
+}
+
+// what both entry points fill once their checks have passed (`capacity`: S_max, or max_pages * P)
+void fill(AppendArgs& a, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const void* lens, int64_t batch, int64_t kv_heads,
+          int64_t L, int64_t capacity, int64_t E, const int64_t* strides, const float* k_scale, const float* k_offset, double k_num_bits,
+          const float* v_scale, const float* v_offset, double v_num_bits, const void* cos_table, const void* sin_table) {
+  a.kn = k_new; a.vn = v_new;
+  a.kc = static_cast<int8_t*>(k_cache); a.vc = static_cast<int8_t*>(v_cache);
+  a.lens = static_cast<const int32_t*>(lens);
+  a.cos = cos_table; a.sin = sin_table;
+  a.ks = k_scale; a.ko = k_offset; a.vs = v_scale; a.vo = v_offset;
+  for (int i = 0; i < 3; ++i) {
+    a.kns[i] = strides[i]; a.vns[i] = strides[3 + i]; a.kcs[i] = strides[6 + i]; a.vcs[i] = strides[9 + i];
+  }
+  a.L = L; a.HKV = (int32_t)kv_heads; a.S_max = (int32_t)capacity; a.E = (int32_t)E;
+  a.chunk_shift = E == 64 ? 2 : 3;
+  a.items = batch * kv_heads * L * (E / 16);
+  const double khalf = ldexp(1.0, (int)k_num_bits - 1), vhalf = ldexp(1.0, (int)v_num_bits - 1);
+  a.klo = (float)-khalf; a.khi = (float)(khalf - 1.0);
+  a.vlo = (float)-vhalf; a.vhi = (float)(vhalf - 1.0);
 }
 
 }  // namespace
@@ -147,22 +204,47 @@ extern "C" int ffq_kv_append(const void* k_new, const void* v_new, int dt, void*
   if (S_max == 0) return FFQ_OK;  // (no position to write to)
 
   AppendArgs a;
-  a.kn = k_new; a.vn = v_new;
-  a.kc = static_cast<int8_t*>(k_cache); a.vc = static_cast<int8_t*>(v_cache);
-  a.lens = static_cast<const int32_t*>(lens);
-  a.cos = cos_table; a.sin = sin_table;
-  a.ks = k_scale; a.ko = k_offset; a.vs = v_scale; a.vo = v_offset;
-  for (int i = 0; i < 3; ++i) {
-    a.kns[i] = strides[i]; a.vns[i] = strides[3 + i]; a.kcs[i] = strides[6 + i]; a.vcs[i] = strides[9 + i];
-  }
-  a.L = L; a.HKV = (int32_t)kv_heads; a.S_max = (int32_t)S_max; a.E = (int32_t)E;
-  a.chunk_shift = E == 64 ? 2 : 3;
-  a.items = batch * kv_heads * L * (E / 16);
-  const double khalf = ldexp(1.0, (int)k_num_bits - 1), vhalf = ldexp(1.0, (int)v_num_bits - 1);
-  a.klo = (float)-khalf; a.khi = (float)(khalf - 1.0);
-  a.vlo = (float)-vhalf; a.vhi = (float)(vhalf - 1.0);
+  fill(a, k_new, v_new, k_cache, v_cache, lens, batch, kv_heads, L, S_max, E, strides, k_scale, k_offset, k_num_bits, v_scale, v_offset, v_num_bits,
+       cos_table, sin_table);
   const unsigned blocks = (unsigned)((a.items + kBlock - 1) / kBlock);
   if (dt == FFQ_F16) launch_append<f16_t>(a, cos_table != nullptr, blocks, s);
   else launch_append<bf16_t>(a, cos_table != nullptr, blocks, s);
   return check_launch("kv_append_kernel");
+}
+
+extern "C" int ffq_kv_paged_append(const void* k_new, const void* v_new, int dt, void* k_pool, void* v_pool, const void* lens, const void* block_table,
+                                   int64_t batch, int64_t kv_heads, int64_t L, int64_t num_pages, int64_t P, int64_t max_pages, int64_t table_stride,
+                                   int64_t E, const int64_t* strides, const float* k_scale, const float* k_offset, double k_num_bits,
+                                   const float* v_scale, const float* v_offset, double v_num_bits, const void* cos_table, const void* sin_table,
+                                   int64_t table_rows, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_paged_append: bf16 or fp16 values");
+  if (!strides) return fail(FFQ_ERR_ARG, "kv_paged_append: NULL strides table");
+  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_paged_append: E must be 64 or 128");
+  if (batch < 0 || L < 0 || kv_heads <= 0) return fail(FFQ_ERR_ARG, "kv_paged_append: bad extent");
+  if (const char* why = paging_error(num_pages, P, max_pages, table_stride)) return fail(FFQ_ERR_ARG, "kv_paged_append: %s", why);
+  const int64_t C = max_pages * P;  // a sequence's capacity, in the place of S_max
+  if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "kv_paged_append: the quantizers need an integral bit-width in 2..8");
+  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "kv_paged_append: a quantizer (and its offset) needs its scale");
+  if (!cos_table != !sin_table) return fail(FFQ_ERR_ARG, "kv_paged_append: the rotary tables come as a pair");
+  if (cos_table && table_rows < C) return fail(FFQ_ERR_ARG, "kv_paged_append: the rotary tables need a row for every position of a sequence (%lld < %lld)", (long long)table_rows, (long long)C);
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (batch >= ((int64_t)1 << 31) || kv_heads >= ((int64_t)1 << 31) || L >= ((int64_t)1 << 40) ||
+      (double)batch * (double)kv_heads * (double)L * (double)E >= 0x1p40)
+    return fail(FFQ_ERR_ARG, "kv_paged_append: too large");
+  if (!aligned16(k_new) || !aligned16(v_new) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(cos_table) || !aligned16(sin_table) ||
+      (reinterpret_cast<uintptr_t>(lens) & 3u) || (reinterpret_cast<uintptr_t>(block_table) & 3u))
+    return fail(FFQ_ERR_ARG, "kv_paged_append: buffers must be 16-byte aligned (lens, block_table: 4-byte)");
+  for (int i = 0; i < 12; ++i)
+    if (strides[i] < 0 || strides[i] % (i < 6 ? 8 : 16)) return fail(FFQ_ERR_ARG, "kv_paged_append: strides must be non-negative multiples of 16 bytes");
+  if (!k_new || !v_new || !k_pool || !v_pool || !lens || !block_table) return fail(FFQ_ERR_ARG, "kv_paged_append: NULL buffer");
+
+  PagedStoreArgs a;
+  fill(a, k_new, v_new, k_pool, v_pool, lens, batch, kv_heads, L, C, E, strides, k_scale, k_offset, k_num_bits, v_scale, v_offset, v_num_bits,
+       cos_table, sin_table);
+  a.pg = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
+  const unsigned blocks = (unsigned)((a.items + kBlock - 1) / kBlock);
+  if (dt == FFQ_F16) launch_paged_store<f16_t>(a, cos_table != nullptr, blocks, s);
+  else launch_paged_store<bf16_t>(a, cos_table != nullptr, blocks, s);
+  return check_launch("kv_paged_store_kernel");
 }

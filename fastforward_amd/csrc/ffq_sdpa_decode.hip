@@ -31,11 +31,19 @@
 // ffq_kv_decode (include/ffq_kv_cache.h) runs the same two kernels over a preallocated cache: the split COUNT is still a host
 // integer, but every batch reads its own key count from `lens` on the device and cuts it over that count by the same rule, and the
 // causal mask is bottom-right. Both entry points share the kernels' instantiations: the difference is a launch-uniform null check.
+//
+// ffq_kv_paged_decode (include/ffq_kv_paged.h) is ffq_kv_decode over K / V held in fixed-size pages of two pools.
+// kv_paged_partial_kernel is the partial kernel's body (decode_partial) instantiated with PAGED: a lane finds its key row through
+// one int32 load of the sequence's block table per tile (page table[b][key / P], row key % P; P >= 32 makes the page uniform over a
+// wave's 32 keys, P = 16 gives two), and the keys of a table entry outside the pool are neither loaded nor scored (-inf, as a bool
+// mask would). The key order, the arithmetic, the LDS and the combine kernel are the dense form's: the same bits at the same split count.
 #include "ffq_affine.h"
 #include "ffq_common.h"
+#include "ffq_paging.h"
 #include "ffq_vec.h"
 
 #include "../../include/ffq_kv_cache.h"
+#include "../../include/ffq_kv_paged.h"
 #include "../../include/ffq_sdpa_decode.h"
 
 #include <math.h>
@@ -160,8 +168,16 @@ struct Lds {
   static constexpr int kStats = 2 * kWaves * kRows * 4;                    // m and l of every wave
 };
 
-template <int E, bool F16>
-__global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArgs a) {
+// Paged K / V (include/ffq_kv_paged.h, ffq_paging.h): the codes live in fixed-size pages of two pools, found through a per-sequence
+// block table. DecodeArgs::ks / vs are then the (page, head, row) strides of the pools, S is the capacity max_pages * P of a sequence
+struct PagedDecodeArgs : DecodeArgs {
+  Paging pg;
+};
+
+// The body of both partial kernels. PAGED changes where a lane finds its key row (stage_load) and adds one mask, the keys of a page
+// the table does not place inside the pool; the arithmetic and the key order are the dense form's
+template <int E, bool F16, bool PAGED, typename Args>
+__device__ __forceinline__ void decode_partial(const Args& a) {
   constexpr int T = E / 16;   // MFMA k-steps of QK^T
   constexpr int U = E / 32;   // 16-byte loads per key row and lane
   constexpr int DB = E / 32;  // 32-column blocks of O^T
@@ -224,19 +240,32 @@ __global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArg
   }
 
   // ---- K / V rows of this lane: key (tile's first) + r32, 16 codes at column (2u + h) * 16; rows >= k_end read nothing
-  const int8_t* kbase = a.k + (int64_t)b * a.ks[0] + (int64_t)kvh * a.ks[1] + h * 16;
-  const int8_t* vbase = a.v + (int64_t)b * a.vs[0] + (int64_t)kvh * a.vs[1] + h * 16;
+  // paged: the row is (page table[b][key / P], row key % P) of the pools, one table load per lane and tile; a table entry outside
+  // [0, num_pages) reads nothing either, and `staged_ok` (bit i: key i of the staged 32 was loaded) masks its keys in the scores
+  const int8_t* kbase = a.k + (PAGED ? 0 : (int64_t)b * a.ks[0]) + (int64_t)kvh * a.ks[1] + h * 16;
+  const int8_t* vbase = a.v + (PAGED ? 0 : (int64_t)b * a.vs[0]) + (int64_t)kvh * a.vs[1] + h * 16;
   u32x4 sk[U], sv[U];
+  uint32_t staged_ok = 0;
   auto stage_load = [&](int32_t it) {
     const int32_t key = k_begin + it * kTile + (int32_t)wave * kWaveKeys + (int32_t)r32;
-    const bool in = key < k_end;
+    bool in = key < k_end;
+    int32_t at = key;                   // the row inside the cache, or inside its page
+    int64_t k_page = 0, v_page = 0;     // (paged) where the page starts in each pool
+    if constexpr (PAGED) {
+      const int32_t page = in ? page_of(a.pg, b, key) : -1;
+      in = page >= 0;
+      at = key & ((1 << a.pg.page_shift) - 1);
+      k_page = (int64_t)page * a.ks[0];
+      v_page = (int64_t)page * a.vs[0];
+      staged_ok = (uint32_t)__ballot(in);  // (both halves of the wave hold the same 32 keys)
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       sk[u] = u32x4{0, 0, 0, 0};
       sv[u] = u32x4{0, 0, 0, 0};
       if (in) {
-        sk[u] = *reinterpret_cast<const u32x4*>(kbase + (int64_t)key * a.ks[2] + u * 32);
-        sv[u] = *reinterpret_cast<const u32x4*>(vbase + (int64_t)key * a.vs[2] + u * 32);
+        sk[u] = *reinterpret_cast<const u32x4*>(kbase + k_page + (int64_t)at * a.ks[2] + u * 32);
+        sv[u] = *reinterpret_cast<const u32x4*>(vbase + v_page + (int64_t)at * a.vs[2] + u * 32);
       }
     }
   };
@@ -266,6 +295,7 @@ __global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArg
       dequant16<F16>(sv[u], dvs, dvo, vw[u][0], vw[u][1]);
     }
     const int32_t key0 = k_begin + it * kTile + (int32_t)wave * kWaveKeys;
+    const uint32_t tile_ok = staged_ok;
     if (it + 1 < iters) stage_load(it + 1);
 
     // ---- V^T image of the wave's 32 keys: column d is a row of 32 keys. Written ahead of the score chain, whose MFMAs and softmax
@@ -324,6 +354,12 @@ __global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArg
     if (!whole) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) s[e] = key_of(e) < k_end ? s[e] : -INFINITY;
+    }
+    if constexpr (PAGED) {
+      if (tile_ok != 0xFFFFFFFFu) {  // (wave-uniform) a key without a page in the pool: as if a bool mask hid it
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[e] = (tile_ok >> (key_of(e) - key0)) & 1u ? s[e] : -INFINITY;
+      }
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -422,6 +458,17 @@ __global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArg
     }
 }
 
+template <int E, bool F16>
+__global__ __launch_bounds__(kThreads) void sdpa_decode_partial_kernel(DecodeArgs a) {
+  decode_partial<E, F16, false>(a);
+}
+
+// (its name holds neither "sdpa_decode_partial_kernel" nor "sdpa_decode_combine_kernel": tests count the dense kernels by those)
+template <int E, bool F16>
+__global__ __launch_bounds__(kThreads) void kv_paged_partial_kernel(PagedDecodeArgs a) {
+  decode_partial<E, F16, true>(a);
+}
+
 struct CombineArgs {
   const float* ws_o;
   const float* ws_m;
@@ -494,11 +541,19 @@ void launch_partial(const DecodeArgs& a, bool f16, unsigned blocks, hipStream_t 
   else sdpa_decode_partial_kernel<E, false><<<blocks, kThreads, 0, s>>>(a);
 }
 
-// the two launches, after an entry point's checks. `lens` nullptr: S keys for every batch (ffq_sdpa_decode); else S is S_max
+template <int E>
+void launch_paged_partial(const PagedDecodeArgs& a, bool f16, unsigned blocks, hipStream_t s) {
+  if (f16) kv_paged_partial_kernel<E, true><<<blocks, kThreads, 0, s>>>(a);
+  else kv_paged_partial_kernel<E, false><<<blocks, kThreads, 0, s>>>(a);
+}
+
+// the two launches, after an entry point's checks. `lens` nullptr: S keys for every batch (ffq_sdpa_decode); else S is S_max.
+// `paging` (ffq_kv_paged_decode): k / v are the pools, their strides those of (page, head, row), S the capacity of a sequence
 int enqueue(const void* q, int q_dt, const void* k, const void* v, int dt, const float* const* deq_scale, const float* const* deq_offset,
             const int32_t* lens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L, int64_t S, int64_t E, const int64_t* strides,
             const void* mask, int mask_kind, int mask_dt, const int64_t* mask_strides, double sqrt_scale, const float* out_scale,
-            const float* out_offset, double out_num_bits, int64_t nsplit, void* out, void* workspace, hipStream_t s) {
+            const float* out_offset, double out_num_bits, int64_t nsplit, void* out, void* workspace, hipStream_t s,
+            const Paging* paging = nullptr) {
   const int64_t rows = L * (q_heads / kv_heads);
   DecodeArgs a;
   a.q = q; a.k = static_cast<const int8_t*>(k); a.v = static_cast<const int8_t*>(v);
@@ -519,9 +574,18 @@ int enqueue(const void* q, int q_dt, const void* k, const void* v, int dt, const
   a.ws_m = a.ws_o + parts * rows * E;
   a.ws_l = a.ws_m + parts * rows;
   const bool f16 = dt == FFQ_F16;
-  if (E == 64) launch_partial<64>(a, f16, (unsigned)parts, s);
-  else launch_partial<128>(a, f16, (unsigned)parts, s);
-  int rc = check_launch("sdpa_decode_partial_kernel");
+  if (paging) {
+    PagedDecodeArgs p;
+    static_cast<DecodeArgs&>(p) = a;
+    p.pg = *paging;
+    if (E == 64) launch_paged_partial<64>(p, f16, (unsigned)parts, s);
+    else launch_paged_partial<128>(p, f16, (unsigned)parts, s);
+  } else if (E == 64) {
+    launch_partial<64>(a, f16, (unsigned)parts, s);
+  } else {
+    launch_partial<128>(a, f16, (unsigned)parts, s);
+  }
+  int rc = check_launch(paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel");
   if (rc != FFQ_OK) return rc;
 
   CombineArgs c;
@@ -628,4 +692,47 @@ extern "C" int ffq_kv_decode(const void* q, int q_dt, const void* k, const void*
   return enqueue(q, q_dt, k, v, dt, deq_scale, deq_offset, static_cast<const int32_t*>(lens), batch, q_heads, kv_heads, L, S_max, E, strides,
                  nullptr, causal ? MASK_CAUSAL : MASK_NONE, FFQ_F32, nullptr, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out,
                  workspace, s);
+}
+
+extern "C" int ffq_kv_paged_decode(const void* q, int q_dt, const void* k_pool, const void* v_pool, int dt, const float* const* deq_scale,
+                                   const float* const* deq_offset, const void* lens, const void* block_table, int64_t batch, int64_t q_heads,
+                                   int64_t kv_heads, int64_t L, int64_t num_pages, int64_t P, int64_t max_pages, int64_t table_stride, int64_t E,
+                                   const int64_t* strides, int causal, double sqrt_scale, const float* out_scale, const float* out_offset,
+                                   double out_num_bits, int64_t splits, int64_t plan_len, void* out, void* workspace,
+                                   size_t workspace_bytes_given, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_paged_decode: bf16 or fp16 values");
+  if (q_dt != dt && q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "kv_paged_decode: q is held in the value dtype or in int8");
+  if (!strides || !deq_scale || !deq_offset) return fail(FFQ_ERR_ARG, "kv_paged_decode: NULL argument table");
+  if (q_dt == FFQ_I8 && !deq_scale[0]) return fail(FFQ_ERR_DTYPE, "kv_paged_decode: int8 q codes need their scale");
+  if (!deq_scale[1] || !deq_scale[2]) return fail(FFQ_ERR_ARG, "kv_paged_decode: k and v are int8 codes and need their scales");
+  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_paged_decode: E must be 64 or 128");
+  if (batch < 0 || L < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return fail(FFQ_ERR_ARG, "kv_paged_decode: bad extent");
+  if (const char* why = paging_error(num_pages, P, max_pages, table_stride)) return fail(FFQ_ERR_ARG, "kv_paged_decode: %s", why);
+  const int64_t C = max_pages * P;  // a sequence's capacity, in the place of S_max
+  if (L > kRows || L * (q_heads / kv_heads) > kRows) return fail(FFQ_ERR_ARG, "kv_paged_decode: L * (q_heads / kv_heads) must be <= %d", kRows);
+  if (causal != 0 && causal != 1) return fail(FFQ_ERR_ARG, "kv_paged_decode: causal is 0 (every key) or 1 (bottom-right)");
+  if (!out_scale && out_offset) return fail(FFQ_ERR_ARG, "kv_paged_decode: an output offset needs its scale");
+  if (out_scale && !(out_num_bits >= 1.0 && out_num_bits <= 8.0 && out_num_bits == (double)(int)out_num_bits))
+    return fail(FFQ_ERR_ARG, "kv_paged_decode: the output quantizer needs an integral bit-width in 1..8");
+  if (splits < 0 || splits > kCap) return fail(FFQ_ERR_ARG, "kv_paged_decode: splits must be 0 (the rule) or 1..%d", (int)kCap);
+  if (plan_len < 0 || plan_len > C) return fail(FFQ_ERR_ARG, "kv_paged_decode: plan_len must be 0 (max_pages * P) or 1..max_pages * P");
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (batch * kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "kv_paged_decode: too large");
+  if (!q || !k_pool || !v_pool || !out || !lens || !block_table) return fail(FFQ_ERR_ARG, "kv_paged_decode: NULL buffer");
+  if (!aligned16(q) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(out) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
+      (reinterpret_cast<uintptr_t>(block_table) & 3u))
+    return fail(FFQ_ERR_ARG, "kv_paged_decode: buffers must be 16-byte aligned (lens, block_table: 4-byte)");
+  const int64_t q_unit = q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
+  for (int i = 0; i < 9; ++i)
+    if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "kv_paged_decode: strides must be non-negative multiples of 16 bytes");
+  const int64_t rows = L * (q_heads / kv_heads);
+  const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, plan_len ? plan_len : C);
+  const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
+  if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
+    return fail(FFQ_ERR_WORKSPACE, "kv_paged_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
+  const Paging paging = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
+  return enqueue(q, q_dt, k_pool, v_pool, dt, deq_scale, deq_offset, static_cast<const int32_t*>(lens), batch, q_heads, kv_heads, L, C, E, strides,
+                 nullptr, causal ? MASK_CAUSAL : MASK_NONE, FFQ_F32, nullptr, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out,
+                 workspace, s, &paging);
 }

@@ -14,7 +14,8 @@ add / sub / mul / div, softmax, sigmoid and GELU kernels (fallbacks: _gen/fallba
 (quantization/_linear_quantized_ops.py:126-171). ``dropout`` follows fallback.py:1399-1423 with no kernel of its own, and
 ``scaled_dot_product_attention`` is the reference's custom operator (nn/sdpa.py; ``fastforward_amd.fused_sdpa`` registers its
 kernel, and ``fastforward_amd.fused_sdpa_decode`` the split-key ``sdpa_decode`` kernels for a query of at most 32 rows per kv head
-over K / V kept as int8 codes, a quantized KV cache). ``rms_norm``, ``pow``, ``exp``, ``sin``, ``cos``, ``sum`` and ``cumsum`` follow their fallbacks (_gen/fallback.py:955-1014,
+over K / V kept as int8 codes, a quantized KV cache; ``nn.QuantizedKVCache`` keeps one in place as a dense slab per tensor,
+``nn.PagedQuantizedKVCache`` as fixed-size pages of a shared pool behind a per-sequence block table). ``rms_norm``, ``pow``, ``exp``, ``sin``, ``cos``, ``sum`` and ``cumsum`` follow their fallbacks (_gen/fallback.py:955-1014,
 1520-1541, 1831-1941), and ``fastforward_amd.fused_math`` registers their one-pass kernels. ``avg_pool1d``, ``avg_pool2d``,
 ``max_pool2d`` and ``interpolate`` follow theirs (_gen/fallback.py:505-575, 1574-1646) with the reference's signatures, and
 ``fastforward_amd.fused_pool`` registers the one-pass kernels of the pools and of nearest interpolation. ``cat`` and ``pad`` follow

@@ -10,6 +10,11 @@ sequences grow, each at its own length. ``is_causal`` is bottom-right: the L new
 modules, an indexed copy per batch, ``scaled_dot_product_attention`` per batch on the slices with a bottom-right bool mask). They read
 the lengths on the host: they are the chain the kernels are tested against and what the class runs on host tensors or with a library
 that lacks the entry points, not a fast path.
+
+``PagedQuantizedKVCache`` keeps the same codes in fixed-size pages of two pools behind a per-sequence block table on the device
+(``ops.kv_paged_append`` / ``ops.kv_paged_decode``, include/ffq_kv_paged.h): a sequence owns only the pages it uses, a finished one
+gives them back without a copy, and sequences can share the pages of a common prefix. Its page bookkeeping is host code that runs
+outside a captured step; ``composed_paged_append`` / ``composed_paged_attend`` gather the pages into a dense view and run the chain above.
 """
 
 from __future__ import annotations
@@ -185,3 +190,206 @@ class QuantizedKVCache:
 
     def values(self, length: int) -> QuantizedTensor:
         return self.value_quantizer.wrap_codes(self.v_cache[:, :, :length], self.dtype)
+
+
+# ---- the same cache in pages ---------------------------------------------------------------------------------------------------------------
+PAGED_LAYOUTS = ("phse", "pshe")
+
+
+def gather_pages(pool: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    """The dense ``[B, H, max_pages * P, E]`` codes a block table ``[B, max_pages]`` describes in a pool ``[num_pages, H, P, E]``: a
+    host-driven gather (the table is read on the host); the rows of an entry outside ``[0, num_pages)`` are zeros."""
+    num_pages, H, P, E = pool.shape
+    table = block_table.cpu().long()
+    valid = (table >= 0) & (table < num_pages)
+    pages = pool[table.clamp(0, num_pages - 1).to(pool.device)]                            # [B, max_pages, H, P, E]
+    pages = pages * valid.to(pool.device)[:, :, None, None, None].to(pool.dtype)
+    return pages.permute(0, 2, 1, 3, 4).reshape(table.shape[0], H, table.shape[1] * P, E)
+
+
+def _in_use(block_table: torch.Tensor, lengths: torch.Tensor, P: int, num_pages: int) -> list[list[int]]:
+    """The table entries every sequence's length reaches, read on the host; ValueError where one lies outside the pool."""
+    rows = block_table.cpu().tolist()
+    out = []
+    for b, n in enumerate(lengths.tolist()):
+        used = rows[b][:-(-min(max(n, 0), len(rows[b]) * P) // P)]
+        if any(not 0 <= page < num_pages for page in used):
+            raise ValueError(f"the composed paged route: sequence {b} of length {n} reaches a page that was never reserved ({used})")
+        out.append(used)
+    return out
+
+
+def composed_paged_append(k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, lengths: torch.Tensor, key: torch.Tensor,
+                          value: torch.Tensor, key_quantizer: LinearQuantizer, value_quantizer: LinearQuantizer, rope: Rope | None = None) -> None:
+    """``ops.kv_paged_append`` from existing pieces: the pages gathered into a dense ``[B, H, C, E]`` view, :func:`composed_append` on
+    it, and the pages the new rows touched scattered back (a row whose page lies outside the pool is dropped). `lengths` already counts
+    the L new rows; it and the table are read on the host."""
+    num_pages, P, L = k_pool.shape[0], k_pool.shape[2], key.shape[2]
+    k_dense, v_dense = gather_pages(k_pool, block_table), gather_pages(v_pool, block_table)
+    composed_append(k_dense, v_dense, lengths, key, value, key_quantizer, value_quantizer, rope)
+    rows = block_table.cpu().tolist()
+    for b, n in enumerate(lengths.tolist()):
+        first, last = max(n - L, 0), min(n, len(rows[b]) * P)
+        for slot in range(first // P, -(-last // P) if last > first else 0):
+            page = rows[b][slot]
+            if 0 <= page < num_pages:
+                k_pool[page].copy_(k_dense[b, :, slot * P:(slot + 1) * P])
+                v_pool[page].copy_(v_dense[b, :, slot * P:(slot + 1) * P])
+
+
+def composed_paged_attend(query: Any, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, lengths: torch.Tensor,
+                          key_quantizer: LinearQuantizer, value_quantizer: LinearQuantizer, dtype: torch.dtype, is_causal: bool = True,
+                          scale: float | None = None, output_quantizer: Any = None) -> torch.Tensor:
+    """``ops.kv_paged_decode`` from existing pieces: :func:`composed_attend` on the gathered dense view. It reads the table on the host
+    and refuses (ValueError) a sequence whose length reaches a page outside the pool, which the kernel masks."""
+    _in_use(block_table, lengths, k_pool.shape[2], k_pool.shape[0])
+    return composed_attend(query, gather_pages(k_pool, block_table), gather_pages(v_pool, block_table), lengths, key_quantizer, value_quantizer,
+                           dtype, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer)
+
+
+class PagedQuantizedKVCache:
+    """:class:`QuantizedKVCache` with the codes in fixed-size pages: two int8 pools of `num_pages` pages of `page_size` positions
+    shared by `batch` sequences, each of which addresses up to `max_pages_per_seq` of them through its row of ``block_table``
+    (int32 ``[batch, max_pages_per_seq]`` on the device, -1 where no page is assigned). A sequence owns only the pages it uses, a
+    finished sequence's pages go back to the free list without a copy, and two sequences can share the pages of a common prefix.
+
+    ``layout="phse"`` allocates ``[num_pages, H, P, E]``; ``"pshe"`` allocates ``[num_pages, P, H, E]`` (a position's heads side by
+    side) and works on its ``transpose(1, 2)`` view. ``k_pool`` / ``v_pool`` are always ``[num_pages, H, P, E]`` views.
+
+    ``append`` and ``attend`` are one launch each (``ops.kv_paged_append`` / ``ops.kv_paged_decode``) and read neither a length nor
+    the table on the host, so a step can be captured in a graph and replayed. The page bookkeeping — ``reserve``, ``release``,
+    ``share_prefix`` — is host code that writes the table with one small copy: call it OUTSIDE a captured region, ahead of the step
+    that needs the page. A position whose page was never reserved is dropped by ``append`` and masked by ``attend``."""
+
+    def __init__(self, num_pages: int, page_size: int, kv_heads: int, head_dim: int, key_quantizer: LinearQuantizer,
+                 value_quantizer: LinearQuantizer, batch: int, max_pages_per_seq: int, dtype: torch.dtype = torch.bfloat16,
+                 device: torch.device | str = "cuda", layout: str = "phse") -> None:
+        name = "PagedQuantizedKVCache"
+        if layout not in PAGED_LAYOUTS:
+            raise ValueError(f"{name}: layout is one of {PAGED_LAYOUTS}, got {layout!r}")
+        if dtype not in _VALUES:
+            raise ValueError(f"{name}: the data dtype is bf16 or fp16, got {dtype}")
+        if head_dim not in (64, 128):
+            raise ValueError(f"{name}: head_dim must be 64 or 128, got {head_dim}")
+        if not 16 <= page_size <= 256 or page_size & (page_size - 1):
+            raise ValueError(f"{name}: page_size is a power of two in 16..256, got {page_size}")
+        if min(num_pages, kv_heads, batch, max_pages_per_seq) < 1 or max_pages_per_seq * page_size >= 1 << 30:
+            raise ValueError(f"{name}: num_pages, kv_heads, batch and max_pages_per_seq are positive and a sequence stays below 2^30 positions, "
+                             f"got {num_pages}, {kv_heads}, {batch}, {max_pages_per_seq}")
+        _quantizer_params(key_quantizer, "key")
+        _quantizer_params(value_quantizer, "value")
+        self.key_quantizer, self.value_quantizer = key_quantizer, value_quantizer
+        self.dtype, self.layout, self.page_size, self.num_pages = dtype, layout, page_size, num_pages
+        self.capacity = max_pages_per_seq * page_size  # positions a sequence can address
+        shape = (num_pages, kv_heads, page_size, head_dim) if layout == "phse" else (num_pages, page_size, kv_heads, head_dim)
+        buffers = [torch.zeros(shape, dtype=torch.int8, device=device) for _ in range(2)]
+        self.k_pool, self.v_pool = (t if layout == "phse" else t.transpose(1, 2) for t in buffers)
+        self.block_table = torch.full((batch, max_pages_per_seq), -1, dtype=torch.int32, device=device)
+        self.lengths = torch.zeros(batch, dtype=torch.int32, device=device)
+        # the host's view of the table: the pages of every sequence in order, how many sequences hold each page, and the free pages
+        self._pages: list[list[int]] = [[] for _ in range(batch)]
+        self._refs = [0] * num_pages
+        self._free = list(range(num_pages - 1, -1, -1))  # (a stack: page 0 goes out first)
+
+    # ---- host-side page bookkeeping (never inside a captured region)
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    def pages(self, seq: int) -> tuple[int, ...]:
+        """The pool pages of sequence `seq`, in order (the host's copy of its table row)."""
+        return tuple(self._pages[seq])
+
+    def _write_row(self, seq: int) -> None:
+        row = self._pages[seq] + [-1] * (self.block_table.shape[1] - len(self._pages[seq]))
+        self.block_table[seq].copy_(torch.tensor(row, dtype=torch.int32))
+
+    def reserve(self, seq: int, n_positions: int) -> None:
+        """Take pages from the free list until sequence `seq` can hold `n_positions`; RuntimeError (and nothing taken) when the pool
+        cannot give them, ValueError beyond the sequence's capacity."""
+        if not 0 <= n_positions <= self.capacity:
+            raise ValueError(f"PagedQuantizedKVCache.reserve: a sequence holds 0..{self.capacity} positions, got {n_positions}")
+        need = -(-n_positions // self.page_size) - len(self._pages[seq])
+        if need <= 0:
+            return
+        if need > len(self._free):
+            raise RuntimeError(f"PagedQuantizedKVCache.reserve: the pool is exhausted ({need} pages wanted, {len(self._free)} free)")
+        for _ in range(need):
+            page = self._free.pop()
+            self._refs[page] = 1
+            self._pages[seq].append(page)
+        self._write_row(seq)
+
+    def release(self, seq: int) -> None:
+        """Give the pages of sequence `seq` back (a shared page once its last holder lets go), its table row to -1, its length to 0."""
+        for page in reversed(self._pages[seq]):
+            self._refs[page] -= 1
+            if self._refs[page] == 0:
+                self._free.append(page)
+        self._pages[seq] = []
+        self._write_row(seq)
+        self.lengths[seq:seq + 1].zero_()
+
+    def share_prefix(self, src: int, dst: int, n_positions: int) -> None:
+        """Point the first ``n_positions // page_size`` whole pages of `dst` (which holds no page yet) at `src`'s pages, reference
+        counted, and set ``lengths[dst]`` to that many positions. A partial last page is not shared: `dst` appends those rows itself."""
+        whole = n_positions // self.page_size
+        if src == dst or self._pages[dst]:
+            raise ValueError("PagedQuantizedKVCache.share_prefix: the receiving sequence is another one and holds no page yet (release it first)")
+        if not 0 <= whole <= len(self._pages[src]):
+            raise ValueError(f"PagedQuantizedKVCache.share_prefix: sequence {src} holds {len(self._pages[src])} pages, {whole} wanted")
+        self._pages[dst] = self._pages[src][:whole]
+        for page in self._pages[dst]:
+            self._refs[page] += 1
+        self._write_row(dst)
+        self.lengths[dst:dst + 1].fill_(whole * self.page_size)
+
+    # ---- the device side
+    def _native(self, *tensors: torch.Tensor) -> bool:
+        lib = _native.library()
+        return all(t.is_cuda for t in (*tensors, self.k_pool)) and all(getattr(lib, name, None) is not None for name in ("ffq_kv_paged_append", "ffq_kv_paged_decode"))
+
+    def append(self, key: torch.Tensor, value: torch.Tensor, rope: Rope | None = None) -> None:
+        """:meth:`QuantizedKVCache.append` into pages: ``lengths += L``, then row l of batch b goes to position ``lengths[b] - L + l``
+        of its sequence; rows outside ``[0, capacity)`` or on a page never reserved are dropped. The rotary tables need `capacity` rows."""
+        B, H, E = self.lengths.shape[0], self.k_pool.shape[1], self.k_pool.shape[3]
+        if key.dim() != 4 or tuple(key.shape) != tuple(value.shape) or (key.shape[0], key.shape[1], key.shape[3]) != (B, H, E):
+            raise ValueError(f"PagedQuantizedKVCache.append: key / value are [{B}, {H}, L, {E}] rows, got {tuple(key.shape)}, {tuple(value.shape)}")
+        if key.dtype != self.dtype or value.dtype != self.dtype:
+            raise ValueError(f"PagedQuantizedKVCache.append: the new rows are plain {self.dtype} values, got {key.dtype}, {value.dtype}")
+        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
+        self.lengths.add_(key.shape[2])
+        if self._native(key, value):
+            ops.kv_paged_append(key.detach(), value.detach(), self.k_pool, self.v_pool, self.lengths, self.block_table, k_params, v_params, rope=rope)
+        else:
+            composed_paged_append(self.k_pool, self.v_pool, self.block_table, self.lengths, key.detach(), value.detach(), self.key_quantizer,
+                                  self.value_quantizer, rope)
+
+    def attend(self, query: Any, is_causal: bool = True, scale: float | None = None, output_quantizer: Any = None, splits: int = 0,
+               plan_len: int | None = None) -> torch.Tensor:
+        """:meth:`QuantizedKVCache.attend` over pages: the same operands, refusals and bits (``ops.kv_paged_decode``)."""
+        kernels = _kernels()
+        if isinstance(query, QuantizedTensor):
+            if kernels._codes_dtype(query, ("int8", "value")) != self.dtype:
+                raise ValueError("PagedQuantizedKVCache.attend: a quantized query holds per-tensor codes of the cache's dtype in an int8 or value-dtype container")
+        elif type(query) is not torch.Tensor or query.dtype != self.dtype:
+            raise ValueError(f"PagedQuantizedKVCache.attend: the query is plain {self.dtype} or per-tensor codes of it")
+        with torch.no_grad():
+            fused = kernels._fused(output_quantizer)
+        if fused is False:
+            raise ValueError("PagedQuantizedKVCache.attend: the output quantizer is not one the decode kernels fuse")
+        raw, q_dequant = kernels._dequant(query)
+        if not self._native(raw):
+            return composed_paged_attend(query, self.k_pool, self.v_pool, self.block_table, self.lengths, self.key_quantizer, self.value_quantizer,
+                                         self.dtype, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer if fused else None)
+        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
+        return ops.kv_paged_decode(raw, self.k_pool, self.v_pool, self.lengths, self.block_table, is_causal=is_causal, scale=scale,
+                                   output_quantizer=fused or None, dequant=(q_dequant, k_params[:2], v_params[:2]), dtype=self.dtype, splits=splits,
+                                   plan_len=plan_len)
+
+    def dense(self, seq: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """The K and V codes gathered into dense ``[B, H, capacity, E]`` tensors (``[H, capacity, E]`` for one sequence), zeros where no
+        page is assigned: a host-driven gather for tests and debugging, not a fast path."""
+        table = self.block_table if seq is None else self.block_table[seq:seq + 1]
+        k, v = gather_pages(self.k_pool, table), gather_pages(self.v_pool, table)
+        return (k, v) if seq is None else (k[0], v[0])

@@ -4,7 +4,11 @@
 every sequence's own position, K optionally rotated on the way. ``kv_decode`` is ``sdpa_decode`` with the key count of every
 sequence read on the device: the split count stays a host integer (so the call is the same under graph capture whatever the lengths
 become), each batch cuts its own keys over it, and ``causal`` is bottom-right. `lens` (int32 ``[B]``) is read by both and written by
-neither: the caller advances it with ``lens.add_(L)`` on the stream ahead of ``kv_append``."""
+neither: the caller advances it with ``lens.add_(L)`` on the stream ahead of ``kv_append``.
+
+``kv_paged_append`` / ``kv_paged_decode`` (include/ffq_kv_paged.h) are the same two calls over K / V held in fixed-size pages: two
+pools ``[num_pages, H, P, E]`` shared by every sequence and an int32 block table ``[B, max_pages]`` on the device, read by the kernels
+and never on the host. The codes and the attention's bits are those of the dense calls."""
 
 from __future__ import annotations
 
@@ -17,7 +21,7 @@ import torch
 
 from fastforward_amd.ops import _base
 from fastforward_amd.ops._base import _ptr, _tag
-from fastforward_amd.ops.decode import MAX_ROWS, MAX_SPLITS, Dequant
+from fastforward_amd.ops.decode import MAX_ROWS, MAX_SPLITS, Dequant, sdpa_decode_plan, sdpa_decode_workspace_bytes
 from fastforward_amd.ops.modules import _entry
 from fastforward_amd.ops.sdpa import _scalar, _strides
 
@@ -30,6 +34,69 @@ def _rows_ok(t: torch.Tensor) -> bool:
 
 def _lens_ok(lens: torch.Tensor, B: int) -> bool:
     return lens.dtype == torch.int32 and tuple(lens.shape) == (B,) and lens.is_contiguous()
+
+
+def _quantizer_args(name: str, k_quantizer: Quantizer, v_quantizer: Quantizer) -> tuple[list, list[torch.Tensor]]:
+    """[k scale, k offset, k bits, v scale, v offset, v bits] as the append entry points take them, and the tensors to keep alive."""
+    keep: list[torch.Tensor] = []
+    params: list = []
+    for quantizer, what in ((k_quantizer, "key"), (v_quantizer, "value")):
+        s, o = _scalar(quantizer[0], f"{what} scale"), _scalar(quantizer[1], f"{what} offset")
+        bits = float(quantizer[2])
+        if s is None or not (2 <= bits <= 8 and bits == int(bits)):
+            raise RuntimeError(f"{name}: the {what} quantizer needs a scale and an integral bit-width in 2..8, got {bits}")
+        keep += [t for t in (s, o) if t is not None]
+        params += [_ptr(s), _ptr(o), bits]
+    return params, keep
+
+
+def _rope_tables(name: str, rope: tuple[torch.Tensor, torch.Tensor] | None, dt: torch.dtype, rows: int, E: int):
+    """(cos, sin) checked: contiguous [P >= rows, E] tables in the data dtype, both the same shape; (None, None) without rotation."""
+    if rope is None:
+        return None, None
+    cos, sin = rope
+    for t in (cos, sin):
+        if t.dtype != dt or t.dim() != 2 or t.shape[1] != E or t.shape[0] < rows or tuple(t.shape) != tuple(cos.shape) or not t.is_contiguous() or t.data_ptr() % 16:
+            raise RuntimeError(f"{name}: the rotary tables are contiguous [P >= {rows}, {E}] in {dt}, got {tuple(t.shape)} {t.dtype}")
+    return cos, sin
+
+
+def _decode_tables(dequant: Sequence[Dequant | None], output_quantizer):
+    """(deq_scale[3], deq_offset[3], out scale, out offset, out bits, the tensors to keep alive) as the decode entry points take them."""
+    keep: list[torch.Tensor] = []
+    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
+    for i, d in enumerate(dequant):
+        if d is not None:
+            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
+            keep += [t for t in (s, o) if t is not None]
+            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
+    out_s = out_o = None
+    bits = 8.0
+    if output_quantizer is not None:
+        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
+        bits = float(output_quantizer[2])
+        keep += [t for t in (out_s, out_o) if t is not None]
+    return deq_s, deq_o, out_s, out_o, bits, keep
+
+
+def _pools_ok(name: str, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, B: int, HKV: int, E: int) -> tuple[int, int, int]:
+    """(num_pages, P, max_pages) of pools [num_pages, HKV, P, E] (int8, any page / head / row strides) and a block table int32
+    [B, max_pages] whose rows are contiguous, else RuntimeError."""
+    if k_pool.dim() != 4 or v_pool.dim() != 4 or k_pool.dtype != torch.int8 or v_pool.dtype != torch.int8:
+        raise RuntimeError(f"{name}: the pools are 4-D [num_pages, H, P, E] int8 codes, got {tuple(k_pool.shape)} {k_pool.dtype}, {tuple(v_pool.shape)} {v_pool.dtype}")
+    num_pages, _, P, _ = k_pool.shape
+    if tuple(k_pool.shape) != (num_pages, HKV, P, E) or tuple(v_pool.shape) != (num_pages, HKV, P, E) or num_pages < 1:
+        raise RuntimeError(f"{name}: pools {tuple(k_pool.shape)}, {tuple(v_pool.shape)} do not fit {HKV} kv heads of {E} columns")
+    if not 16 <= P <= 256 or P & (P - 1):
+        raise RuntimeError(f"{name}: the page size is a power of two in 16..256, got {P}")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.stride(1) != 1:
+        raise RuntimeError(f"{name}: the block table is int32 [{B}, max_pages] with contiguous rows, got {block_table.dtype} {tuple(block_table.shape)}")
+    max_pages = block_table.shape[1]
+    if B > 1 and block_table.stride(0) < max_pages:
+        raise RuntimeError(f"{name}: the block table's rows overlap (stride {block_table.stride(0)} < {max_pages})")
+    if max_pages * P >= 1 << 30:
+        raise RuntimeError(f"{name}: a sequence's capacity {max_pages} x {P} must stay below 2^30")
+    return num_pages, P, max_pages
 
 
 def kv_append(
@@ -67,21 +134,8 @@ def kv_append(
     for t in (k_new, v_new, k_cache, v_cache):
         if not _rows_ok(t):
             raise RuntimeError("kv_append: the last dimension must be contiguous with 16-byte aligned rows")
-    cos = sin = None
-    if rope is not None:
-        cos, sin = rope
-        for t in (cos, sin):
-            if t.dtype != dt or t.dim() != 2 or t.shape[1] != E or t.shape[0] < S_max or tuple(t.shape) != tuple(cos.shape) or not t.is_contiguous() or t.data_ptr() % 16:
-                raise RuntimeError(f"kv_append: the rotary tables are contiguous [P >= {S_max}, {E}] in {dt}, got {tuple(t.shape)} {t.dtype}")
-    keep: list[torch.Tensor] = []
-    params = []
-    for quantizer, what in ((k_quantizer, "key"), (v_quantizer, "value")):
-        s, o = _scalar(quantizer[0], f"{what} scale"), _scalar(quantizer[1], f"{what} offset")
-        bits = float(quantizer[2])
-        if s is None or not (2 <= bits <= 8 and bits == int(bits)):
-            raise RuntimeError(f"kv_append: the {what} quantizer needs a scale and an integral bit-width in 2..8, got {bits}")
-        keep += [t for t in (s, o) if t is not None]
-        params += [_ptr(s), _ptr(o), bits]
+    cos, sin = _rope_tables("kv_append", rope, dt, S_max, E)
+    params, keep = _quantizer_args("kv_append", k_quantizer, v_quantizer)
     lib, stream = _base._prepare(k_new, v_new, k_cache, v_cache, lens, cos, sin, *keep)
     entry = _entry(lib, "ffq_kv_append")
     strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_cache), *_strides(v_cache))
@@ -146,19 +200,7 @@ def kv_decode(
     for t in (query, k_cache, v_cache):
         if not _rows_ok(t):
             raise RuntimeError("kv_decode: the last dimension must be contiguous with 16-byte aligned rows")
-    keep: list[torch.Tensor] = []
-    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
-    for i, d in enumerate(dequant):
-        if d is not None:
-            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
-            keep += [t for t in (s, o) if t is not None]
-            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
-    out_s = out_o = None
-    bits = 8.0
-    if output_quantizer is not None:
-        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
-        bits = float(output_quantizer[2])
-        keep += [t for t in (out_s, out_o) if t is not None]
+    deq_s, deq_o, out_s, out_o, bits, keep = _decode_tables(dequant, output_quantizer)
     lib, stream = _base._prepare(query, k_cache, v_cache, lens, *keep)
     entry = _entry(lib, "ffq_kv_decode")
     count = splits or int(_entry(lib, "ffq_sdpa_decode_splits")(B, HKV, plan_len or S_max, rows, E))
@@ -171,6 +213,128 @@ def kv_decode(
         entry(
             _ptr(query), _tag(query.dtype), _ptr(k_cache), _ptr(v_cache), _tag(dt), deq_s, deq_o, _ptr(lens), B, H, HKV, L, S_max, E, strides,
             int(bool(is_causal)), sqrt_scale, _ptr(out_s), _ptr(out_o), bits, splits, plan_len or 0, _ptr(out), _ptr(workspace), nbytes, stream,
+        )
+    )
+    del keep
+    return out
+
+
+def kv_paged_append(
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    lens: torch.Tensor,
+    block_table: torch.Tensor,
+    k_quantizer: Quantizer,
+    v_quantizer: Quantizer,
+    rope: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> None:
+    """One call of ``ffq_kv_paged_append``: :func:`kv_append` into pages. k_pool / v_pool int8 [num_pages, H, P, E] (any page / head /
+    row strides: ``[num_pages, P, H, E].transpose(1, 2)`` is served), P a power of two in 16..256; `block_table` int32 [B, max_pages].
+    Sequence b holds up to ``C = max_pages * P`` positions and position ``pos`` lives in page ``block_table[b, pos // P]`` at row
+    ``pos % P``. Row l goes to ``lens[b] - L + l``; a row outside ``[0, C)``, or whose table entry lies outside ``[0, num_pages)``, is
+    skipped. The codes are :func:`kv_append`'s; the rotary tables need ``C`` rows. Nothing is read on the host."""
+    name = "kv_paged_append"
+    if k_new.dim() != 4 or v_new.dim() != 4:
+        raise RuntimeError(f"{name}: the new rows are 4-D [B, H, L, E]")
+    dt = k_new.dtype
+    if dt not in (torch.bfloat16, torch.float16) or v_new.dtype != dt:
+        raise RuntimeError(f"{name}: the new rows are bf16 or fp16, both the same, got {k_new.dtype} and {v_new.dtype}")
+    B, HKV, L, E = k_new.shape
+    if tuple(v_new.shape) != (B, HKV, L, E):
+        raise RuntimeError(f"{name}: shapes {tuple(k_new.shape)}, {tuple(v_new.shape)} do not fit")
+    if E not in (64, 128):
+        raise RuntimeError(f"{name}: E must be 64 or 128, got {E}")
+    if HKV < 1:
+        raise RuntimeError(f"{name}: no kv head")
+    num_pages, P, max_pages = _pools_ok(name, k_pool, v_pool, block_table, B, HKV, E)
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    for t in (k_new, v_new, k_pool, v_pool):
+        if not _rows_ok(t):
+            raise RuntimeError(f"{name}: the last dimension must be contiguous with 16-byte aligned rows")
+    cos, sin = _rope_tables(name, rope, dt, max_pages * P, E)
+    params, keep = _quantizer_args(name, k_quantizer, v_quantizer)
+    lib, stream = _base._prepare(k_new, v_new, k_pool, v_pool, lens, block_table, cos, sin, *keep)
+    entry = _entry(lib, "ffq_kv_paged_append")
+    strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_pool), *_strides(v_pool))
+    lib.check(
+        entry(
+            _ptr(k_new), _ptr(v_new), _tag(dt), _ptr(k_pool), _ptr(v_pool), _ptr(lens), _ptr(block_table), B, HKV, L, num_pages, P, max_pages,
+            block_table.stride(0) if B > 1 else max_pages, E, strides, *params, _ptr(cos), _ptr(sin), 0 if cos is None else cos.shape[0], stream,
+        )
+    )
+    del keep
+    # written through raw pointers: tell the version counters
+    torch.autograd.graph.increment_version(k_pool)
+    torch.autograd.graph.increment_version(v_pool)
+
+
+def kv_paged_decode(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    lens: torch.Tensor,
+    block_table: torch.Tensor,
+    is_causal: bool = False,
+    scale: float | None = None,
+    output_quantizer: tuple[torch.Tensor, torch.Tensor | None, float] | None = None,
+    dequant: Sequence[Dequant | None] = (None, None, None),
+    dtype: torch.dtype | None = None,
+    splits: int = 0,
+    plan_len: int | None = None,
+) -> torch.Tensor:
+    """One call of ``ffq_kv_paged_decode``: :func:`kv_decode` over pools [num_pages, H, P, E] addressed through `block_table` int32
+    [B, max_pages] (:func:`kv_paged_append`), with the capacity ``C = max_pages * P`` in the place of ``S_max``: sequence b holds
+    ``clamp(lens[b], 0, C)`` keys, ``plan_len`` is a hint in ``1..C``. The keys of a table entry outside ``[0, num_pages)`` are masked.
+    The result is bit-equal to :func:`kv_decode` on the same codes laid out densely at the same split count."""
+    name = "kv_paged_decode"
+    if query.dim() != 4:
+        raise RuntimeError(f"{name}: q is 4-D [B, H, L, E]")
+    if dequant[1] is None or dequant[2] is None:
+        raise RuntimeError(f"{name}: k / v are int8 codes with their (scale, offset)")
+    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
+    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
+        raise RuntimeError(f"{name}: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
+    if query.dtype == torch.int8 and dequant[0] is None:
+        raise RuntimeError(f"{name}: int8 q codes need their (scale, offset)")
+    B, H, L, E = query.shape
+    if E not in (64, 128):
+        raise RuntimeError(f"{name}: E must be 64 or 128, got {E}")
+    HKV = k_pool.shape[1] if k_pool.dim() == 4 else 0
+    if HKV < 1 or H % HKV:
+        raise RuntimeError(f"{name}: {H} query heads are not a multiple of {HKV} kv heads")
+    if min(B, L) < 1:
+        raise RuntimeError(f"{name}: empty operands {tuple(query.shape)}")
+    num_pages, P, max_pages = _pools_ok(name, k_pool, v_pool, block_table, B, HKV, E)
+    C = max_pages * P
+    rows = L * (H // HKV)
+    if rows > MAX_ROWS:
+        raise RuntimeError(f"{name}: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    if not 0 <= splits <= MAX_SPLITS:
+        raise RuntimeError(f"{name}: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
+    if plan_len is not None and not 1 <= plan_len <= C:
+        raise RuntimeError(f"{name}: plan_len is a key count in 1..{C}, got {plan_len}")
+    for t in (query, k_pool, v_pool):
+        if not _rows_ok(t):
+            raise RuntimeError(f"{name}: the last dimension must be contiguous with 16-byte aligned rows")
+    deq_s, deq_o, out_s, out_o, bits, keep = _decode_tables(dequant, output_quantizer)
+    lib, stream = _base._prepare(query, k_pool, v_pool, lens, block_table, *keep)
+    entry = _entry(lib, "ffq_kv_paged_decode")
+    count = splits or sdpa_decode_plan(B, HKV, plan_len or C, rows, E)
+    nbytes = sdpa_decode_workspace_bytes(B, HKV, rows, E, count)
+    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
+    workspace = _base._workspace(nbytes, query.device)
+    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(k_pool), *_strides(v_pool))
+    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
+    lib.check(
+        entry(
+            _ptr(query), _tag(query.dtype), _ptr(k_pool), _ptr(v_pool), _tag(dt), deq_s, deq_o, _ptr(lens), _ptr(block_table), B, H, HKV, L, num_pages,
+            P, max_pages, block_table.stride(0) if B > 1 else max_pages, E, strides, int(bool(is_causal)), sqrt_scale, _ptr(out_s), _ptr(out_o), bits,
+            splits, plan_len or 0, _ptr(out), _ptr(workspace), nbytes, stream,
         )
     )
     del keep
