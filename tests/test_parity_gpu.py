@@ -848,7 +848,8 @@ def test_full_size_producers_properties():
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_backward_kernel_matches_composite_formulas(shape, tile, dtype):
     """HIP kernel vs the op-for-op composite on the device at Llama sizes: dinput identical, per-tile sums within
-    the fp32 summation tolerance; the straight-through property dinput == grad where nothing clips."""
+    the fp32 summation tolerance; the straight-through property dinput == grad where nothing clips. (Exactness — every bit of
+    the sums, on each launch route — is held by tests/test_quantizer_exact_gpu.py.)"""
     torch.manual_seed(3)
     x = (torch.randn(shape, device=DEV) * 2).to(dtype)
     g = torch.randn(shape, device=DEV).to(dtype)
@@ -1261,7 +1262,8 @@ _ODD_TILINGS = [((96, 160), (96, 1)), ((64, 48, 40), (16, 8, 4)), ((33, 17), (1,
 @pytest.mark.parametrize("dtype,with_offset", [(torch.float32, True), (torch.bfloat16, True), (torch.float32, False)])
 def test_backward_by_tile_kernel_covers_every_tiling(shape, tile, dtype, with_offset, monkeypatch):
     """PerChannel(-1), PerChannel(1) on 3-D, N-d tiles, element-wise tiles, 2-D blocks: the HIP library itself produces the
-    gradients (the composite of device tensor ops is never called) and they equal the op-for-op formulas."""
+    gradients (the composite of device tensor ops is never called) and they equal the op-for-op formulas. (Exactness — every
+    bit of the sums on these tilings — is held by tests/test_quantizer_exact_gpu.py.)"""
     torch.manual_seed(sum(shape))
     x = (torch.randn(shape, device=DEV) * 2).to(dtype)
     g = torch.randn(shape, device=DEV).to(dtype)
