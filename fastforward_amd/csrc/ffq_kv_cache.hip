@@ -15,6 +15,9 @@
 // kv_paged_store_kernel (ffq_kv_paged_append, include/ffq_kv_paged.h) is the same body with the caches held in fixed-size pages of two
 // pools: the lane reads the sequence's block table once (page table[b][pos / P]) and writes row pos % P of that page; a table entry
 // outside [0, num_pages) drops the row. The codes, the rotation (table row `pos`) and the resources are the dense kernel's.
+//
+// Host side: both entry points run the shared rules (check_shape, check_quantizers_and_tables, check_sizes_and_buffers) in the order
+// their error tables pin, with their own steps in between, fill() the kernel's arguments and launch through launch_rows.
 #include "ffq_affine.h"
 #include "ffq_common.h"
 #include "ffq_paging.h"
@@ -24,6 +27,8 @@
 #include "../../include/ffq_kv_paged.h"
 
 #include <math.h>
+
+#include <initializer_list>
 
 namespace ffq {
 namespace {
@@ -141,16 +146,53 @@ __global__ __launch_bounds__(kBlock) void kv_paged_store_kernel(PagedStoreArgs a
 
 bool bits_ok(double bits) { return bits >= 2.0 && bits <= 8.0 && bits == (double)(int)bits; }
 
-template <typename T>
-void launch_append(const AppendArgs& a, bool rope, unsigned blocks, hipStream_t s) {
-  if (rope) kv_append_kernel<T, true><<<blocks, kBlock, 0, s>>>(a);
-  else kv_append_kernel<T, false><<<blocks, kBlock, 0, s>>>(a);
+// Each rule of the two entry points once: it takes the entry point's name for its message and returns the first failing status. An
+// entry point calls them in the order its error table pins (tests/test_kv_cache_cpu.py, tests/test_kv_paged_cpu.py) with its own
+// steps in between. `capacity` is S_max, or max_pages * P.
+// The value dtype, the strides table, E and the extents
+int check_shape(const char* name, int dt, const int64_t* strides, int64_t E, int64_t batch, int64_t kv_heads, int64_t L, int64_t capacity) {
+  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "%s: bf16 or fp16 values", name);
+  if (!strides) return fail(FFQ_ERR_ARG, "%s: NULL strides table", name);
+  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "%s: E must be 64 or 128", name);
+  if (batch < 0 || L < 0 || capacity < 0 || kv_heads <= 0) return fail(FFQ_ERR_ARG, "%s: bad extent", name);
+  return FFQ_OK;
 }
 
-template <typename T>
-void launch_paged_store(const PagedStoreArgs& a, bool rope, unsigned blocks, hipStream_t s) {
-  if (rope) kv_paged_store_kernel<T, true><<<blocks, kBlock, 0, s>>>(a);
-  else kv_paged_store_kernel<T, false><<<blocks, kBlock, 0, s>>>(a);
+// The two quantizers and the rotary tables; `positions` is how the entry point words what the tables need a row for
+int check_quantizers_and_tables(const char* name, const float* k_scale, double k_num_bits, const float* v_scale, double v_num_bits, const void* cos_table,
+                                const void* sin_table, int64_t table_rows, int64_t capacity, const char* positions) {
+  if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "%s: the quantizers need an integral bit-width in 2..8", name);
+  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "%s: a quantizer (and its offset) needs its scale", name);
+  if (!cos_table != !sin_table) return fail(FFQ_ERR_ARG, "%s: the rotary tables come as a pair", name);
+  if (cos_table && table_rows < capacity)
+    return fail(FFQ_ERR_ARG, "%s: the rotary tables need a row for every %s (%lld < %lld)", name, positions, (long long)table_rows, (long long)capacity);
+  return FFQ_OK;
+}
+
+// The sizes, the alignment, the twelve strides, then the NULL check. `rows`: the new rows and the caches (16-byte aligned, not NULL);
+// `words`: the entry point's int32 tables (4-byte aligned, not NULL), `named` as its message names them; the rotary pair may be NULL
+int check_sizes_and_buffers(const char* name, int64_t batch, int64_t kv_heads, int64_t L, int64_t capacity, int64_t E, const int64_t* strides,
+                            std::initializer_list<const void*> rows, const void* cos_table, const void* sin_table,
+                            std::initializer_list<const void*> words, const char* named) {
+  if (capacity >= ((int64_t)1 << 30) || batch >= ((int64_t)1 << 31) || kv_heads >= ((int64_t)1 << 31) || L >= ((int64_t)1 << 40) ||
+      (double)batch * (double)kv_heads * (double)L * (double)E >= 0x1p40)
+    return fail(FFQ_ERR_ARG, "%s: too large", name);
+  bool aligned = aligned16(cos_table) && aligned16(sin_table), present = true;
+  for (const void* p : rows) { aligned &= aligned16(p); present &= p != nullptr; }
+  for (const void* p : words) { aligned &= aligned4(p); present &= p != nullptr; }
+  if (!aligned) return fail(FFQ_ERR_ARG, "%s: buffers must be 16-byte aligned (%s: 4-byte)", name, named);
+  for (int i = 0; i < 12; ++i)
+    if (strides[i] < 0 || strides[i] % (i < 6 ? 8 : 16)) return fail(FFQ_ERR_ARG, "%s: strides must be non-negative multiples of 16 bytes", name);
+  if (!present) return fail(FFQ_ERR_ARG, "%s: NULL buffer", name);
+  return FFQ_OK;
+}
+
+// one launch: `rotary` / `plain` are the dense or the paged kernel's two instantiations at the call's dtype
+template <typename Args>
+int launch_rows(void (*rotary)(Args), void (*plain)(Args), const Args& a, const char* what, hipStream_t s) {
+  auto kernel = a.cos ? rotary : plain;
+  kernel<<<(unsigned)((a.items + kBlock - 1) / kBlock), kBlock, 0, s>>>(a);
+  return check_launch(what);
 }
 
 // what both entry points fill once their checks have passed (`capacity`: S_max, or max_pages * P)
@@ -183,33 +225,17 @@ extern "C" int ffq_kv_append(const void* k_new, const void* v_new, int dt, void*
                              const float* k_offset, double k_num_bits, const float* v_scale, const float* v_offset, double v_num_bits,
                              const void* cos_table, const void* sin_table, int64_t table_rows, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_append: bf16 or fp16 values");
-  if (!strides) return fail(FFQ_ERR_ARG, "kv_append: NULL strides table");
-  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_append: E must be 64 or 128");
-  if (batch < 0 || L < 0 || S_max < 0 || kv_heads <= 0) return fail(FFQ_ERR_ARG, "kv_append: bad extent");
-  if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "kv_append: the quantizers need an integral bit-width in 2..8");
-  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "kv_append: a quantizer (and its offset) needs its scale");
-  if (!cos_table != !sin_table) return fail(FFQ_ERR_ARG, "kv_append: the rotary tables come as a pair");
-  if (cos_table && table_rows < S_max) return fail(FFQ_ERR_ARG, "kv_append: the rotary tables need a row for every cache position (%lld < %lld)", (long long)table_rows, (long long)S_max);
+  if (int rc = check_shape("kv_append", dt, strides, E, batch, kv_heads, L, S_max)) return rc;
+  if (int rc = check_quantizers_and_tables("kv_append", k_scale, k_num_bits, v_scale, v_num_bits, cos_table, sin_table, table_rows, S_max, "cache position")) return rc;
   if (batch == 0 || L == 0) return FFQ_OK;
-  if (S_max >= ((int64_t)1 << 30) || batch >= ((int64_t)1 << 31) || kv_heads >= ((int64_t)1 << 31) || L >= ((int64_t)1 << 40) ||
-      (double)batch * (double)kv_heads * (double)L * (double)E >= 0x1p40)
-    return fail(FFQ_ERR_ARG, "kv_append: too large");
-  if (!aligned16(k_new) || !aligned16(v_new) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(cos_table) || !aligned16(sin_table) ||
-      (reinterpret_cast<uintptr_t>(lens) & 3u))
-    return fail(FFQ_ERR_ARG, "kv_append: buffers must be 16-byte aligned (lens: 4-byte)");
-  for (int i = 0; i < 12; ++i)
-    if (strides[i] < 0 || strides[i] % (i < 6 ? 8 : 16)) return fail(FFQ_ERR_ARG, "kv_append: strides must be non-negative multiples of 16 bytes");
-  if (!k_new || !v_new || !k_cache || !v_cache || !lens) return fail(FFQ_ERR_ARG, "kv_append: NULL buffer");
+  if (int rc = check_sizes_and_buffers("kv_append", batch, kv_heads, L, S_max, E, strides, {k_new, v_new, k_cache, v_cache}, cos_table, sin_table, {lens}, "lens")) return rc;
   if (S_max == 0) return FFQ_OK;  // (no position to write to)
 
   AppendArgs a;
   fill(a, k_new, v_new, k_cache, v_cache, lens, batch, kv_heads, L, S_max, E, strides, k_scale, k_offset, k_num_bits, v_scale, v_offset, v_num_bits,
        cos_table, sin_table);
-  const unsigned blocks = (unsigned)((a.items + kBlock - 1) / kBlock);
-  if (dt == FFQ_F16) launch_append<f16_t>(a, cos_table != nullptr, blocks, s);
-  else launch_append<bf16_t>(a, cos_table != nullptr, blocks, s);
-  return check_launch("kv_append_kernel");
+  if (dt == FFQ_F16) return launch_rows(kv_append_kernel<f16_t, true>, kv_append_kernel<f16_t, false>, a, "kv_append_kernel", s);
+  return launch_rows(kv_append_kernel<bf16_t, true>, kv_append_kernel<bf16_t, false>, a, "kv_append_kernel", s);
 }
 
 extern "C" int ffq_kv_paged_append(const void* k_new, const void* v_new, int dt, void* k_pool, void* v_pool, const void* lens, const void* block_table,
@@ -218,33 +244,19 @@ extern "C" int ffq_kv_paged_append(const void* k_new, const void* v_new, int dt,
                                    const float* v_scale, const float* v_offset, double v_num_bits, const void* cos_table, const void* sin_table,
                                    int64_t table_rows, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_paged_append: bf16 or fp16 values");
-  if (!strides) return fail(FFQ_ERR_ARG, "kv_paged_append: NULL strides table");
-  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_paged_append: E must be 64 or 128");
-  if (batch < 0 || L < 0 || kv_heads <= 0) return fail(FFQ_ERR_ARG, "kv_paged_append: bad extent");
+  if (int rc = check_shape("kv_paged_append", dt, strides, E, batch, kv_heads, L, 0)) return rc;
   if (const char* why = paging_error(num_pages, P, max_pages, table_stride)) return fail(FFQ_ERR_ARG, "kv_paged_append: %s", why);
-  const int64_t C = max_pages * P;  // a sequence's capacity, in the place of S_max
-  if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "kv_paged_append: the quantizers need an integral bit-width in 2..8");
-  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "kv_paged_append: a quantizer (and its offset) needs its scale");
-  if (!cos_table != !sin_table) return fail(FFQ_ERR_ARG, "kv_paged_append: the rotary tables come as a pair");
-  if (cos_table && table_rows < C) return fail(FFQ_ERR_ARG, "kv_paged_append: the rotary tables need a row for every position of a sequence (%lld < %lld)", (long long)table_rows, (long long)C);
+  const int64_t C = max_pages * P;  // a sequence's capacity, in the place of S_max (below 2^30)
+  if (int rc = check_quantizers_and_tables("kv_paged_append", k_scale, k_num_bits, v_scale, v_num_bits, cos_table, sin_table, table_rows, C, "position of a sequence")) return rc;
   if (batch == 0 || L == 0) return FFQ_OK;
-  if (batch >= ((int64_t)1 << 31) || kv_heads >= ((int64_t)1 << 31) || L >= ((int64_t)1 << 40) ||
-      (double)batch * (double)kv_heads * (double)L * (double)E >= 0x1p40)
-    return fail(FFQ_ERR_ARG, "kv_paged_append: too large");
-  if (!aligned16(k_new) || !aligned16(v_new) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(cos_table) || !aligned16(sin_table) ||
-      (reinterpret_cast<uintptr_t>(lens) & 3u) || (reinterpret_cast<uintptr_t>(block_table) & 3u))
-    return fail(FFQ_ERR_ARG, "kv_paged_append: buffers must be 16-byte aligned (lens, block_table: 4-byte)");
-  for (int i = 0; i < 12; ++i)
-    if (strides[i] < 0 || strides[i] % (i < 6 ? 8 : 16)) return fail(FFQ_ERR_ARG, "kv_paged_append: strides must be non-negative multiples of 16 bytes");
-  if (!k_new || !v_new || !k_pool || !v_pool || !lens || !block_table) return fail(FFQ_ERR_ARG, "kv_paged_append: NULL buffer");
+  if (int rc = check_sizes_and_buffers("kv_paged_append", batch, kv_heads, L, C, E, strides, {k_new, v_new, k_pool, v_pool}, cos_table, sin_table,
+                                       {lens, block_table}, "lens, block_table"))
+    return rc;
 
   PagedStoreArgs a;
   fill(a, k_new, v_new, k_pool, v_pool, lens, batch, kv_heads, L, C, E, strides, k_scale, k_offset, k_num_bits, v_scale, v_offset, v_num_bits,
        cos_table, sin_table);
   a.pg = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
-  const unsigned blocks = (unsigned)((a.items + kBlock - 1) / kBlock);
-  if (dt == FFQ_F16) launch_paged_store<f16_t>(a, cos_table != nullptr, blocks, s);
-  else launch_paged_store<bf16_t>(a, cos_table != nullptr, blocks, s);
-  return check_launch("kv_paged_store_kernel");
+  if (dt == FFQ_F16) return launch_rows(kv_paged_store_kernel<f16_t, true>, kv_paged_store_kernel<f16_t, false>, a, "kv_paged_store_kernel", s);
+  return launch_rows(kv_paged_store_kernel<bf16_t, true>, kv_paged_store_kernel<bf16_t, false>, a, "kv_paged_store_kernel", s);
 }

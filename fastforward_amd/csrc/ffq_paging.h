@@ -1,5 +1,6 @@
 // ffq_paging.h — what the two paged kernels (kv_paged_store_kernel in ffq_kv_cache.hip, kv_paged_partial_kernel in
-// ffq_sdpa_decode.hip) share: how a sequence's position is found in a pool of fixed-size pages (include/ffq_kv_paged.h).
+// ffq_sdpa_decode.hip) share: how a sequence's position is found in a pool of fixed-size pages (include/ffq_kv_paged.h), and the
+// alignment rule of the int32 tables (lens, block_table) that the host side of both files checks.
 //
 // Position `pos` of sequence b lives in pool page table[b][pos >> page_shift] at row pos & (P - 1). A kernel reads a table entry
 // only for a position below the sequence's length, and dereferences it only when it lies in [0, num_pages): an entry outside that
@@ -31,6 +32,9 @@ inline const char* paging_error(int64_t num_pages, int64_t P, int64_t max_pages,
   if (table_stride < max_pages) return "the block table's row stride is below max_pages";
   return nullptr;
 }
+
+// the alignment of the int32 side tables the cache entry points read on the device (lens, block_table); true for nullptr
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 inline int32_t page_shift_of(int64_t P) {
   int32_t shift = 0;

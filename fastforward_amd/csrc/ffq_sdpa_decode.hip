@@ -37,6 +37,10 @@
 // one int32 load of the sequence's block table per tile (page table[b][key / P], row key % P; P >= 32 makes the page uniform over a
 // wave's 32 keys, P = 16 gives two), and the keys of a table entry outside the pool are neither loaded nor scored (-inf, as a bool
 // mask would). The key order, the arithmetic, the LDS and the combine kernel are the dense form's: the same bits at the same split count.
+//
+// Host side: the three entry points fill one DecodeCall from their own parameter lists, run the shared rules (check_operands,
+// check_rows, check_quantizer_and_splits, check_sizes_and_buffers, check_layout_and_workspace) in the order their error tables pin,
+// with their own steps in between, and hand the call to enqueue(); launch_partial is the one partial launch (docs/kernels.md).
 #include "ffq_affine.h"
 #include "ffq_common.h"
 #include "ffq_paging.h"
@@ -535,69 +539,131 @@ size_t workspace_bytes(int64_t batch, int64_t kv_heads, int64_t rows, int64_t E,
   return (size_t)(batch * kv_heads * splits * rows * (E + 2)) * sizeof(float);
 }
 
-template <int E>
-void launch_partial(const DecodeArgs& a, bool f16, unsigned blocks, hipStream_t s) {
-  if (f16) sdpa_decode_partial_kernel<E, true><<<blocks, kThreads, 0, s>>>(a);
-  else sdpa_decode_partial_kernel<E, false><<<blocks, kThreads, 0, s>>>(a);
+// ---- one decode call, and each rule of the three entry points once ----------------------------------------------------------------
+// What ffq_sdpa_decode, ffq_kv_decode and ffq_kv_paged_decode fill from their own parameter lists: the rules below read it and
+// enqueue() launches from it. A member with an initialiser is one that only some entry points have.
+struct DecodeCall {
+  const void* q;
+  const void* k;  // k / v: the codes [B, HKV, keys, E], or (paging) the two pools with the strides of (page, head, row)
+  const void* v;
+  int q_dt, dt;
+  const float* const* deq_scale;
+  const float* const* deq_offset;
+  int64_t batch, q_heads, kv_heads, L, E, keys;  // keys: S, S_max or max_pages * P
+  const int64_t* strides;
+  const int32_t* lens = nullptr;  // nullptr: `keys` keys for every batch; else the device-side counts, `keys` their cap, MASK_CAUSAL bottom-right
+  const void* mask = nullptr;
+  const int64_t* mask_strides = nullptr;
+  int mask_kind = MASK_NONE, mask_dt = FFQ_F32;
+  double sqrt_scale, out_num_bits;
+  const float* out_scale;
+  const float* out_offset;
+  // splits and plan_len as given (0: the rule, over plan_len or, 0 again, `keys` keys); nsplit: the count check_layout_and_workspace settles
+  int64_t splits, plan_len = 0, nsplit = 0;
+  void* out;
+  void* workspace;
+  size_t workspace_bytes;
+  const Paging* paging = nullptr;
+};
+
+int64_t rows_of(const DecodeCall& c) { return c.L * (c.q_heads / c.kv_heads); }
+
+// Each rule takes the entry point's name for its message and returns the first failing status; an entry point calls them in the order
+// its error table pins (tests/test_sdpa_decode_cpu.py, test_kv_cache_cpu.py, test_kv_paged_cpu.py) with its own steps in between.
+// The value dtype, q's container, the argument tables, the scales, E and the extents
+int check_operands(const char* name, const DecodeCall& c) {
+  if (c.dt != FFQ_BF16 && c.dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "%s: bf16 or fp16 values", name);
+  if (c.q_dt != c.dt && c.q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "%s: q is held in the value dtype or in int8", name);
+  if (!c.strides || !c.deq_scale || !c.deq_offset) return fail(FFQ_ERR_ARG, "%s: NULL argument table", name);
+  if (c.q_dt == FFQ_I8 && !c.deq_scale[0]) return fail(FFQ_ERR_DTYPE, "%s: int8 q codes need their scale", name);
+  if (!c.deq_scale[1] || !c.deq_scale[2]) return fail(FFQ_ERR_ARG, "%s: k and v are int8 codes and need their scales", name);
+  if (c.E != 64 && c.E != 128) return fail(FFQ_ERR_ARG, "%s: E must be 64 or 128", name);
+  if (c.batch < 0 || c.L < 0 || c.keys < 0 || c.q_heads <= 0 || c.kv_heads <= 0 || c.q_heads % c.kv_heads) return fail(FFQ_ERR_ARG, "%s: bad extent", name);
+  return FFQ_OK;
 }
 
-template <int E>
-void launch_paged_partial(const PagedDecodeArgs& a, bool f16, unsigned blocks, hipStream_t s) {
-  if (f16) kv_paged_partial_kernel<E, true><<<blocks, kThreads, 0, s>>>(a);
-  else kv_paged_partial_kernel<E, false><<<blocks, kThreads, 0, s>>>(a);
+// The query rows of one kv head fit the one MFMA tile
+int check_rows(const char* name, const DecodeCall& c) {
+  if (c.L > kRows || rows_of(c) > kRows) return fail(FFQ_ERR_ARG, "%s: L * (q_heads / kv_heads) must be <= %d", name, kRows);
+  return FFQ_OK;
 }
 
-// the two launches, after an entry point's checks. `lens` nullptr: S keys for every batch (ffq_sdpa_decode); else S is S_max.
-// `paging` (ffq_kv_paged_decode): k / v are the pools, their strides those of (page, head, row), S the capacity of a sequence
-int enqueue(const void* q, int q_dt, const void* k, const void* v, int dt, const float* const* deq_scale, const float* const* deq_offset,
-            const int32_t* lens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L, int64_t S, int64_t E, const int64_t* strides,
-            const void* mask, int mask_kind, int mask_dt, const int64_t* mask_strides, double sqrt_scale, const float* out_scale,
-            const float* out_offset, double out_num_bits, int64_t nsplit, void* out, void* workspace, hipStream_t s,
-            const Paging* paging = nullptr) {
-  const int64_t rows = L * (q_heads / kv_heads);
-  DecodeArgs a;
-  a.q = q; a.k = static_cast<const int8_t*>(k); a.v = static_cast<const int8_t*>(v);
+// The output quantizer and the forced split count
+int check_quantizer_and_splits(const char* name, const DecodeCall& c) {
+  if (!c.out_scale && c.out_offset) return fail(FFQ_ERR_ARG, "%s: an output offset needs its scale", name);
+  if (c.out_scale && !(c.out_num_bits >= 1.0 && c.out_num_bits <= 8.0 && c.out_num_bits == (double)(int)c.out_num_bits))
+    return fail(FFQ_ERR_ARG, "%s: the output quantizer needs an integral bit-width in 1..8", name);
+  if (c.splits < 0 || c.splits > kCap) return fail(FFQ_ERR_ARG, "%s: splits must be 0 (the rule) or 1..%d", name, (int)kCap);
+  return FFQ_OK;
+}
+
+// The sizes the kernels' 32-bit fields hold, then the buffers every entry point has; `others`: the entry point's own are there too
+int check_sizes_and_buffers(const char* name, const DecodeCall& c, bool others = true) {
+  if (c.keys >= ((int64_t)1 << 30) || c.batch * c.kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "%s: too large", name);
+  if (!c.q || !c.k || !c.v || !c.out || !others) return fail(FFQ_ERR_ARG, "%s: NULL buffer", name);
+  return FFQ_OK;
+}
+
+// Alignment (`words_aligned`, `words`: the entry point's own 4-byte tables and how its message names them), the nine strides, then
+// the split count (c.nsplit) and the workspace it needs
+int check_layout_and_workspace(const char* name, DecodeCall& c, bool words_aligned = true, const char* words = "") {
+  if (!aligned16(c.q) || !aligned16(c.k) || !aligned16(c.v) || !aligned16(c.out) || !words_aligned)
+    return fail(FFQ_ERR_ARG, "%s: buffers must be 16-byte aligned%s", name, words);
+  const int64_t q_unit = c.q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
+  for (int i = 0; i < 9; ++i)
+    if (c.strides[i] < 0 || c.strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "%s: strides must be non-negative multiples of 16 bytes", name);
+  c.nsplit = c.splits ? c.splits : plan_splits(c.batch, c.kv_heads, c.plan_len ? c.plan_len : c.keys);
+  const size_t need = workspace_bytes(c.batch, c.kv_heads, rows_of(c), c.E, c.nsplit);
+  if (!c.workspace || !aligned16(c.workspace) || c.workspace_bytes < need)
+    return fail(FFQ_ERR_WORKSPACE, "%s: the workspace needs %zu bytes, 16-byte aligned (got %zu)", name, need, c.workspace_bytes);
+  return FFQ_OK;
+}
+
+// one partial launch: `f16` / `bf16` are the dense or the paged kernel's two instantiations at the call's E
+template <typename Args>
+void launch_partial(void (*f16)(Args), void (*bf16)(Args), bool is_f16, const Args& a, unsigned blocks, hipStream_t s) {
+  auto kernel = is_f16 ? f16 : bf16;
+  kernel<<<blocks, kThreads, 0, s>>>(a);
+}
+
+// the two launches, after an entry point's checks
+int enqueue(const DecodeCall& c, hipStream_t s) {
+  const int64_t rows = rows_of(c), parts = c.batch * c.kv_heads * c.nsplit;
+  PagedDecodeArgs a;  // (the dense kernels take its DecodeArgs)
+  a.q = c.q; a.k = static_cast<const int8_t*>(c.k); a.v = static_cast<const int8_t*>(c.v);
   for (int i = 0; i < 3; ++i) {
-    a.deq_s[i] = deq_scale[i];
-    a.deq_o[i] = deq_scale[i] ? deq_offset[i] : nullptr;
-    a.qs[i] = strides[i]; a.ks[i] = strides[3 + i]; a.vs[i] = strides[6 + i];
+    a.deq_s[i] = c.deq_scale[i];
+    a.deq_o[i] = c.deq_scale[i] ? c.deq_offset[i] : nullptr;
+    a.qs[i] = c.strides[i]; a.ks[i] = c.strides[3 + i]; a.vs[i] = c.strides[6 + i];
   }
-  a.B = (int32_t)batch; a.H = (int32_t)q_heads; a.HKV = (int32_t)kv_heads; a.L = (int32_t)L; a.S = (int32_t)S;
-  a.rows = (int32_t)rows; a.splits = (int32_t)nsplit; a.tiles_per_split = (int32_t)((tiles_of(S) + nsplit - 1) / nsplit);
-  a.q_i8 = q_dt == FFQ_I8;
-  a.mask = mask; a.mask_kind = mask_kind; a.mask_dt = mask_dt;
-  for (int i = 0; i < 4; ++i) a.ms[i] = mask_kind >= MASK_BOOL ? mask_strides[i] : 0;
-  a.c = (float)sqrt_scale;
-  a.lens = lens;
-  const int64_t parts = batch * kv_heads * nsplit;
-  a.ws_o = static_cast<float*>(workspace);
-  a.ws_m = a.ws_o + parts * rows * E;
+  a.B = (int32_t)c.batch; a.H = (int32_t)c.q_heads; a.HKV = (int32_t)c.kv_heads; a.L = (int32_t)c.L; a.S = (int32_t)c.keys;
+  a.rows = (int32_t)rows; a.splits = (int32_t)c.nsplit; a.tiles_per_split = (int32_t)((tiles_of(c.keys) + c.nsplit - 1) / c.nsplit);
+  a.q_i8 = c.q_dt == FFQ_I8;
+  a.mask = c.mask; a.mask_kind = c.mask_kind; a.mask_dt = c.mask_dt;
+  for (int i = 0; i < 4; ++i) a.ms[i] = c.mask_kind >= MASK_BOOL ? c.mask_strides[i] : 0;
+  a.c = (float)c.sqrt_scale;
+  a.lens = c.lens;
+  a.ws_o = static_cast<float*>(c.workspace);
+  a.ws_m = a.ws_o + parts * rows * c.E;
   a.ws_l = a.ws_m + parts * rows;
-  const bool f16 = dt == FFQ_F16;
-  if (paging) {
-    PagedDecodeArgs p;
-    static_cast<DecodeArgs&>(p) = a;
-    p.pg = *paging;
-    if (E == 64) launch_paged_partial<64>(p, f16, (unsigned)parts, s);
-    else launch_paged_partial<128>(p, f16, (unsigned)parts, s);
-  } else if (E == 64) {
-    launch_partial<64>(a, f16, (unsigned)parts, s);
-  } else {
-    launch_partial<128>(a, f16, (unsigned)parts, s);
-  }
-  int rc = check_launch(paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel");
-  if (rc != FFQ_OK) return rc;
+  a.pg = c.paging ? *c.paging : Paging{};
+  const bool f16 = c.dt == FFQ_F16;
+  if (c.paging && c.E == 64) launch_partial(kv_paged_partial_kernel<64, true>, kv_paged_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
+  else if (c.paging) launch_partial(kv_paged_partial_kernel<128, true>, kv_paged_partial_kernel<128, false>, f16, a, (unsigned)parts, s);
+  else if (c.E == 64) launch_partial<DecodeArgs>(sdpa_decode_partial_kernel<64, true>, sdpa_decode_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
+  else launch_partial<DecodeArgs>(sdpa_decode_partial_kernel<128, true>, sdpa_decode_partial_kernel<128, false>, f16, a, (unsigned)parts, s);
+  if (int rc = check_launch(c.paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel")) return rc;
 
-  CombineArgs c;
-  c.ws_o = a.ws_o; c.ws_m = a.ws_m; c.ws_l = a.ws_l;
-  c.out = static_cast<uint16_t*>(out);
-  c.H = a.H; c.HKV = a.HKV; c.L = a.L; c.E = (int32_t)E; c.rows = a.rows; c.splits = a.splits;
-  c.out_scale = out_scale; c.out_offset = out_scale ? out_offset : nullptr;
-  const double half = out_scale ? ldexp(1.0, (int)out_num_bits - 1) : 1.0;
-  c.lo = (float)-half; c.hi = (float)(half - 1.0);
-  const unsigned cblocks = (unsigned)(batch * q_heads * L);
-  if (f16) sdpa_decode_combine_kernel<true><<<cblocks, 128, 0, s>>>(c);
-  else sdpa_decode_combine_kernel<false><<<cblocks, 128, 0, s>>>(c);
+  CombineArgs m;
+  m.ws_o = a.ws_o; m.ws_m = a.ws_m; m.ws_l = a.ws_l;
+  m.out = static_cast<uint16_t*>(c.out);
+  m.H = a.H; m.HKV = a.HKV; m.L = a.L; m.E = (int32_t)c.E; m.rows = a.rows; m.splits = a.splits;
+  m.out_scale = c.out_scale; m.out_offset = c.out_scale ? c.out_offset : nullptr;
+  const double half = c.out_scale ? ldexp(1.0, (int)c.out_num_bits - 1) : 1.0;
+  m.lo = (float)-half; m.hi = (float)(half - 1.0);
+  const unsigned cblocks = (unsigned)(c.batch * c.q_heads * c.L);
+  if (f16) sdpa_decode_combine_kernel<true><<<cblocks, 128, 0, s>>>(m);
+  else sdpa_decode_combine_kernel<false><<<cblocks, 128, 0, s>>>(m);
   return check_launch("sdpa_decode_combine_kernel");
 }
 
@@ -622,37 +688,23 @@ extern "C" int ffq_sdpa_decode(const void* q, int q_dt, const void* k, const voi
                                int64_t E, const int64_t* strides, const void* mask, int mask_kind, int mask_dt, const int64_t* mask_strides,
                                double sqrt_scale, const float* out_scale, const float* out_offset, double out_num_bits, int64_t splits,
                                void* out, void* workspace, size_t workspace_bytes_given, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "sdpa_decode: bf16 or fp16 values");
-  if (q_dt != dt && q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "sdpa_decode: q is held in the value dtype or in int8");
-  if (!strides || !deq_scale || !deq_offset) return fail(FFQ_ERR_ARG, "sdpa_decode: NULL argument table");
-  if (q_dt == FFQ_I8 && !deq_scale[0]) return fail(FFQ_ERR_DTYPE, "sdpa_decode: int8 q codes need their scale");
-  if (!deq_scale[1] || !deq_scale[2]) return fail(FFQ_ERR_ARG, "sdpa_decode: k and v are int8 codes and need their scales");
-  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "sdpa_decode: E must be 64 or 128");
-  if (batch < 0 || L < 0 || S < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return fail(FFQ_ERR_ARG, "sdpa_decode: bad extent");
-  if (L > kRows || L * (q_heads / kv_heads) > kRows) return fail(FFQ_ERR_ARG, "sdpa_decode: L * (q_heads / kv_heads) must be <= %d", kRows);
+  DecodeCall c;
+  c.q = q; c.q_dt = q_dt; c.k = k; c.v = v; c.dt = dt; c.deq_scale = deq_scale; c.deq_offset = deq_offset;
+  c.batch = batch; c.q_heads = q_heads; c.kv_heads = kv_heads; c.L = L; c.keys = S; c.E = E; c.strides = strides;
+  c.mask = mask; c.mask_kind = mask_kind; c.mask_dt = mask_dt; c.mask_strides = mask_strides;
+  c.sqrt_scale = sqrt_scale; c.out_scale = out_scale; c.out_offset = out_offset; c.out_num_bits = out_num_bits;
+  c.splits = splits; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes_given;
+  if (int rc = check_operands("sdpa_decode", c)) return rc;
+  if (int rc = check_rows("sdpa_decode", c)) return rc;
   if (mask_kind < MASK_NONE || mask_kind > MASK_FLOAT) return fail(FFQ_ERR_ARG, "sdpa_decode: bad mask kind");
   if (mask_kind == MASK_FLOAT && mask_dt != FFQ_F32 && mask_dt != FFQ_BF16 && mask_dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "sdpa_decode: float mask dtype");
-  if (!out_scale && out_offset) return fail(FFQ_ERR_ARG, "sdpa_decode: an output offset needs its scale");
-  if (out_scale && !(out_num_bits >= 1.0 && out_num_bits <= 8.0 && out_num_bits == (double)(int)out_num_bits))
-    return fail(FFQ_ERR_ARG, "sdpa_decode: the output quantizer needs an integral bit-width in 1..8");
-  if (splits < 0 || splits > kCap) return fail(FFQ_ERR_ARG, "sdpa_decode: splits must be 0 (the rule) or 1..%d", (int)kCap);
+  if (int rc = check_quantizer_and_splits("sdpa_decode", c)) return rc;
   if (batch == 0 || L == 0) return FFQ_OK;
   if (S == 0) return fail(FFQ_ERR_ARG, "sdpa_decode: S must be >= 1");
-  if (S >= ((int64_t)1 << 30) || batch * kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "sdpa_decode: too large");
-  if (!q || !k || !v || !out) return fail(FFQ_ERR_ARG, "sdpa_decode: NULL buffer");
+  if (int rc = check_sizes_and_buffers("sdpa_decode", c)) return rc;
   if (mask_kind >= MASK_BOOL && (!mask || !mask_strides)) return fail(FFQ_ERR_ARG, "sdpa_decode: the mask needs its data and strides");
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out)) return fail(FFQ_ERR_ARG, "sdpa_decode: buffers must be 16-byte aligned");
-  const int64_t q_unit = q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
-  for (int i = 0; i < 9; ++i)
-    if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "sdpa_decode: strides must be non-negative multiples of 16 bytes");
-  const int64_t rows = L * (q_heads / kv_heads);
-  const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, S);
-  const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
-  if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
-    return fail(FFQ_ERR_WORKSPACE, "sdpa_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
-  return enqueue(q, q_dt, k, v, dt, deq_scale, deq_offset, nullptr, batch, q_heads, kv_heads, L, S, E, strides, mask, mask_kind, mask_dt,
-                 mask_strides, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out, workspace, s);
+  if (int rc = check_layout_and_workspace("sdpa_decode", c)) return rc;
+  return enqueue(c, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ffq_kv_decode(const void* q, int q_dt, const void* k, const void* v, int dt, const float* const* deq_scale,
@@ -660,38 +712,22 @@ extern "C" int ffq_kv_decode(const void* q, int q_dt, const void* k, const void*
                              int64_t S_max, int64_t E, const int64_t* strides, int causal, double sqrt_scale, const float* out_scale,
                              const float* out_offset, double out_num_bits, int64_t splits, int64_t plan_len, void* out, void* workspace,
                              size_t workspace_bytes_given, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_decode: bf16 or fp16 values");
-  if (q_dt != dt && q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "kv_decode: q is held in the value dtype or in int8");
-  if (!strides || !deq_scale || !deq_offset) return fail(FFQ_ERR_ARG, "kv_decode: NULL argument table");
-  if (q_dt == FFQ_I8 && !deq_scale[0]) return fail(FFQ_ERR_DTYPE, "kv_decode: int8 q codes need their scale");
-  if (!deq_scale[1] || !deq_scale[2]) return fail(FFQ_ERR_ARG, "kv_decode: k and v are int8 codes and need their scales");
-  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_decode: E must be 64 or 128");
-  if (batch < 0 || L < 0 || S_max < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return fail(FFQ_ERR_ARG, "kv_decode: bad extent");
-  if (L > kRows || L * (q_heads / kv_heads) > kRows) return fail(FFQ_ERR_ARG, "kv_decode: L * (q_heads / kv_heads) must be <= %d", kRows);
+  DecodeCall c;
+  c.q = q; c.q_dt = q_dt; c.k = k; c.v = v; c.dt = dt; c.deq_scale = deq_scale; c.deq_offset = deq_offset;
+  c.batch = batch; c.q_heads = q_heads; c.kv_heads = kv_heads; c.L = L; c.keys = S_max; c.E = E; c.strides = strides;
+  c.lens = static_cast<const int32_t*>(lens); c.mask_kind = causal ? MASK_CAUSAL : MASK_NONE;
+  c.sqrt_scale = sqrt_scale; c.out_scale = out_scale; c.out_offset = out_offset; c.out_num_bits = out_num_bits;
+  c.splits = splits; c.plan_len = plan_len; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes_given;
+  if (int rc = check_operands("kv_decode", c)) return rc;
+  if (int rc = check_rows("kv_decode", c)) return rc;
   if (causal != 0 && causal != 1) return fail(FFQ_ERR_ARG, "kv_decode: causal is 0 (every key) or 1 (bottom-right)");
-  if (!out_scale && out_offset) return fail(FFQ_ERR_ARG, "kv_decode: an output offset needs its scale");
-  if (out_scale && !(out_num_bits >= 1.0 && out_num_bits <= 8.0 && out_num_bits == (double)(int)out_num_bits))
-    return fail(FFQ_ERR_ARG, "kv_decode: the output quantizer needs an integral bit-width in 1..8");
-  if (splits < 0 || splits > kCap) return fail(FFQ_ERR_ARG, "kv_decode: splits must be 0 (the rule) or 1..%d", (int)kCap);
+  if (int rc = check_quantizer_and_splits("kv_decode", c)) return rc;
   if (plan_len < 0 || plan_len > S_max) return fail(FFQ_ERR_ARG, "kv_decode: plan_len must be 0 (S_max) or 1..S_max");
   if (batch == 0 || L == 0) return FFQ_OK;
   if (S_max == 0) return fail(FFQ_ERR_ARG, "kv_decode: S_max must be >= 1");
-  if (S_max >= ((int64_t)1 << 30) || batch * kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "kv_decode: too large");
-  if (!q || !k || !v || !out || !lens) return fail(FFQ_ERR_ARG, "kv_decode: NULL buffer");
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (reinterpret_cast<uintptr_t>(lens) & 3u))
-    return fail(FFQ_ERR_ARG, "kv_decode: buffers must be 16-byte aligned (lens: 4-byte)");
-  const int64_t q_unit = q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
-  for (int i = 0; i < 9; ++i)
-    if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "kv_decode: strides must be non-negative multiples of 16 bytes");
-  const int64_t rows = L * (q_heads / kv_heads);
-  const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, plan_len ? plan_len : S_max);
-  const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
-  if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
-    return fail(FFQ_ERR_WORKSPACE, "kv_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
-  return enqueue(q, q_dt, k, v, dt, deq_scale, deq_offset, static_cast<const int32_t*>(lens), batch, q_heads, kv_heads, L, S_max, E, strides,
-                 nullptr, causal ? MASK_CAUSAL : MASK_NONE, FFQ_F32, nullptr, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out,
-                 workspace, s);
+  if (int rc = check_sizes_and_buffers("kv_decode", c, lens != nullptr)) return rc;
+  if (int rc = check_layout_and_workspace("kv_decode", c, aligned4(lens), " (lens: 4-byte)")) return rc;
+  return enqueue(c, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ffq_kv_paged_decode(const void* q, int q_dt, const void* k_pool, const void* v_pool, int dt, const float* const* deq_scale,
@@ -700,39 +736,23 @@ extern "C" int ffq_kv_paged_decode(const void* q, int q_dt, const void* k_pool, 
                                    const int64_t* strides, int causal, double sqrt_scale, const float* out_scale, const float* out_offset,
                                    double out_num_bits, int64_t splits, int64_t plan_len, void* out, void* workspace,
                                    size_t workspace_bytes_given, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dt != FFQ_BF16 && dt != FFQ_F16) return fail(FFQ_ERR_DTYPE, "kv_paged_decode: bf16 or fp16 values");
-  if (q_dt != dt && q_dt != FFQ_I8) return fail(FFQ_ERR_DTYPE, "kv_paged_decode: q is held in the value dtype or in int8");
-  if (!strides || !deq_scale || !deq_offset) return fail(FFQ_ERR_ARG, "kv_paged_decode: NULL argument table");
-  if (q_dt == FFQ_I8 && !deq_scale[0]) return fail(FFQ_ERR_DTYPE, "kv_paged_decode: int8 q codes need their scale");
-  if (!deq_scale[1] || !deq_scale[2]) return fail(FFQ_ERR_ARG, "kv_paged_decode: k and v are int8 codes and need their scales");
-  if (E != 64 && E != 128) return fail(FFQ_ERR_ARG, "kv_paged_decode: E must be 64 or 128");
-  if (batch < 0 || L < 0 || q_heads <= 0 || kv_heads <= 0 || q_heads % kv_heads) return fail(FFQ_ERR_ARG, "kv_paged_decode: bad extent");
+  DecodeCall c;
+  c.q = q; c.q_dt = q_dt; c.k = k_pool; c.v = v_pool; c.dt = dt; c.deq_scale = deq_scale; c.deq_offset = deq_offset;
+  c.batch = batch; c.q_heads = q_heads; c.kv_heads = kv_heads; c.L = L; c.keys = 0; c.E = E; c.strides = strides;  // (keys: once the geometry is sound)
+  c.lens = static_cast<const int32_t*>(lens); c.mask_kind = causal ? MASK_CAUSAL : MASK_NONE;
+  c.sqrt_scale = sqrt_scale; c.out_scale = out_scale; c.out_offset = out_offset; c.out_num_bits = out_num_bits;
+  c.splits = splits; c.plan_len = plan_len; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes_given;
+  if (int rc = check_operands("kv_paged_decode", c)) return rc;
   if (const char* why = paging_error(num_pages, P, max_pages, table_stride)) return fail(FFQ_ERR_ARG, "kv_paged_decode: %s", why);
-  const int64_t C = max_pages * P;  // a sequence's capacity, in the place of S_max
-  if (L > kRows || L * (q_heads / kv_heads) > kRows) return fail(FFQ_ERR_ARG, "kv_paged_decode: L * (q_heads / kv_heads) must be <= %d", kRows);
+  c.keys = max_pages * P;  // a sequence's capacity, in the place of S_max (below 2^30)
+  if (int rc = check_rows("kv_paged_decode", c)) return rc;
   if (causal != 0 && causal != 1) return fail(FFQ_ERR_ARG, "kv_paged_decode: causal is 0 (every key) or 1 (bottom-right)");
-  if (!out_scale && out_offset) return fail(FFQ_ERR_ARG, "kv_paged_decode: an output offset needs its scale");
-  if (out_scale && !(out_num_bits >= 1.0 && out_num_bits <= 8.0 && out_num_bits == (double)(int)out_num_bits))
-    return fail(FFQ_ERR_ARG, "kv_paged_decode: the output quantizer needs an integral bit-width in 1..8");
-  if (splits < 0 || splits > kCap) return fail(FFQ_ERR_ARG, "kv_paged_decode: splits must be 0 (the rule) or 1..%d", (int)kCap);
-  if (plan_len < 0 || plan_len > C) return fail(FFQ_ERR_ARG, "kv_paged_decode: plan_len must be 0 (max_pages * P) or 1..max_pages * P");
+  if (int rc = check_quantizer_and_splits("kv_paged_decode", c)) return rc;
+  if (plan_len < 0 || plan_len > c.keys) return fail(FFQ_ERR_ARG, "kv_paged_decode: plan_len must be 0 (max_pages * P) or 1..max_pages * P");
   if (batch == 0 || L == 0) return FFQ_OK;
-  if (batch * kv_heads >= ((int64_t)1 << 24)) return fail(FFQ_ERR_ARG, "kv_paged_decode: too large");
-  if (!q || !k_pool || !v_pool || !out || !lens || !block_table) return fail(FFQ_ERR_ARG, "kv_paged_decode: NULL buffer");
-  if (!aligned16(q) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(out) || (reinterpret_cast<uintptr_t>(lens) & 3u) ||
-      (reinterpret_cast<uintptr_t>(block_table) & 3u))
-    return fail(FFQ_ERR_ARG, "kv_paged_decode: buffers must be 16-byte aligned (lens, block_table: 4-byte)");
-  const int64_t q_unit = q_dt == FFQ_I8 ? 16 : 8;  // elements per 16 bytes
-  for (int i = 0; i < 9; ++i)
-    if (strides[i] < 0 || strides[i] % (i < 3 ? q_unit : 16)) return fail(FFQ_ERR_ARG, "kv_paged_decode: strides must be non-negative multiples of 16 bytes");
-  const int64_t rows = L * (q_heads / kv_heads);
-  const int64_t nsplit = splits ? splits : plan_splits(batch, kv_heads, plan_len ? plan_len : C);
-  const size_t need = workspace_bytes(batch, kv_heads, rows, E, nsplit);
-  if (!workspace || !aligned16(workspace) || workspace_bytes_given < need)
-    return fail(FFQ_ERR_WORKSPACE, "kv_paged_decode: the workspace needs %zu bytes, 16-byte aligned (got %zu)", need, workspace_bytes_given);
+  if (int rc = check_sizes_and_buffers("kv_paged_decode", c, lens && block_table)) return rc;
+  if (int rc = check_layout_and_workspace("kv_paged_decode", c, aligned4(lens) && aligned4(block_table), " (lens, block_table: 4-byte)")) return rc;
   const Paging paging = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
-  return enqueue(q, q_dt, k_pool, v_pool, dt, deq_scale, deq_offset, static_cast<const int32_t*>(lens), batch, q_heads, kv_heads, L, C, E, strides,
-                 nullptr, causal ? MASK_CAUSAL : MASK_NONE, FFQ_F32, nullptr, sqrt_scale, out_scale, out_offset, out_num_bits, nsplit, out,
-                 workspace, s, &paging);
+  c.paging = &paging;
+  return enqueue(c, static_cast<hipStream_t>(stream));
 }

@@ -109,7 +109,63 @@ def composed_attend(query: Any, k_cache: torch.Tensor, v_cache: torch.Tensor, le
     return out
 
 
-class QuantizedKVCache:
+class _CacheBase:
+    """What the two caches share: the data dtype, the head size and the two quantizers, the choice between the kernels and the composed
+    chain, the checks of ``append``, and the whole of ``attend``. A subclass allocates its buffers and ``lengths`` (int32 ``[B]``),
+    names its two entry points in ``_SYMBOLS`` and supplies the two calls that differ (``_native_attend``, ``_composed_attend``)."""
+
+    _SYMBOLS: tuple[str, str]
+
+    def __init__(self, dtype: torch.dtype, head_dim: int, key_quantizer: LinearQuantizer, value_quantizer: LinearQuantizer) -> None:
+        name = type(self).__name__
+        if dtype not in _VALUES:
+            raise ValueError(f"{name}: the data dtype is bf16 or fp16, got {dtype}")
+        if head_dim not in (64, 128):
+            raise ValueError(f"{name}: head_dim must be 64 or 128, got {head_dim}")
+        _quantizer_params(key_quantizer, "key")
+        _quantizer_params(value_quantizer, "value")
+        self.key_quantizer, self.value_quantizer, self.dtype = key_quantizer, value_quantizer, dtype
+
+    def _native(self, *tensors: torch.Tensor) -> bool:
+        lib = _native.library()
+        return all(t.is_cuda for t in (*tensors, self.lengths)) and all(getattr(lib, name, None) is not None for name in self._SYMBOLS)
+
+    def _new_rows(self, key: torch.Tensor, value: torch.Tensor, store: torch.Tensor, rows: str):
+        """``append``'s checks of key / value against `store` (the K cache or pool; `rows` is how the class words what it takes), then
+        ``lengths += L``. Returns the two quantizers' ``(scale, offset, bits)``."""
+        name = type(self).__name__
+        if key.dim() != 4 or tuple(key.shape) != tuple(value.shape) or (key.shape[0], key.shape[1], key.shape[3]) != (self.lengths.shape[0], store.shape[1], store.shape[3]):
+            raise ValueError(f"{name}.append: key / value are {rows}, got {tuple(key.shape)}, {tuple(value.shape)}")
+        if key.dtype != self.dtype or value.dtype != self.dtype:
+            raise ValueError(f"{name}.append: the new rows are plain {self.dtype} values, got {key.dtype}, {value.dtype}")
+        params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
+        self.lengths.add_(key.shape[2])
+        return params
+
+    def attend(self, query: Any, is_causal: bool = True, scale: float | None = None, output_quantizer: Any = None, splits: int = 0,
+               plan_len: int | None = None) -> torch.Tensor:
+        """Attention of query ``[B, H_q, L, E]`` (plain, or per-tensor codes in an int8 or value-dtype container) over every sequence's
+        own keys; ``H_q`` is a multiple of the cache's heads (GQA). ``is_causal`` is bottom-right. `output_quantizer`: None, a stub, or
+        one the decode kernels fuse (then the result is A2 of its codes in the data dtype). ``splits`` / ``plan_len``: ``ops.kv_decode``
+        (``ops.kv_paged_decode`` over pages: the same operands, refusals and bits)."""
+        kernels = _kernels()
+        if isinstance(query, QuantizedTensor):
+            if kernels._codes_dtype(query, ("int8", "value")) != self.dtype:
+                raise ValueError(f"{type(self).__name__}.attend: a quantized query holds per-tensor codes of the cache's dtype in an int8 or value-dtype container")
+        elif type(query) is not torch.Tensor or query.dtype != self.dtype:
+            raise ValueError(f"{type(self).__name__}.attend: the query is plain {self.dtype} or per-tensor codes of it")
+        with torch.no_grad():
+            fused = kernels._fused(output_quantizer)
+        if fused is False:
+            raise ValueError(f"{type(self).__name__}.attend: the output quantizer is not one the decode kernels fuse")
+        raw, q_dequant = kernels._dequant(query)
+        if not self._native(raw):
+            return self._composed_attend(query, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer if fused else None)
+        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
+        return self._native_attend(raw, is_causal, scale, fused or None, (q_dequant, k_params[:2], v_params[:2]), splits, plan_len)
+
+
+class QuantizedKVCache(_CacheBase):
     """int8 K / V codes for `batch` sequences of up to `max_len` positions, quantized by two per-tensor static quantizers.
 
     ``layout="bhse"`` allocates ``[B, H, S_max, E]``; ``"bshe"`` allocates ``[B, S_max, H, E]`` (a position's heads side by side, the
@@ -120,24 +176,16 @@ class QuantizedKVCache:
                  dtype: torch.dtype = torch.bfloat16, device: torch.device | str = "cuda", layout: str = "bhse") -> None:
         if layout not in LAYOUTS:
             raise ValueError(f"QuantizedKVCache: layout is one of {LAYOUTS}, got {layout!r}")
-        if dtype not in _VALUES:
-            raise ValueError(f"QuantizedKVCache: the data dtype is bf16 or fp16, got {dtype}")
-        if head_dim not in (64, 128):
-            raise ValueError(f"QuantizedKVCache: head_dim must be 64 or 128, got {head_dim}")
         if min(batch, kv_heads, max_len) < 1:
             raise ValueError(f"QuantizedKVCache: batch, kv_heads and max_len are positive, got {batch}, {kv_heads}, {max_len}")
-        _quantizer_params(key_quantizer, "key")
-        _quantizer_params(value_quantizer, "value")
-        self.key_quantizer, self.value_quantizer = key_quantizer, value_quantizer
-        self.dtype, self.layout, self.max_len = dtype, layout, max_len
+        super().__init__(dtype, head_dim, key_quantizer, value_quantizer)
+        self.layout, self.max_len = layout, max_len
         shape = (batch, kv_heads, max_len, head_dim) if layout == "bhse" else (batch, max_len, kv_heads, head_dim)
         buffers = [torch.zeros(shape, dtype=torch.int8, device=device) for _ in range(2)]
         self.k_cache, self.v_cache = (t if layout == "bhse" else t.transpose(1, 2) for t in buffers)
         self.lengths = torch.zeros(batch, dtype=torch.int32, device=device)
 
-    def _native(self, *tensors: torch.Tensor) -> bool:
-        lib = _native.library()
-        return all(t.is_cuda for t in (*tensors, self.k_cache)) and all(getattr(lib, name, None) is not None for name in ("ffq_kv_append", "ffq_kv_decode"))
+    _SYMBOLS = ("ffq_kv_append", "ffq_kv_decode")
 
     def reset(self, lengths: torch.Tensor | Sequence[int] | None = None) -> None:
         """Every sequence back to length 0, or to `lengths` (the codes stay where they are: positions below a length are the cache)."""
@@ -150,39 +198,17 @@ class QuantizedKVCache:
         """Quantize key / value ``[B, H, L, E]`` (plain values in the cache's dtype) to the end of every sequence: ``lengths += L``, then
         row l of batch b goes to position ``lengths[b] - L + l``; rows outside ``[0, max_len)`` are dropped. ``rope=(cos, sin)``,
         ``[P >= max_len, E]`` tables in the data dtype: K is rotated with the row of its position first."""
-        if key.dim() != 4 or tuple(key.shape) != tuple(value.shape) or (key.shape[0], key.shape[1], key.shape[3]) != (self.k_cache.shape[0], self.k_cache.shape[1], self.k_cache.shape[3]):
-            raise ValueError(f"QuantizedKVCache.append: key / value are [B, H, L, E] rows of a {tuple(self.k_cache.shape)} cache, got {tuple(key.shape)}, {tuple(value.shape)}")
-        if key.dtype != self.dtype or value.dtype != self.dtype:
-            raise ValueError(f"QuantizedKVCache.append: the new rows are plain {self.dtype} values, got {key.dtype}, {value.dtype}")
-        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
-        self.lengths.add_(key.shape[2])
+        k_params, v_params = self._new_rows(key, value, self.k_cache, f"[B, H, L, E] rows of a {tuple(self.k_cache.shape)} cache")
         if self._native(key, value):
             ops.kv_append(key.detach(), value.detach(), self.k_cache, self.v_cache, self.lengths, k_params, v_params, rope=rope)
         else:
             composed_append(self.k_cache, self.v_cache, self.lengths, key.detach(), value.detach(), self.key_quantizer, self.value_quantizer, rope)
 
-    def attend(self, query: Any, is_causal: bool = True, scale: float | None = None, output_quantizer: Any = None, splits: int = 0,
-               plan_len: int | None = None) -> torch.Tensor:
-        """Attention of query ``[B, H_q, L, E]`` (plain, or per-tensor codes in an int8 or value-dtype container) over every sequence's
-        own keys; ``H_q`` is a multiple of the cache's heads (GQA). ``is_causal`` is bottom-right. `output_quantizer`: None, a stub, or
-        one the decode kernels fuse (then the result is A2 of its codes in the data dtype). ``splits`` / ``plan_len``: ``ops.kv_decode``."""
-        kernels = _kernels()
-        if isinstance(query, QuantizedTensor):
-            if kernels._codes_dtype(query, ("int8", "value")) != self.dtype:
-                raise ValueError("QuantizedKVCache.attend: a quantized query holds per-tensor codes of the cache's dtype in an int8 or value-dtype container")
-        elif type(query) is not torch.Tensor or query.dtype != self.dtype:
-            raise ValueError(f"QuantizedKVCache.attend: the query is plain {self.dtype} or per-tensor codes of it")
-        with torch.no_grad():
-            fused = kernels._fused(output_quantizer)
-        if fused is False:
-            raise ValueError("QuantizedKVCache.attend: the output quantizer is not one the decode kernels fuse")
-        raw, q_dequant = kernels._dequant(query)
-        if not self._native(raw):
-            return composed_attend(query, self.k_cache, self.v_cache, self.lengths, self.key_quantizer, self.value_quantizer, self.dtype,
-                                   is_causal=is_causal, scale=scale, output_quantizer=output_quantizer if fused else None)
-        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
-        return ops.kv_decode(raw, self.k_cache, self.v_cache, self.lengths, is_causal=is_causal, scale=scale, output_quantizer=fused or None,
-                             dequant=(q_dequant, k_params[:2], v_params[:2]), dtype=self.dtype, splits=splits, plan_len=plan_len)
+    def _native_attend(self, raw, is_causal, scale, output_quantizer, dequant, splits, plan_len) -> torch.Tensor:
+        return ops.kv_decode(raw, self.k_cache, self.v_cache, self.lengths, is_causal, scale, output_quantizer, dequant, self.dtype, splits, plan_len)
+
+    def _composed_attend(self, query: Any, **how: Any) -> torch.Tensor:
+        return composed_attend(query, self.k_cache, self.v_cache, self.lengths, self.key_quantizer, self.value_quantizer, self.dtype, **how)
 
     def keys(self, length: int) -> QuantizedTensor:
         """The first `length` positions of every sequence's keys as the QuantizedTensor the key quantizer would have returned."""
@@ -247,7 +273,7 @@ def composed_paged_attend(query: Any, k_pool: torch.Tensor, v_pool: torch.Tensor
                            dtype, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer)
 
 
-class PagedQuantizedKVCache:
+class PagedQuantizedKVCache(_CacheBase):
     """:class:`QuantizedKVCache` with the codes in fixed-size pages: two int8 pools of `num_pages` pages of `page_size` positions
     shared by `batch` sequences, each of which addresses up to `max_pages_per_seq` of them through its row of ``block_table``
     (int32 ``[batch, max_pages_per_seq]`` on the device, -1 where no page is assigned). A sequence owns only the pages it uses, a
@@ -267,19 +293,13 @@ class PagedQuantizedKVCache:
         name = "PagedQuantizedKVCache"
         if layout not in PAGED_LAYOUTS:
             raise ValueError(f"{name}: layout is one of {PAGED_LAYOUTS}, got {layout!r}")
-        if dtype not in _VALUES:
-            raise ValueError(f"{name}: the data dtype is bf16 or fp16, got {dtype}")
-        if head_dim not in (64, 128):
-            raise ValueError(f"{name}: head_dim must be 64 or 128, got {head_dim}")
         if not 16 <= page_size <= 256 or page_size & (page_size - 1):
             raise ValueError(f"{name}: page_size is a power of two in 16..256, got {page_size}")
         if min(num_pages, kv_heads, batch, max_pages_per_seq) < 1 or max_pages_per_seq * page_size >= 1 << 30:
             raise ValueError(f"{name}: num_pages, kv_heads, batch and max_pages_per_seq are positive and a sequence stays below 2^30 positions, "
                              f"got {num_pages}, {kv_heads}, {batch}, {max_pages_per_seq}")
-        _quantizer_params(key_quantizer, "key")
-        _quantizer_params(value_quantizer, "value")
-        self.key_quantizer, self.value_quantizer = key_quantizer, value_quantizer
-        self.dtype, self.layout, self.page_size, self.num_pages = dtype, layout, page_size, num_pages
+        super().__init__(dtype, head_dim, key_quantizer, value_quantizer)
+        self.layout, self.page_size, self.num_pages = layout, page_size, num_pages
         self.capacity = max_pages_per_seq * page_size  # positions a sequence can address
         shape = (num_pages, kv_heads, page_size, head_dim) if layout == "phse" else (num_pages, page_size, kv_heads, head_dim)
         buffers = [torch.zeros(shape, dtype=torch.int8, device=device) for _ in range(2)]
@@ -345,47 +365,25 @@ class PagedQuantizedKVCache:
         self.lengths[dst:dst + 1].fill_(whole * self.page_size)
 
     # ---- the device side
-    def _native(self, *tensors: torch.Tensor) -> bool:
-        lib = _native.library()
-        return all(t.is_cuda for t in (*tensors, self.k_pool)) and all(getattr(lib, name, None) is not None for name in ("ffq_kv_paged_append", "ffq_kv_paged_decode"))
+    _SYMBOLS = ("ffq_kv_paged_append", "ffq_kv_paged_decode")
 
     def append(self, key: torch.Tensor, value: torch.Tensor, rope: Rope | None = None) -> None:
         """:meth:`QuantizedKVCache.append` into pages: ``lengths += L``, then row l of batch b goes to position ``lengths[b] - L + l``
         of its sequence; rows outside ``[0, capacity)`` or on a page never reserved are dropped. The rotary tables need `capacity` rows."""
-        B, H, E = self.lengths.shape[0], self.k_pool.shape[1], self.k_pool.shape[3]
-        if key.dim() != 4 or tuple(key.shape) != tuple(value.shape) or (key.shape[0], key.shape[1], key.shape[3]) != (B, H, E):
-            raise ValueError(f"PagedQuantizedKVCache.append: key / value are [{B}, {H}, L, {E}] rows, got {tuple(key.shape)}, {tuple(value.shape)}")
-        if key.dtype != self.dtype or value.dtype != self.dtype:
-            raise ValueError(f"PagedQuantizedKVCache.append: the new rows are plain {self.dtype} values, got {key.dtype}, {value.dtype}")
-        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
-        self.lengths.add_(key.shape[2])
+        k_params, v_params = self._new_rows(key, value, self.k_pool, f"[{self.lengths.shape[0]}, {self.k_pool.shape[1]}, L, {self.k_pool.shape[3]}] rows")
         if self._native(key, value):
             ops.kv_paged_append(key.detach(), value.detach(), self.k_pool, self.v_pool, self.lengths, self.block_table, k_params, v_params, rope=rope)
         else:
             composed_paged_append(self.k_pool, self.v_pool, self.block_table, self.lengths, key.detach(), value.detach(), self.key_quantizer,
                                   self.value_quantizer, rope)
 
-    def attend(self, query: Any, is_causal: bool = True, scale: float | None = None, output_quantizer: Any = None, splits: int = 0,
-               plan_len: int | None = None) -> torch.Tensor:
-        """:meth:`QuantizedKVCache.attend` over pages: the same operands, refusals and bits (``ops.kv_paged_decode``)."""
-        kernels = _kernels()
-        if isinstance(query, QuantizedTensor):
-            if kernels._codes_dtype(query, ("int8", "value")) != self.dtype:
-                raise ValueError("PagedQuantizedKVCache.attend: a quantized query holds per-tensor codes of the cache's dtype in an int8 or value-dtype container")
-        elif type(query) is not torch.Tensor or query.dtype != self.dtype:
-            raise ValueError(f"PagedQuantizedKVCache.attend: the query is plain {self.dtype} or per-tensor codes of it")
-        with torch.no_grad():
-            fused = kernels._fused(output_quantizer)
-        if fused is False:
-            raise ValueError("PagedQuantizedKVCache.attend: the output quantizer is not one the decode kernels fuse")
-        raw, q_dequant = kernels._dequant(query)
-        if not self._native(raw):
-            return composed_paged_attend(query, self.k_pool, self.v_pool, self.block_table, self.lengths, self.key_quantizer, self.value_quantizer,
-                                         self.dtype, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer if fused else None)
-        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
-        return ops.kv_paged_decode(raw, self.k_pool, self.v_pool, self.lengths, self.block_table, is_causal=is_causal, scale=scale,
-                                   output_quantizer=fused or None, dequant=(q_dequant, k_params[:2], v_params[:2]), dtype=self.dtype, splits=splits,
-                                   plan_len=plan_len)
+    def _native_attend(self, raw, is_causal, scale, output_quantizer, dequant, splits, plan_len) -> torch.Tensor:
+        return ops.kv_paged_decode(raw, self.k_pool, self.v_pool, self.lengths, self.block_table, is_causal, scale, output_quantizer, dequant, self.dtype,
+                                   splits, plan_len)
+
+    def _composed_attend(self, query: Any, **how: Any) -> torch.Tensor:
+        return composed_paged_attend(query, self.k_pool, self.v_pool, self.block_table, self.lengths, self.key_quantizer, self.value_quantizer,
+                                     self.dtype, **how)
 
     def dense(self, seq: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
         """The K and V codes gathered into dense ``[B, H, capacity, E]`` tensors (``[H, capacity, E]`` for one sequence), zeros where no

@@ -53,6 +53,88 @@ def sdpa_decode_workspace_bytes(B: int, HKV: int, rows: int, E: int, splits: int
     return 0 if min(B, HKV, rows, E, splits) <= 0 else B * HKV * splits * rows * (E + 2) * 4
 
 
+def _rows_ok(t: torch.Tensor) -> bool:
+    return t.stride(-1) == 1 and not any(st * t.element_size() % 16 for st in _strides(t)) and t.data_ptr() % 16 == 0
+
+
+def _check_decode(name: str, query: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dequant: Sequence[Dequant | None], dtype: torch.dtype | None,
+                  HKV: int, splits: int) -> tuple[torch.dtype, int, int, int, int, int, int]:
+    """What ``sdpa_decode``, ``kv_decode`` and ``kv_paged_decode`` ask alike of a 4-D query over `HKV` kv heads: the data dtype, int8 q
+    codes, E, the GQA group, the rows of one kv head, `splits`, and the rows of q / k / v in memory. ``(dt, B, H, L, E, HKV, rows)``, else
+    RuntimeError under the wrapper's `name`."""
+    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
+    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
+        raise RuntimeError(f"{name}: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
+    if query.dtype == torch.int8 and dequant[0] is None:
+        raise RuntimeError(f"{name}: int8 q codes need their (scale, offset)")
+    B, H, L, E = query.shape
+    if E not in (64, 128):
+        raise RuntimeError(f"{name}: E must be 64 or 128, got {E}")
+    if HKV < 1 or H % HKV:
+        raise RuntimeError(f"{name}: {H} query heads are not a multiple of {HKV} kv heads")
+    rows = L * (H // HKV)
+    if rows > MAX_ROWS:
+        raise RuntimeError(f"{name}: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
+    if not 0 <= splits <= MAX_SPLITS:
+        raise RuntimeError(f"{name}: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
+    for t in (query, k, v):
+        if not _rows_ok(t):
+            raise RuntimeError(f"{name}: the last dimension must be contiguous with 16-byte aligned rows")
+    return dt, B, H, L, E, HKV, rows
+
+
+def _decode_tables(dequant: Sequence[Dequant | None], output_quantizer):
+    """(deq_scale[3], deq_offset[3], out scale, out offset, out bits, the tensors to keep alive) as the decode entry points take them."""
+    keep: list[torch.Tensor] = []
+    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
+    for i, d in enumerate(dequant):
+        if d is not None:
+            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
+            keep += [t for t in (s, o) if t is not None]
+            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
+    out_s = out_o = None
+    bits = 8.0
+    if output_quantizer is not None:
+        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
+        bits = float(output_quantizer[2])
+        keep += [t for t in (out_s, out_o) if t is not None]
+    return deq_s, deq_o, out_s, out_o, bits, keep
+
+
+def _split_workspace(B: int, HKV: int, rows: int, E: int, keys: int, splits: int, device: torch.device):
+    """(the split count, the workspace's bytes, the workspace) of a decode call that plans over `keys` keys: `splits`, or the rule.
+    The count and the size are the restatements above, which tests/test_sdpa_decode_cpu.py holds equal to the library's queries; the
+    entry point checks the size again (FFQ_ERR_WORKSPACE)."""
+    count = splits or sdpa_decode_plan(B, HKV, keys, rows, E)
+    nbytes = sdpa_decode_workspace_bytes(B, HKV, rows, E, count)
+    return count, nbytes, torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _run_decode(symbol: str, query: torch.Tensor, k: torch.Tensor, v: torch.Tensor, others: Sequence[torch.Tensor | None], dt: torch.dtype,
+                shape: tuple[int, ...], plan_keys: int, splits: int, scale: float | None, dequant: Sequence[Dequant | None], output_quantizer,
+                extents: tuple, selection: tuple, split_args: tuple | None = None) -> torch.Tensor:
+    """The tail of the three decode wrappers, after their checks: the tables, the library, the split count and the workspace, the
+    output, and the call of `symbol`. `others` are the entry point's own tensors (a mask; lens; lens and the block table); `extents`
+    and `selection` are its own arguments on either side of the strides; `split_args` is what it takes in the place of the split
+    count (``splits`` and ``plan_len`` as given, for the cache forms)."""
+    B, H, HKV, L, E, rows = shape
+    deq_s, deq_o, out_s, out_o, bits, keep = _decode_tables(dequant, output_quantizer)
+    lib, stream = _base._prepare(query, k, v, *others, *keep)
+    entry = _entry(lib, symbol)
+    count, nbytes, workspace = _split_workspace(B, HKV, rows, E, plan_keys, splits, query.device)
+    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
+    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(k), *_strides(v))
+    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
+    lib.check(
+        entry(
+            _ptr(query), _tag(query.dtype), _ptr(k), _ptr(v), _tag(dt), deq_s, deq_o, *extents, strides, *selection, sqrt_scale, _ptr(out_s),
+            _ptr(out_o), bits, *(split_args or (count,)), _ptr(out), _ptr(workspace), nbytes, stream,
+        )
+    )
+    del keep
+    return out
+
+
 def sdpa_decode(
     query: torch.Tensor,
     key: torch.Tensor,
@@ -74,29 +156,12 @@ def sdpa_decode(
         raise RuntimeError("sdpa_decode: q / k / v are 4-D [B, H, L|S, E]")
     if key.dtype != torch.int8 or value.dtype != torch.int8 or dequant[1] is None or dequant[2] is None:
         raise RuntimeError(f"sdpa_decode: k / v are int8 codes with their (scale, offset), got {key.dtype}, {value.dtype}")
-    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
-    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
-        raise RuntimeError(f"sdpa_decode: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
-    if query.dtype == torch.int8 and dequant[0] is None:
-        raise RuntimeError("sdpa_decode: int8 q codes need their (scale, offset)")
-    B, H, L, E = query.shape
-    _, HKV, S, _ = key.shape
+    S = key.shape[2]
+    dt, B, H, L, E, HKV, rows = _check_decode("sdpa_decode", query, key, value, dequant, dtype, key.shape[1], splits)
     if key.shape[0] != B or key.shape[3] != E or tuple(value.shape) != (B, HKV, S, E):
         raise RuntimeError(f"sdpa_decode: shapes {tuple(query.shape)}, {tuple(key.shape)}, {tuple(value.shape)} do not fit")
-    if E not in (64, 128):
-        raise RuntimeError(f"sdpa_decode: E must be 64 or 128, got {E}")
-    if HKV < 1 or H % HKV:
-        raise RuntimeError(f"sdpa_decode: {H} query heads are not a multiple of {HKV} kv heads")
-    rows = L * (H // HKV)
-    if rows > MAX_ROWS:
-        raise RuntimeError(f"sdpa_decode: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
     if min(B, L, S) < 1:
         raise RuntimeError(f"sdpa_decode: empty operands {tuple(query.shape)}, {tuple(key.shape)}")
-    if not 0 <= splits <= MAX_SPLITS:
-        raise RuntimeError(f"sdpa_decode: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
-    for t in (query, key, value):
-        if t.stride(-1) != 1 or any(st * t.element_size() % 16 for st in _strides(t)) or t.data_ptr() % 16:
-            raise RuntimeError("sdpa_decode: the last dimension must be contiguous with 16-byte aligned rows")
     if attn_mask is not None and is_causal:
         raise ValueError("Explicit attn_mask should not be set when is_causal=True")
     mask, mask_kind, mask_dt, mask_strides = None, MASK_KINDS["causal" if is_causal else "none"], _tag(torch.float32), None
@@ -111,32 +176,5 @@ def sdpa_decode(
         else:
             raise RuntimeError(f"sdpa_decode: a mask is bool or float, got {mask.dtype}")
         mask_strides = (ctypes.c_int64 * 4)(*mask.stride())
-    keep: list[torch.Tensor] = []
-    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
-    for i, d in enumerate(dequant):
-        if d is not None:
-            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
-            keep += [t for t in (s, o) if t is not None]
-            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
-    out_s = out_o = None
-    bits = 8.0
-    if output_quantizer is not None:
-        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
-        bits = float(output_quantizer[2])
-        keep += [t for t in (out_s, out_o) if t is not None]
-    lib, stream = _base._prepare(query, key, value, mask, *keep)
-    entry = _entry(lib, "ffq_sdpa_decode")
-    count = splits or int(_entry(lib, "ffq_sdpa_decode_splits")(B, HKV, S, rows, E))
-    nbytes = int(_entry(lib, "ffq_sdpa_decode_workspace_bytes")(B, HKV, rows, E, count))
-    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
-    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(key), *_strides(value))
-    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
-    lib.check(
-        entry(
-            _ptr(query), _tag(query.dtype), _ptr(key), _ptr(value), _tag(dt), deq_s, deq_o, B, H, HKV, L, S, E, strides, _ptr(mask), mask_kind,
-            mask_dt, mask_strides, sqrt_scale, _ptr(out_s), _ptr(out_o), bits, count, _ptr(out), _ptr(workspace), nbytes, stream,
-        )
-    )
-    del keep
-    return out
+    return _run_decode("ffq_sdpa_decode", query, key, value, (mask,), dt, (B, H, HKV, L, E, rows), S, splits, scale, dequant, output_quantizer,
+                       (B, H, HKV, L, S, E), (_ptr(mask), mask_kind, mask_dt, mask_strides))

@@ -13,7 +13,6 @@ and never on the host. The codes and the attention's bits are those of the dense
 from __future__ import annotations
 
 import ctypes
-import math
 
 from typing import Sequence
 
@@ -21,15 +20,11 @@ import torch
 
 from fastforward_amd.ops import _base
 from fastforward_amd.ops._base import _ptr, _tag
-from fastforward_amd.ops.decode import MAX_ROWS, MAX_SPLITS, Dequant, sdpa_decode_plan, sdpa_decode_workspace_bytes
+from fastforward_amd.ops.decode import Dequant, _check_decode, _rows_ok, _run_decode
 from fastforward_amd.ops.modules import _entry
 from fastforward_amd.ops.sdpa import _scalar, _strides
 
 Quantizer = tuple[torch.Tensor, "torch.Tensor | None", float]
-
-
-def _rows_ok(t: torch.Tensor) -> bool:
-    return t.stride(-1) == 1 and not any(st * t.element_size() % 16 for st in _strides(t)) and t.data_ptr() % 16 == 0
 
 
 def _lens_ok(lens: torch.Tensor, B: int) -> bool:
@@ -61,24 +56,6 @@ def _rope_tables(name: str, rope: tuple[torch.Tensor, torch.Tensor] | None, dt: 
     return cos, sin
 
 
-def _decode_tables(dequant: Sequence[Dequant | None], output_quantizer):
-    """(deq_scale[3], deq_offset[3], out scale, out offset, out bits, the tensors to keep alive) as the decode entry points take them."""
-    keep: list[torch.Tensor] = []
-    deq_s, deq_o = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
-    for i, d in enumerate(dequant):
-        if d is not None:
-            s, o = _scalar(d[0], "dequant scale"), _scalar(d[1], "dequant offset")
-            keep += [t for t in (s, o) if t is not None]
-            deq_s[i], deq_o[i] = _ptr(s), _ptr(o)
-    out_s = out_o = None
-    bits = 8.0
-    if output_quantizer is not None:
-        out_s, out_o = _scalar(output_quantizer[0], "output scale"), _scalar(output_quantizer[1], "output offset")
-        bits = float(output_quantizer[2])
-        keep += [t for t in (out_s, out_o) if t is not None]
-    return deq_s, deq_o, out_s, out_o, bits, keep
-
-
 def _pools_ok(name: str, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, B: int, HKV: int, E: int) -> tuple[int, int, int]:
     """(num_pages, P, max_pages) of pools [num_pages, HKV, P, E] (int8, any page / head / row strides) and a block table int32
     [B, max_pages] whose rows are contiguous, else RuntimeError."""
@@ -99,6 +76,46 @@ def _pools_ok(name: str, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table
     return num_pages, P, max_pages
 
 
+def _check_new_rows(name: str, k_new: torch.Tensor, v_new: torch.Tensor, k_store: torch.Tensor, v_store: torch.Tensor, lens: torch.Tensor) -> None:
+    """What ``kv_append`` and ``kv_paged_append`` ask alike of 4-D new rows that fit their caches or pools (`k_store`, `v_store`): the
+    dtype, E, a kv head, `lens`, and the rows of all four tensors in memory; else RuntimeError under the wrapper's `name`."""
+    B, HKV, _, E = k_new.shape
+    if k_new.dtype not in (torch.bfloat16, torch.float16) or v_new.dtype != k_new.dtype:
+        raise RuntimeError(f"{name}: the new rows are bf16 or fp16, both the same, got {k_new.dtype} and {v_new.dtype}")
+    if E not in (64, 128):
+        raise RuntimeError(f"{name}: E must be 64 or 128, got {E}")
+    if HKV < 1:
+        raise RuntimeError(f"{name}: no kv head")
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    for t in (k_new, v_new, k_store, v_store):
+        if not _rows_ok(t):
+            raise RuntimeError(f"{name}: the last dimension must be contiguous with 16-byte aligned rows")
+
+
+def _run_append(name: str, k_new: torch.Tensor, v_new: torch.Tensor, k_store: torch.Tensor, v_store: torch.Tensor, tables: Sequence[torch.Tensor],
+                capacity: int, k_quantizer: Quantizer, v_quantizer: Quantizer, rope: tuple[torch.Tensor, torch.Tensor] | None, extents: tuple) -> None:
+    """The tail of both append wrappers, after their checks: the rotary tables (`capacity` rows), the quantizers, the library and the
+    call of ``ffq_<name>``. `tables` are the entry point's int32 tensors (lens; lens and the block table), `extents` its arguments
+    between them and the strides."""
+    dt, E = k_new.dtype, k_new.shape[3]
+    cos, sin = _rope_tables(name, rope, dt, capacity, E)
+    params, keep = _quantizer_args(name, k_quantizer, v_quantizer)
+    lib, stream = _base._prepare(k_new, v_new, k_store, v_store, *tables, cos, sin, *keep)
+    entry = _entry(lib, f"ffq_{name}")
+    strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_store), *_strides(v_store))
+    lib.check(
+        entry(
+            _ptr(k_new), _ptr(v_new), _tag(dt), _ptr(k_store), _ptr(v_store), *(_ptr(t) for t in tables), *extents, strides, *params, _ptr(cos),
+            _ptr(sin), 0 if cos is None else cos.shape[0], stream,
+        )
+    )
+    del keep
+    # written through raw pointers: tell the version counters
+    torch.autograd.graph.increment_version(k_store)
+    torch.autograd.graph.increment_version(v_store)
+
+
 def kv_append(
     k_new: torch.Tensor,
     v_new: torch.Tensor,
@@ -116,39 +133,13 @@ def kv_append(
     rotated with the row of its position before it is quantized."""
     if k_new.dim() != 4 or v_new.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise RuntimeError("kv_append: the new rows and the caches are 4-D [B, H, L|S_max, E]")
-    dt = k_new.dtype
-    if dt not in (torch.bfloat16, torch.float16) or v_new.dtype != dt:
-        raise RuntimeError(f"kv_append: the new rows are bf16 or fp16, both the same, got {k_new.dtype} and {v_new.dtype}")
     if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8:
         raise RuntimeError(f"kv_append: the caches hold int8 codes, got {k_cache.dtype}, {v_cache.dtype}")
-    B, HKV, L, E = k_new.shape
-    S_max = k_cache.shape[2]
+    (B, HKV, L, E), S_max = k_new.shape, k_cache.shape[2]
     if tuple(v_new.shape) != (B, HKV, L, E) or tuple(k_cache.shape) != (B, HKV, S_max, E) or tuple(v_cache.shape) != (B, HKV, S_max, E):
         raise RuntimeError(f"kv_append: shapes {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)} do not fit")
-    if E not in (64, 128):
-        raise RuntimeError(f"kv_append: E must be 64 or 128, got {E}")
-    if HKV < 1:
-        raise RuntimeError("kv_append: no kv head")
-    if not _lens_ok(lens, B):
-        raise RuntimeError(f"kv_append: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
-    for t in (k_new, v_new, k_cache, v_cache):
-        if not _rows_ok(t):
-            raise RuntimeError("kv_append: the last dimension must be contiguous with 16-byte aligned rows")
-    cos, sin = _rope_tables("kv_append", rope, dt, S_max, E)
-    params, keep = _quantizer_args("kv_append", k_quantizer, v_quantizer)
-    lib, stream = _base._prepare(k_new, v_new, k_cache, v_cache, lens, cos, sin, *keep)
-    entry = _entry(lib, "ffq_kv_append")
-    strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_cache), *_strides(v_cache))
-    lib.check(
-        entry(
-            _ptr(k_new), _ptr(v_new), _tag(dt), _ptr(k_cache), _ptr(v_cache), _ptr(lens), B, HKV, L, S_max, E, strides, *params, _ptr(cos), _ptr(sin),
-            0 if cos is None else cos.shape[0], stream,
-        )
-    )
-    del keep
-    # written through raw pointers: tell the version counters
-    torch.autograd.graph.increment_version(k_cache)
-    torch.autograd.graph.increment_version(v_cache)
+    _check_new_rows("kv_append", k_new, v_new, k_cache, v_cache, lens)
+    _run_append("kv_append", k_new, v_new, k_cache, v_cache, (lens,), S_max, k_quantizer, v_quantizer, rope, (B, HKV, L, S_max, E))
 
 
 def kv_decode(
@@ -173,50 +164,18 @@ def kv_decode(
         raise RuntimeError("kv_decode: q / k / v are 4-D [B, H, L|S_max, E]")
     if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8 or dequant[1] is None or dequant[2] is None:
         raise RuntimeError(f"kv_decode: k / v are int8 codes with their (scale, offset), got {k_cache.dtype}, {v_cache.dtype}")
-    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
-    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
-        raise RuntimeError(f"kv_decode: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
-    if query.dtype == torch.int8 and dequant[0] is None:
-        raise RuntimeError("kv_decode: int8 q codes need their (scale, offset)")
-    B, H, L, E = query.shape
-    _, HKV, S_max, _ = k_cache.shape
+    S_max = k_cache.shape[2]
+    dt, B, H, L, E, HKV, rows = _check_decode("kv_decode", query, k_cache, v_cache, dequant, dtype, k_cache.shape[1], splits)
     if k_cache.shape[0] != B or k_cache.shape[3] != E or tuple(v_cache.shape) != (B, HKV, S_max, E):
         raise RuntimeError(f"kv_decode: shapes {tuple(query.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)} do not fit")
-    if E not in (64, 128):
-        raise RuntimeError(f"kv_decode: E must be 64 or 128, got {E}")
-    if HKV < 1 or H % HKV:
-        raise RuntimeError(f"kv_decode: {H} query heads are not a multiple of {HKV} kv heads")
-    rows = L * (H // HKV)
-    if rows > MAX_ROWS:
-        raise RuntimeError(f"kv_decode: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
     if min(B, L, S_max) < 1:
         raise RuntimeError(f"kv_decode: empty operands {tuple(query.shape)}, {tuple(k_cache.shape)}")
     if not _lens_ok(lens, B):
         raise RuntimeError(f"kv_decode: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
-    if not 0 <= splits <= MAX_SPLITS:
-        raise RuntimeError(f"kv_decode: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
     if plan_len is not None and not 1 <= plan_len <= S_max:
         raise RuntimeError(f"kv_decode: plan_len is a key count in 1..{S_max}, got {plan_len}")
-    for t in (query, k_cache, v_cache):
-        if not _rows_ok(t):
-            raise RuntimeError("kv_decode: the last dimension must be contiguous with 16-byte aligned rows")
-    deq_s, deq_o, out_s, out_o, bits, keep = _decode_tables(dequant, output_quantizer)
-    lib, stream = _base._prepare(query, k_cache, v_cache, lens, *keep)
-    entry = _entry(lib, "ffq_kv_decode")
-    count = splits or int(_entry(lib, "ffq_sdpa_decode_splits")(B, HKV, plan_len or S_max, rows, E))
-    nbytes = int(_entry(lib, "ffq_sdpa_decode_workspace_bytes")(B, HKV, rows, E, count))
-    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
-    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(k_cache), *_strides(v_cache))
-    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
-    lib.check(
-        entry(
-            _ptr(query), _tag(query.dtype), _ptr(k_cache), _ptr(v_cache), _tag(dt), deq_s, deq_o, _ptr(lens), B, H, HKV, L, S_max, E, strides,
-            int(bool(is_causal)), sqrt_scale, _ptr(out_s), _ptr(out_o), bits, splits, plan_len or 0, _ptr(out), _ptr(workspace), nbytes, stream,
-        )
-    )
-    del keep
-    return out
+    return _run_decode("ffq_kv_decode", query, k_cache, v_cache, (lens,), dt, (B, H, HKV, L, E, rows), plan_len or S_max, splits, scale, dequant,
+                       output_quantizer, (_ptr(lens), B, H, HKV, L, S_max, E), (int(bool(is_causal)),), (splits, plan_len or 0))
 
 
 def kv_paged_append(
@@ -238,37 +197,14 @@ def kv_paged_append(
     name = "kv_paged_append"
     if k_new.dim() != 4 or v_new.dim() != 4:
         raise RuntimeError(f"{name}: the new rows are 4-D [B, H, L, E]")
-    dt = k_new.dtype
-    if dt not in (torch.bfloat16, torch.float16) or v_new.dtype != dt:
-        raise RuntimeError(f"{name}: the new rows are bf16 or fp16, both the same, got {k_new.dtype} and {v_new.dtype}")
     B, HKV, L, E = k_new.shape
     if tuple(v_new.shape) != (B, HKV, L, E):
         raise RuntimeError(f"{name}: shapes {tuple(k_new.shape)}, {tuple(v_new.shape)} do not fit")
-    if E not in (64, 128):
-        raise RuntimeError(f"{name}: E must be 64 or 128, got {E}")
-    if HKV < 1:
-        raise RuntimeError(f"{name}: no kv head")
     num_pages, P, max_pages = _pools_ok(name, k_pool, v_pool, block_table, B, HKV, E)
-    if not _lens_ok(lens, B):
-        raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
-    for t in (k_new, v_new, k_pool, v_pool):
-        if not _rows_ok(t):
-            raise RuntimeError(f"{name}: the last dimension must be contiguous with 16-byte aligned rows")
-    cos, sin = _rope_tables(name, rope, dt, max_pages * P, E)
-    params, keep = _quantizer_args(name, k_quantizer, v_quantizer)
-    lib, stream = _base._prepare(k_new, v_new, k_pool, v_pool, lens, block_table, cos, sin, *keep)
-    entry = _entry(lib, "ffq_kv_paged_append")
-    strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_pool), *_strides(v_pool))
-    lib.check(
-        entry(
-            _ptr(k_new), _ptr(v_new), _tag(dt), _ptr(k_pool), _ptr(v_pool), _ptr(lens), _ptr(block_table), B, HKV, L, num_pages, P, max_pages,
-            block_table.stride(0) if B > 1 else max_pages, E, strides, *params, _ptr(cos), _ptr(sin), 0 if cos is None else cos.shape[0], stream,
-        )
-    )
-    del keep
-    # written through raw pointers: tell the version counters
-    torch.autograd.graph.increment_version(k_pool)
-    torch.autograd.graph.increment_version(v_pool)
+    _check_new_rows(name, k_new, v_new, k_pool, v_pool, lens)
+    table_stride = block_table.stride(0) if B > 1 else max_pages
+    _run_append(name, k_new, v_new, k_pool, v_pool, (lens, block_table), max_pages * P, k_quantizer, v_quantizer, rope,
+                (B, HKV, L, num_pages, P, max_pages, table_stride, E))
 
 
 def kv_paged_decode(
@@ -294,48 +230,16 @@ def kv_paged_decode(
         raise RuntimeError(f"{name}: q is 4-D [B, H, L, E]")
     if dequant[1] is None or dequant[2] is None:
         raise RuntimeError(f"{name}: k / v are int8 codes with their (scale, offset)")
-    dt = dtype or (query.dtype if query.dtype != torch.int8 else None)
-    if dt not in (torch.bfloat16, torch.float16) or query.dtype not in (dt, torch.int8):
-        raise RuntimeError(f"{name}: the data dtype is bf16 or fp16 and q is held in it or in int8, got {dt} and {query.dtype}")
-    if query.dtype == torch.int8 and dequant[0] is None:
-        raise RuntimeError(f"{name}: int8 q codes need their (scale, offset)")
-    B, H, L, E = query.shape
-    if E not in (64, 128):
-        raise RuntimeError(f"{name}: E must be 64 or 128, got {E}")
-    HKV = k_pool.shape[1] if k_pool.dim() == 4 else 0
-    if HKV < 1 or H % HKV:
-        raise RuntimeError(f"{name}: {H} query heads are not a multiple of {HKV} kv heads")
+    dt, B, H, L, E, HKV, rows = _check_decode(name, query, k_pool, v_pool, dequant, dtype, k_pool.shape[1] if k_pool.dim() == 4 else 0, splits)
     if min(B, L) < 1:
         raise RuntimeError(f"{name}: empty operands {tuple(query.shape)}")
     num_pages, P, max_pages = _pools_ok(name, k_pool, v_pool, block_table, B, HKV, E)
     C = max_pages * P
-    rows = L * (H // HKV)
-    if rows > MAX_ROWS:
-        raise RuntimeError(f"{name}: L * (H_q / H) = {rows} query rows per kv head, at most {MAX_ROWS}")
     if not _lens_ok(lens, B):
         raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
-    if not 0 <= splits <= MAX_SPLITS:
-        raise RuntimeError(f"{name}: splits is 0 (the rule) or 1..{MAX_SPLITS}, got {splits}")
     if plan_len is not None and not 1 <= plan_len <= C:
         raise RuntimeError(f"{name}: plan_len is a key count in 1..{C}, got {plan_len}")
-    for t in (query, k_pool, v_pool):
-        if not _rows_ok(t):
-            raise RuntimeError(f"{name}: the last dimension must be contiguous with 16-byte aligned rows")
-    deq_s, deq_o, out_s, out_o, bits, keep = _decode_tables(dequant, output_quantizer)
-    lib, stream = _base._prepare(query, k_pool, v_pool, lens, block_table, *keep)
-    entry = _entry(lib, "ffq_kv_paged_decode")
-    count = splits or sdpa_decode_plan(B, HKV, plan_len or C, rows, E)
-    nbytes = sdpa_decode_workspace_bytes(B, HKV, rows, E, count)
-    out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
-    workspace = _base._workspace(nbytes, query.device)
-    strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(k_pool), *_strides(v_pool))
-    sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
-    lib.check(
-        entry(
-            _ptr(query), _tag(query.dtype), _ptr(k_pool), _ptr(v_pool), _tag(dt), deq_s, deq_o, _ptr(lens), _ptr(block_table), B, H, HKV, L, num_pages,
-            P, max_pages, block_table.stride(0) if B > 1 else max_pages, E, strides, int(bool(is_causal)), sqrt_scale, _ptr(out_s), _ptr(out_o), bits,
-            splits, plan_len or 0, _ptr(out), _ptr(workspace), nbytes, stream,
-        )
-    )
-    del keep
-    return out
+    table_stride = block_table.stride(0) if B > 1 else max_pages
+    return _run_decode("ffq_kv_paged_decode", query, k_pool, v_pool, (lens, block_table), dt, (B, H, HKV, L, E, rows), plan_len or C, splits, scale,
+                       dequant, output_quantizer, (_ptr(lens), _ptr(block_table), B, H, HKV, L, num_pages, P, max_pages, table_stride, E),
+                       (int(bool(is_causal)),), (splits, plan_len or 0))

@@ -272,8 +272,38 @@ def test_the_wrappers_say_not_covered_on_a_library_without_the_symbols(oracle_ba
         ops.kv_decode(q, kc, vc, lens, dequant=(None, kq[:2], vq[:2]))
 
 
-def test_the_wrappers_check_their_operands_and_refuse_host_tensors():
+def wrapper_refusals():
+    """The calls ``ops.kv_append`` / ``ops.kv_decode`` refuse on host tensors, ahead of any library call
+    (tests/golden/gen_decode_refusals.py records their texts from the same list)."""
     bf = torch.bfloat16
+    k_new, v_new, kc, vc, lens, q = _operands()
+    kq, vq = cases.params((8, 0.5, 0.0), "cpu"), cases.params((4, 0.5, 1.0), "cpu")
+    one = (torch.ones(1), None)
+    table = torch.zeros(20, 64, dtype=bf)
+    return [lambda: ops.kv_append(k_new[0], v_new, kc, vc, lens, kq, vq), lambda: ops.kv_append(k_new.float(), v_new.float(), kc, vc, lens, kq, vq),
+            lambda: ops.kv_append(k_new, v_new.half(), kc, vc, lens, kq, vq), lambda: ops.kv_append(k_new, v_new, kc.to(bf), vc, lens, kq, vq),
+            lambda: ops.kv_append(k_new, v_new[:, :1], kc, vc, lens, kq, vq), lambda: ops.kv_append(k_new, v_new, kc, vc[:, :, :19], lens, kq, vq),
+            lambda: ops.kv_append(k_new[..., :32], v_new[..., :32], kc[..., :32], vc[..., :32], lens, kq, vq),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, lens.long(), kq, vq), lambda: ops.kv_append(k_new, v_new, kc, vc, lens[:1], kq, vq),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, torch.zeros(4, dtype=torch.int32)[::2], kq, vq),
+            lambda: ops.kv_append(k_new.transpose(2, 3).contiguous().transpose(2, 3), v_new, kc, vc, lens, kq, vq),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, lens, (kq[0], kq[1], 9.0), vq), lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, (vq[0], vq[1], 1.0)),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, lens, (None, kq[1], 8.0), vq), lambda: ops.kv_append(k_new, v_new, kc, vc, lens, (torch.ones(2), None, 8.0), vq),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq, rope=(table[:19], table[:19])),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq, rope=(table, table.half())),
+            lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq, rope=(table, torch.zeros(21, 64, dtype=bf))),
+            lambda: ops.kv_decode(q, kc, vc, lens), lambda: ops.kv_decode(q, kc.to(bf), vc, lens, dequant=(None, one, one)),
+            lambda: ops.kv_decode(q[0], kc, vc, lens, dequant=(None, one, one)), lambda: ops.kv_decode(q.float(), kc, vc, lens, dequant=(None, one, one)),
+            lambda: ops.kv_decode(q.to(torch.int8), kc, vc, lens, dequant=(None, one, one), dtype=bf),
+            lambda: ops.kv_decode(torch.zeros(2, 2, 33, 64, dtype=bf), kc, vc, lens, dequant=(None, one, one)),
+            lambda: ops.kv_decode(torch.zeros(2, 3, 1, 64, dtype=bf), kc, vc, lens, dequant=(None, one, one)),
+            lambda: ops.kv_decode(q, kc, vc[:, :, :4], lens, dequant=(None, one, one)), lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), splits=65),
+            lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), splits=-1), lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), plan_len=0),
+            lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), plan_len=21), lambda: ops.kv_decode(q, kc, vc, lens.long(), dequant=(None, one, one)),
+            lambda: ops.kv_decode(q, kc, vc, lens[:1], dequant=(None, one, one))]
+
+
+def test_the_wrappers_check_their_operands_and_refuse_host_tensors():
     k_new, v_new, kc, vc, lens, q = _operands()
     kq, vq = cases.params((8, 0.5, 0.0), "cpu"), cases.params((4, 0.5, 1.0), "cpu")
     one = (torch.ones(1), None)
@@ -281,66 +311,56 @@ def test_the_wrappers_check_their_operands_and_refuse_host_tensors():
         ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq)
     with pytest.raises(BackendError, match="HIP device only"):
         ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one))
-    table = torch.zeros(20, 64, dtype=bf)
-    for call in (lambda: ops.kv_append(k_new[0], v_new, kc, vc, lens, kq, vq), lambda: ops.kv_append(k_new.float(), v_new.float(), kc, vc, lens, kq, vq),
-                 lambda: ops.kv_append(k_new, v_new.half(), kc, vc, lens, kq, vq), lambda: ops.kv_append(k_new, v_new, kc.to(bf), vc, lens, kq, vq),
-                 lambda: ops.kv_append(k_new, v_new[:, :1], kc, vc, lens, kq, vq), lambda: ops.kv_append(k_new, v_new, kc, vc[:, :, :19], lens, kq, vq),
-                 lambda: ops.kv_append(k_new[..., :32], v_new[..., :32], kc[..., :32], vc[..., :32], lens, kq, vq),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, lens.long(), kq, vq), lambda: ops.kv_append(k_new, v_new, kc, vc, lens[:1], kq, vq),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, torch.zeros(4, dtype=torch.int32)[::2], kq, vq),
-                 lambda: ops.kv_append(k_new.transpose(2, 3).contiguous().transpose(2, 3), v_new, kc, vc, lens, kq, vq),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, lens, (kq[0], kq[1], 9.0), vq), lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, (vq[0], vq[1], 1.0)),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, lens, (None, kq[1], 8.0), vq), lambda: ops.kv_append(k_new, v_new, kc, vc, lens, (torch.ones(2), None, 8.0), vq),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq, rope=(table[:19], table[:19])),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq, rope=(table, table.half())),
-                 lambda: ops.kv_append(k_new, v_new, kc, vc, lens, kq, vq, rope=(table, torch.zeros(21, 64, dtype=bf))),
-                 lambda: ops.kv_decode(q, kc, vc, lens), lambda: ops.kv_decode(q, kc.to(bf), vc, lens, dequant=(None, one, one)),
-                 lambda: ops.kv_decode(q[0], kc, vc, lens, dequant=(None, one, one)), lambda: ops.kv_decode(q.float(), kc, vc, lens, dequant=(None, one, one)),
-                 lambda: ops.kv_decode(q.to(torch.int8), kc, vc, lens, dequant=(None, one, one), dtype=bf),
-                 lambda: ops.kv_decode(torch.zeros(2, 2, 33, 64, dtype=bf), kc, vc, lens, dequant=(None, one, one)),
-                 lambda: ops.kv_decode(torch.zeros(2, 3, 1, 64, dtype=bf), kc, vc, lens, dequant=(None, one, one)),
-                 lambda: ops.kv_decode(q, kc, vc[:, :, :4], lens, dequant=(None, one, one)), lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), splits=65),
-                 lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), splits=-1), lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), plan_len=0),
-                 lambda: ops.kv_decode(q, kc, vc, lens, dequant=(None, one, one), plan_len=21), lambda: ops.kv_decode(q, kc, vc, lens.long(), dequant=(None, one, one)),
-                 lambda: ops.kv_decode(q, kc, vc, lens[:1], dequant=(None, one, one))):
+    for call in wrapper_refusals():
         with pytest.raises(RuntimeError):
             call()
 
 
 # ---- the class ------------------------------------------------------------------------------------------------------------------------------
-def test_the_constructor_refuses_what_the_kernels_do_not_reproduce():
+def _estimating(build, quantizer):
+    """`build` while a range estimator is installed on `quantizer`."""
+    def call():
+        with ff.estimate_ranges(quantizer, ff.range_setting.running_minmax):
+            build()
+    return call
+
+
+def class_refusals():
+    """(a sound cache, its keyword arguments, [(call, the words its ValueError must hold or None)]): what the constructor, ``append``
+    and ``attend`` of ``QuantizedKVCache`` refuse (tests/golden/gen_decode_refusals.py records the texts from the same list)."""
     good = cases.quantizer((8, 0.5, 3.0))
     ok = dict(batch=2, kv_heads=2, max_len=16, head_dim=64, key_quantizer=good, value_quantizer=cases.quantizer((4, 0.25, -1.0)), dtype=torch.bfloat16, device="cpu")
     cache = ff.nn.QuantizedKVCache(**ok)
-    assert cache.k_cache.shape == cache.v_cache.shape == (2, 2, 16, 64) and cache.k_cache.dtype == torch.int8 and cache.k_cache.is_contiguous()
-    assert cache.lengths.dtype == torch.int32 and cache.lengths.tolist() == [0, 0]
-    other = ff.nn.QuantizedKVCache(**{**ok, "layout": "bshe", "dtype": torch.float16})
-    assert other.k_cache.shape == (2, 2, 16, 64) and other.k_cache.transpose(1, 2).is_contiguous() and other.k_cache.stride(2) == 2 * 64
     per_channel = ff.nn.LinearQuantizer(8, granularity=ff.PerChannel(1), quantized_dtype=torch.int8)
     per_channel.quantization_range = (torch.full((2,), -1.0), torch.full((2,), 1.0))
     estimating = cases.quantizer((8, 0.5, 3.0))
     bad_quantizers = [ff.nn.LinearQuantizer(8, quantized_dtype=torch.int8), per_channel, cases.quantizer((16, 0.5, 0.0)), cases.quantizer((8, 0.5, 0.0), container=None),
                       cases.quantizer((8, 0.5, 0.0), container=torch.bfloat16), cases.quantizer((1, 0.5, 0.0)), ff.nn.QuantizerStub(), None,
                       ff.nn.DynamicLinearQuantizer(8)]
-    for q in bad_quantizers:  # not initialised; per channel; 16 bits; codes held in the data dtype; 1 bit; not a LinearQuantizer
-        for slot in ("key_quantizer", "value_quantizer"):
-            with pytest.raises(ValueError, match="quantizer"):
-                ff.nn.QuantizedKVCache(**{**ok, slot: q})
-    with ff.estimate_ranges(estimating, ff.range_setting.running_minmax):  # not static while a range estimator is installed
-        with pytest.raises(ValueError, match="quantizer"):
-            ff.nn.QuantizedKVCache(**{**ok, "key_quantizer": estimating})
-    for change in (dict(layout="sbhe"), dict(dtype=torch.float32), dict(head_dim=96), dict(batch=0), dict(max_len=0), dict(kv_heads=0)):
-        with pytest.raises(ValueError):
-            ff.nn.QuantizedKVCache(**{**ok, **change})
+    build = lambda **change: lambda: ff.nn.QuantizedKVCache(**{**ok, **change})  # noqa: E731
+    # not initialised; per channel; 16 bits; codes held in the data dtype; 1 bit; not a LinearQuantizer
+    refused = [(build(**{slot: q}), "quantizer") for q in bad_quantizers for slot in ("key_quantizer", "value_quantizer")]
+    refused.append((_estimating(build(key_quantizer=estimating), estimating), "quantizer"))  # not static while a range estimator is installed
+    refused += [(build(**change), None)
+                for change in (dict(layout="sbhe"), dict(dtype=torch.float32), dict(head_dim=96), dict(batch=0), dict(max_len=0), dict(kv_heads=0))]
     k = torch.zeros(2, 2, 3, 64, dtype=torch.bfloat16)
-    for key, value in ((k.half(), k.half()), (k[:1], k[:1]), (k, k[:, :, :2]), (k[..., :32], k[..., :32]), (k[0], k[0])):
-        with pytest.raises(ValueError):
-            cache.append(key, value)
+    refused += [(lambda key=key, value=value: cache.append(key, value), None)
+                for key, value in ((k.half(), k.half()), (k[:1], k[:1]), (k, k[:, :, :2]), (k[..., :32], k[..., :32]), (k[0], k[0]))]
     q = torch.zeros(2, 4, 1, 64, dtype=torch.bfloat16)
-    with pytest.raises(ValueError):
-        cache.attend(q.half())
-    with pytest.raises(ValueError, match="output quantizer"):
-        cache.attend(q, output_quantizer=cases.quantizer((16, 0.5, 0.0), container=None))
+    refused.append((lambda: cache.attend(q.half()), None))
+    refused.append((lambda: cache.attend(q, output_quantizer=cases.quantizer((16, 0.5, 0.0), container=None)), "output quantizer"))
+    return cache, ok, refused
+
+
+def test_the_constructor_refuses_what_the_kernels_do_not_reproduce():
+    cache, ok, refused = class_refusals()
+    assert cache.k_cache.shape == cache.v_cache.shape == (2, 2, 16, 64) and cache.k_cache.dtype == torch.int8 and cache.k_cache.is_contiguous()
+    assert cache.lengths.dtype == torch.int32 and cache.lengths.tolist() == [0, 0]
+    other = ff.nn.QuantizedKVCache(**{**ok, "layout": "bshe", "dtype": torch.float16})
+    assert other.k_cache.shape == (2, 2, 16, 64) and other.k_cache.transpose(1, 2).is_contiguous() and other.k_cache.stride(2) == 2 * 64
+    for call, words in refused:
+        with pytest.raises(ValueError, match=words):
+            call()
     assert cache.lengths.tolist() == [0, 0]  # (a refused call moved nothing)
 
 

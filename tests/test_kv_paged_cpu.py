@@ -302,17 +302,13 @@ def test_the_wrappers_say_not_covered_on_a_library_without_the_symbols(oracle_ba
         ops.kv_paged_decode(q, kp, vp, lens, table, dequant=(None, kq[:2], vq[:2]))
 
 
-def test_the_wrappers_check_their_operands_and_refuse_host_tensors():
+def wrapper_refusals():
+    """The calls ``ops.kv_paged_append`` / ``ops.kv_paged_decode`` refuse on host tensors, ahead of any library call
+    (tests/golden/gen_decode_refusals.py records their texts from the same list)."""
     bf = torch.bfloat16
     k_new, v_new, kp, vp, lens, table, q = _operands()
     kq, vq = cases.params((8, 0.5, 0.0), "cpu"), cases.params((4, 0.5, 1.0), "cpu")
     one = (torch.ones(1), None)
-    with pytest.raises(BackendError, match="HIP device only"):
-        ops.kv_paged_append(k_new, v_new, kp, vp, lens, table, kq, vq)
-    with pytest.raises(BackendError, match="HIP device only"):
-        ops.kv_paged_decode(q, kp, vp, lens, table, dequant=(None, one, one))
-    with pytest.raises(BackendError, match="HIP device only"):  # both layouts and a table that is a window of a wider one pass the checks
-        ops.kv_paged_decode(q, kp.transpose(1, 2).contiguous().transpose(1, 2), vp, lens, torch.zeros(2, 5, dtype=torch.int32)[:, 1:3], dequant=(None, one, one))
     rope = torch.zeros(32, 64, dtype=bf)
 
     def append(**change):
@@ -323,24 +319,37 @@ def test_the_wrappers_check_their_operands_and_refuse_host_tensors():
         a = dict(query=q, k_pool=kp, v_pool=vp, lens=lens, block_table=table, dequant=(None, one, one))
         return lambda: ops.kv_paged_decode(**{**a, **change})
 
-    for call in (append(k_new=k_new[0]), append(k_new=k_new.float(), v_new=v_new.float()), append(v_new=v_new.half()), append(k_pool=kp.to(bf)),
-                 append(v_new=v_new[:, :1]), append(v_pool=vp[:, :, :8]), append(k_pool=kp[:, :1]), append(k_pool=kp[0]),
-                 append(k_new=k_new[..., :32], v_new=v_new[..., :32], k_pool=kp[..., :32], v_pool=vp[..., :32]),
-                 append(k_pool=torch.zeros(6, 2, 24, 64, dtype=torch.int8), v_pool=torch.zeros(6, 2, 24, 64, dtype=torch.int8)),      # P = 24
-                 append(k_pool=torch.zeros(6, 2, 8, 64, dtype=torch.int8), v_pool=torch.zeros(6, 2, 8, 64, dtype=torch.int8)),        # P = 8
-                 append(lens=lens.long()), append(lens=lens[:1]), append(lens=torch.zeros(4, dtype=torch.int32)[::2]),
-                 append(block_table=table.long()), append(block_table=table[:1]), append(block_table=table[0]),
-                 append(block_table=torch.zeros(2, 4, dtype=torch.int32)[:, ::2]), append(block_table=torch.zeros(2, 0, dtype=torch.int32)),
-                 append(block_table=torch.zeros(1, 2, dtype=torch.int32).expand(2, 2)),
-                 append(k_new=k_new.transpose(2, 3).contiguous().transpose(2, 3)),
-                 append(k_quantizer=(kq[0], kq[1], 9.0)), append(v_quantizer=(vq[0], vq[1], 1.0)), append(k_quantizer=(None, kq[1], 8.0)),
-                 append(k_quantizer=(torch.ones(2), None, 8.0)),
-                 append(rope=(rope[:31], rope[:31])), append(rope=(rope, rope.half())), append(rope=(rope, torch.zeros(33, 64, dtype=bf))),
-                 attend(dequant=(None, None, None)), attend(k_pool=kp.to(bf)), attend(query=q[0]), attend(query=q.float()),
-                 attend(query=q.to(torch.int8), dtype=bf), attend(query=torch.zeros(2, 2, 33, 64, dtype=bf)), attend(query=torch.zeros(2, 3, 1, 64, dtype=bf)),
-                 attend(v_pool=vp[:, :, :8]), attend(v_pool=vp[:5]), attend(splits=65), attend(splits=-1), attend(plan_len=0), attend(plan_len=33),
-                 attend(lens=lens.long()), attend(lens=lens[:1]), attend(block_table=table.long()), attend(block_table=table[:1]),
-                 attend(block_table=torch.zeros(2, 4, dtype=torch.int32)[:, ::2])):
+    return [append(k_new=k_new[0]), append(k_new=k_new.float(), v_new=v_new.float()), append(v_new=v_new.half()), append(k_pool=kp.to(bf)),
+            append(v_new=v_new[:, :1]), append(v_pool=vp[:, :, :8]), append(k_pool=kp[:, :1]), append(k_pool=kp[0]),
+            append(k_new=k_new[..., :32], v_new=v_new[..., :32], k_pool=kp[..., :32], v_pool=vp[..., :32]),
+            append(k_pool=torch.zeros(6, 2, 24, 64, dtype=torch.int8), v_pool=torch.zeros(6, 2, 24, 64, dtype=torch.int8)),      # P = 24
+            append(k_pool=torch.zeros(6, 2, 8, 64, dtype=torch.int8), v_pool=torch.zeros(6, 2, 8, 64, dtype=torch.int8)),        # P = 8
+            append(lens=lens.long()), append(lens=lens[:1]), append(lens=torch.zeros(4, dtype=torch.int32)[::2]),
+            append(block_table=table.long()), append(block_table=table[:1]), append(block_table=table[0]),
+            append(block_table=torch.zeros(2, 4, dtype=torch.int32)[:, ::2]), append(block_table=torch.zeros(2, 0, dtype=torch.int32)),
+            append(block_table=torch.zeros(1, 2, dtype=torch.int32).expand(2, 2)),
+            append(k_new=k_new.transpose(2, 3).contiguous().transpose(2, 3)),
+            append(k_quantizer=(kq[0], kq[1], 9.0)), append(v_quantizer=(vq[0], vq[1], 1.0)), append(k_quantizer=(None, kq[1], 8.0)),
+            append(k_quantizer=(torch.ones(2), None, 8.0)),
+            append(rope=(rope[:31], rope[:31])), append(rope=(rope, rope.half())), append(rope=(rope, torch.zeros(33, 64, dtype=bf))),
+            attend(dequant=(None, None, None)), attend(k_pool=kp.to(bf)), attend(query=q[0]), attend(query=q.float()),
+            attend(query=q.to(torch.int8), dtype=bf), attend(query=torch.zeros(2, 2, 33, 64, dtype=bf)), attend(query=torch.zeros(2, 3, 1, 64, dtype=bf)),
+            attend(v_pool=vp[:, :, :8]), attend(v_pool=vp[:5]), attend(splits=65), attend(splits=-1), attend(plan_len=0), attend(plan_len=33),
+            attend(lens=lens.long()), attend(lens=lens[:1]), attend(block_table=table.long()), attend(block_table=table[:1]),
+            attend(block_table=torch.zeros(2, 4, dtype=torch.int32)[:, ::2])]
+
+
+def test_the_wrappers_check_their_operands_and_refuse_host_tensors():
+    k_new, v_new, kp, vp, lens, table, q = _operands()
+    kq, vq = cases.params((8, 0.5, 0.0), "cpu"), cases.params((4, 0.5, 1.0), "cpu")
+    one = (torch.ones(1), None)
+    with pytest.raises(BackendError, match="HIP device only"):
+        ops.kv_paged_append(k_new, v_new, kp, vp, lens, table, kq, vq)
+    with pytest.raises(BackendError, match="HIP device only"):
+        ops.kv_paged_decode(q, kp, vp, lens, table, dequant=(None, one, one))
+    with pytest.raises(BackendError, match="HIP device only"):  # both layouts and a table that is a window of a wider one pass the checks
+        ops.kv_paged_decode(q, kp.transpose(1, 2).contiguous().transpose(1, 2), vp, lens, torch.zeros(2, 5, dtype=torch.int32)[:, 1:3], dequant=(None, one, one))
+    for call in wrapper_refusals():
         with pytest.raises(RuntimeError):
             call()
 
@@ -352,35 +361,41 @@ def make(dtype=torch.bfloat16, layout="phse", **change):
     return ff.nn.PagedQuantizedKVCache(**{**kw, **change})
 
 
-def test_the_constructor_refuses_what_the_kernels_do_not_reproduce():
+def class_refusals():
+    """(a sound cache, [(call, the words its ValueError must hold or None)]): what the constructor, ``append`` and ``attend`` of
+    ``PagedQuantizedKVCache`` refuse (tests/golden/gen_decode_refusals.py records the texts from the same list)."""
     cache = make()
-    assert cache.k_pool.shape == cache.v_pool.shape == (10, 2, 16, 64) and cache.k_pool.dtype == torch.int8 and cache.k_pool.is_contiguous()
-    assert cache.block_table.dtype == torch.int32 and cache.block_table.tolist() == [[-1] * 4] * 3
-    assert cache.lengths.dtype == torch.int32 and cache.lengths.tolist() == [0, 0, 0] and cache.capacity == 64 and cache.free_pages == 10
-    other = make(torch.float16, "pshe")
-    assert other.k_pool.shape == (10, 2, 16, 64) and other.k_pool.transpose(1, 2).is_contiguous() and other.k_pool.stride(2) == 2 * 64
     per_channel = ff.nn.LinearQuantizer(8, granularity=ff.PerChannel(1), quantized_dtype=torch.int8)
     per_channel.quantization_range = (torch.full((2,), -1.0), torch.full((2,), 1.0))
     bad_quantizers = [ff.nn.LinearQuantizer(8, quantized_dtype=torch.int8), per_channel, cases.quantizer((16, 0.5, 0.0)), cases.quantizer((8, 0.5, 0.0), container=None),
                       cases.quantizer((8, 0.5, 0.0), container=torch.bfloat16), cases.quantizer((1, 0.5, 0.0)), ff.nn.QuantizerStub(), None,
                       ff.nn.DynamicLinearQuantizer(8)]
-    for q in bad_quantizers:  # the rules of QuantizedKVCache: _quantizer_params
-        for slot in ("key_quantizer", "value_quantizer"):
-            with pytest.raises(ValueError, match="quantizer"):
-                make(**{slot: q})
-    for change in (dict(layout="bhse"), dict(dtype=torch.float32), dict(head_dim=96), dict(batch=0), dict(num_pages=0), dict(kv_heads=0), dict(max_pages_per_seq=0),
-                   dict(page_size=8), dict(page_size=24), dict(page_size=512), dict(page_size=256, max_pages_per_seq=1 << 22)):
-        with pytest.raises(ValueError):
-            make(**change)
+    build = lambda **change: lambda: make(**change)  # noqa: E731
+    # the rules of QuantizedKVCache: _quantizer_params
+    refused = [(build(**{slot: q}), "quantizer") for q in bad_quantizers for slot in ("key_quantizer", "value_quantizer")]
+    refused += [(build(**change), None)
+                for change in (dict(layout="bhse"), dict(dtype=torch.float32), dict(head_dim=96), dict(batch=0), dict(num_pages=0), dict(kv_heads=0),
+                               dict(max_pages_per_seq=0), dict(page_size=8), dict(page_size=24), dict(page_size=512),
+                               dict(page_size=256, max_pages_per_seq=1 << 22))]
     k = torch.zeros(3, 2, 3, 64, dtype=torch.bfloat16)
-    for key, value in ((k.half(), k.half()), (k[:1], k[:1]), (k, k[:, :, :2]), (k[..., :32], k[..., :32]), (k[0], k[0])):
-        with pytest.raises(ValueError):
-            cache.append(key, value)
+    refused += [(lambda key=key, value=value: cache.append(key, value), None)
+                for key, value in ((k.half(), k.half()), (k[:1], k[:1]), (k, k[:, :, :2]), (k[..., :32], k[..., :32]), (k[0], k[0]))]
     q = torch.zeros(3, 4, 1, 64, dtype=torch.bfloat16)
-    with pytest.raises(ValueError):
-        cache.attend(q.half())
-    with pytest.raises(ValueError, match="output quantizer"):
-        cache.attend(q, output_quantizer=cases.quantizer((16, 0.5, 0.0), container=None))
+    refused.append((lambda: cache.attend(q.half()), None))
+    refused.append((lambda: cache.attend(q, output_quantizer=cases.quantizer((16, 0.5, 0.0), container=None)), "output quantizer"))
+    return cache, refused
+
+
+def test_the_constructor_refuses_what_the_kernels_do_not_reproduce():
+    cache, refused = class_refusals()
+    assert cache.k_pool.shape == cache.v_pool.shape == (10, 2, 16, 64) and cache.k_pool.dtype == torch.int8 and cache.k_pool.is_contiguous()
+    assert cache.block_table.dtype == torch.int32 and cache.block_table.tolist() == [[-1] * 4] * 3
+    assert cache.lengths.dtype == torch.int32 and cache.lengths.tolist() == [0, 0, 0] and cache.capacity == 64 and cache.free_pages == 10
+    other = make(torch.float16, "pshe")
+    assert other.k_pool.shape == (10, 2, 16, 64) and other.k_pool.transpose(1, 2).is_contiguous() and other.k_pool.stride(2) == 2 * 64
+    for call, words in refused:
+        with pytest.raises(ValueError, match=words):
+            call()
     assert cache.lengths.tolist() == [0, 0, 0]  # (a refused call moved nothing)
 
 

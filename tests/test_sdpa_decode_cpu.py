@@ -198,24 +198,38 @@ def test_the_wrapper_says_not_covered_on_a_library_without_the_symbol(oracle_bac
         ops.sdpa_decode(q, k, k, dequant=(None, one, one))
 
 
-def test_the_wrapper_checks_its_operands_and_refuses_host_tensors():
+def wrapper_refusals():
+    """The calls ``ops.sdpa_decode`` refuses on host tensors, ahead of any library call (tests/golden/gen_decode_refusals.py records
+    their texts from the same list)."""
     bf = torch.bfloat16
     q, k = torch.zeros(1, 2, 1, 64, dtype=bf), torch.zeros(1, 2, 5, 64, dtype=torch.int8)
     one = (torch.ones(1), None)
+    return [lambda: ops.sdpa_decode(q, k, k), lambda: ops.sdpa_decode(q, k.to(bf), k, dequant=(None, one, one)), lambda: ops.sdpa_decode(q[0], k, k, dequant=(None, one, one)),
+            lambda: ops.sdpa_decode(q.float(), k, k, dequant=(None, one, one)), lambda: ops.sdpa_decode(q.to(torch.int8), k, k, dequant=(None, one, one), dtype=bf),
+            lambda: ops.sdpa_decode(torch.zeros(1, 2, 17, 64, dtype=bf), k, k, dequant=(None, one, one), splits=65),
+            lambda: ops.sdpa_decode(torch.zeros(1, 2, 33, 64, dtype=bf), k, k, dequant=(None, one, one)),
+            lambda: ops.sdpa_decode(torch.zeros(1, 3, 1, 64, dtype=bf), k, k, dequant=(None, one, one)),
+            lambda: ops.sdpa_decode(q, k, k[:, :, :4], dequant=(None, one, one)), lambda: ops.sdpa_decode(q, k, k, dequant=(None, one, one), splits=-1),
+            lambda: ops.sdpa_decode(q, k, k, dequant=(None, one, one), attn_mask=torch.zeros(1, 4)),
+            lambda: ops.sdpa_decode(q, k, k, dequant=(None, one, one), attn_mask=torch.zeros(1, 5, dtype=torch.int32))]
+
+
+def causal_with_a_mask():
+    q, k = torch.zeros(1, 2, 1, 64, dtype=torch.bfloat16), torch.zeros(1, 2, 5, 64, dtype=torch.int8)
+    one = (torch.ones(1), None)
+    return ops.sdpa_decode(q, k, k, dequant=(None, one, one), attn_mask=torch.zeros(1, 5), is_causal=True)
+
+
+def test_the_wrapper_checks_its_operands_and_refuses_host_tensors():
+    q, k = torch.zeros(1, 2, 1, 64, dtype=torch.bfloat16), torch.zeros(1, 2, 5, 64, dtype=torch.int8)
+    one = (torch.ones(1), None)
     with pytest.raises(BackendError, match="HIP device only"):
         ops.sdpa_decode(q, k, k, dequant=(None, one, one))
-    for call in (lambda: ops.sdpa_decode(q, k, k), lambda: ops.sdpa_decode(q, k.to(bf), k, dequant=(None, one, one)), lambda: ops.sdpa_decode(q[0], k, k, dequant=(None, one, one)),
-                 lambda: ops.sdpa_decode(q.float(), k, k, dequant=(None, one, one)), lambda: ops.sdpa_decode(q.to(torch.int8), k, k, dequant=(None, one, one), dtype=bf),
-                 lambda: ops.sdpa_decode(torch.zeros(1, 2, 17, 64, dtype=bf), k, k, dequant=(None, one, one), splits=65),
-                 lambda: ops.sdpa_decode(torch.zeros(1, 2, 33, 64, dtype=bf), k, k, dequant=(None, one, one)),
-                 lambda: ops.sdpa_decode(torch.zeros(1, 3, 1, 64, dtype=bf), k, k, dequant=(None, one, one)),
-                 lambda: ops.sdpa_decode(q, k, k[:, :, :4], dequant=(None, one, one)), lambda: ops.sdpa_decode(q, k, k, dequant=(None, one, one), splits=-1),
-                 lambda: ops.sdpa_decode(q, k, k, dequant=(None, one, one), attn_mask=torch.zeros(1, 4)),
-                 lambda: ops.sdpa_decode(q, k, k, dequant=(None, one, one), attn_mask=torch.zeros(1, 5, dtype=torch.int32))):
+    for call in wrapper_refusals():
         with pytest.raises(RuntimeError):
             call()
     with pytest.raises(ValueError, match="is_causal"):
-        ops.sdpa_decode(q, k, k, dequant=(None, one, one), attn_mask=torch.zeros(1, 5), is_causal=True)
+        causal_with_a_mask()
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------------------
