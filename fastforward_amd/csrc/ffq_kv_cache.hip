@@ -16,15 +16,23 @@
 // pools: the lane reads the sequence's block table once (page table[b][pos / P]) and writes row pos % P of that page; a table entry
 // outside [0, num_pages) drops the row. The codes, the rotation (table row `pos`) and the resources are the dense kernel's.
 //
-// Host side: both entry points run the shared rules (check_shape, check_quantizers_and_tables, check_sizes_and_buffers) in the order
+// kv_token_store_kernel (ffq_kv_token_append, include/ffq_kv_token.h) is the dense body with a dynamic quantizer per row: the E / 16
+// neighbouring lanes of a row reduce its min / max (NaN apart, as ffq_minmax_by_tile propagates it) with three DPP steps at most,
+// every one of them runs A5 (range_to_parameters: one copy of the arithmetic) on the same pair, quantizes its own 16 elements with A1,
+// and the row's first lane writes (k_scale, k_offset, v_scale, v_offset) with one 16-byte store. In the rotary path the lane's 16
+// elements are the two 8-element halves it rotated, after their rounding to the data dtype. No LDS, no scratch.
+//
+// Host side: the entry points run the shared rules (check_shape, check_quantizers_and_tables, check_sizes_and_buffers) in the order
 // their error tables pin, with their own steps in between, fill() the kernel's arguments and launch through launch_rows.
 #include "ffq_affine.h"
 #include "ffq_common.h"
+#include "ffq_extrema.h"
 #include "ffq_paging.h"
 #include "ffq_vec.h"
 
 #include "../../include/ffq_kv_cache.h"
 #include "../../include/ffq_kv_paged.h"
+#include "../../include/ffq_kv_token.h"
 
 #include <math.h>
 
@@ -76,9 +84,132 @@ struct PagedStoreArgs : AppendArgs {
   Paging pg;
 };
 
+// A cache with per-position parameters (include/ffq_kv_token.h): ks / ko / vs / vo are unused, `params` is the fp32 store with the
+// (batch, head, row) strides ps, and krange / vrange hold A5's constants of the two dynamic quantizers
+struct TokenStoreArgs : AppendArgs {
+  float* params;
+  int64_t ps[3];
+  RangeArgs krange, vrange;
+};
+
+typedef __attribute__((ext_vector_type(4))) float kv_f32x4;
+
+// min / max of a row's elements; torch.min / torch.max propagate NaN and v_min_f32 / v_max_f32 do not, so NaN travels apart
+struct RowRange {
+  float mn, mx;
+  int nan;
+};
+
+template <int N>
+__device__ __forceinline__ RowRange range_of(const float (&x)[N]) {
+  RowRange m = {INFINITY, -INFINITY, 0};
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    m.mn = __builtin_fminf(m.mn, x[i]);
+    m.mx = __builtin_fmaxf(m.mx, x[i]);
+    m.nan |= x[i] != x[i];
+  }
+  return m;
+}
+
+template <int CTRL>
+__device__ __forceinline__ void range_step(RowRange& m) {
+  const int mn = __builtin_bit_cast(int, m.mn), mx = __builtin_bit_cast(int, m.mx);
+  m.mn = __builtin_fminf(m.mn, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(mn, mn, CTRL, 0xf, 0xf, false)));
+  m.mx = __builtin_fmaxf(m.mx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(mx, mx, CTRL, 0xf, 0xf, false)));
+  m.nan |= __builtin_amdgcn_update_dpp(m.nan, m.nan, CTRL, 0xf, 0xf, false);
+}
+
+// The butterfly over the 4 (E = 64) or 8 (E = 128) neighbouring lanes that hold one row: every one of them ends with the row's range.
+// The lanes of a row are all active here (they leave together: `items` is a multiple of the group and `pos` is uniform over it)
+__device__ __forceinline__ void range_over_row(RowRange& m, int chunk_shift) {
+  range_step<0xB1>(m);                        // quad_perm [1,0,3,2]: lane ^ 1
+  range_step<0x4E>(m);                        // quad_perm [2,3,0,1]: lane ^ 2
+  if (chunk_shift == 3) range_step<0x141>(m); // row_half_mirror: lane -> 7 - lane within 8
+  if (m.nan) m.mn = m.mx = NAN;
+}
+
+// A5 then A1 of this lane's N elements of a row whose range is `m`; returns the row's (scale, rounded offset)
+template <int N>
+__device__ __forceinline__ void quantize_row_part(const float (&x)[N], const RowRange& m, const RangeArgs& r, float lo, float hi, float& s, float& o,
+                                                  Chunk<int8_t, N>& y) {
+  range_to_parameters(m.mn, m.mx, 0, r, s, o);
+  quantize_chunk_to_bytes<N>(x, s, o, lo, hi, y);
+}
+
+// K of one lane, rotated: columns [8 j, +8) of both halves with table row `pos` (the arithmetic both kernels' rotary paths share)
+template <typename T, typename Args>
+__device__ __forceinline__ void rotate_halves(const Args& a, const T* kn, int64_t pos, int64_t j, float (&ol)[8], float (&oh)[8]) {
+  const int64_t half = a.E / 2;
+  const T* cr = static_cast<const T*>(a.cos) + pos * a.E;
+  const T* sr = static_cast<const T*>(a.sin) + pos * a.E;
+  Chunk<T, 8> x1c, x2c, cl, ch, sl, sh;
+  x1c.load(kn + j * 8);
+  x2c.load(kn + half + j * 8);
+  cl.load(cr + j * 8);
+  ch.load(cr + half + j * 8);
+  sl.load(sr + j * 8);
+  sh.load(sr + half + j * 8);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float x1 = x1c.get(i), x2 = x2c.get(i);
+    const float p = rd<T>(x1 * cl.get(i)), q = rd<T>((-x2) * sl.get(i));
+    const float r = rd<T>(x2 * ch.get(i)), t = rd<T>(x1 * sh.get(i));
+    ol[i] = rd<T>(p + q);
+    oh[i] = rd<T>(r + t);
+  }
+}
+
+// The rows of ffq_kv_token_append, once a lane knows where its row goes: V, then K (rotated or plain), each reduced over the row,
+// turned into parameters and quantized; the row's first lane stores the four parameters
+template <typename T, bool ROPE>
+__device__ __forceinline__ void token_row(const TokenStoreArgs& a, const T* kn, const T* vn, int8_t* kc, int8_t* vc, float* prm, int64_t pos, int64_t j) {
+  float ks, ko, vs, vo;
+  {
+    Chunk<T, 16> x;
+    x.load(vn + j * 16);
+    float xf[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) xf[i] = x.get(i);
+    RowRange m = range_of<16>(xf);
+    range_over_row(m, a.chunk_shift);
+    Chunk<int8_t, 16> y;
+    quantize_row_part<16>(xf, m, a.vrange, a.vlo, a.vhi, vs, vo, y);
+    y.store(vc + j * 16);
+  }
+  if constexpr (!ROPE) {
+    Chunk<T, 16> x;
+    x.load(kn + j * 16);
+    float xf[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) xf[i] = x.get(i);
+    RowRange m = range_of<16>(xf);
+    range_over_row(m, a.chunk_shift);
+    Chunk<int8_t, 16> y;
+    quantize_row_part<16>(xf, m, a.krange, a.klo, a.khi, ks, ko, y);
+    y.store(kc + j * 16);
+  } else {
+    float ol[8], oh[8];
+    rotate_halves<T>(a, kn, pos, j, ol, oh);
+    RowRange m = range_of<8>(ol);
+    const RowRange mh = range_of<8>(oh);
+    m.mn = __builtin_fminf(m.mn, mh.mn);
+    m.mx = __builtin_fmaxf(m.mx, mh.mx);
+    m.nan |= mh.nan;
+    range_over_row(m, a.chunk_shift);
+    Chunk<int8_t, 8> yl, yh;
+    quantize_row_part<8>(ol, m, a.krange, a.klo, a.khi, ks, ko, yl);
+    quantize_row_part<8>(oh, m, a.krange, a.klo, a.khi, ks, ko, yh);
+    yl.store(kc + j * 8);
+    yh.store(kc + a.E / 2 + j * 8);
+  }
+  if (j == 0) *reinterpret_cast<kv_f32x4*>(prm) = kv_f32x4{ks, ko, vs, vo};
+}
+
 // The body of both kernels. PAGED changes where a row's codes go: page table[b][pos / P], row pos % P of the pools; a row whose table
 // entry lies outside the pool is dropped like one outside [0, S_max), before any load
-template <typename T, bool ROPE, bool PAGED, typename Args>
+// TOKEN (kv_token_store_kernel): the row's parameters are its own, computed here (token_row)
+template <typename T, bool ROPE, bool PAGED, bool TOKEN = false, typename Args>
 __device__ __forceinline__ void append_rows(const Args& a) {
   const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (item >= a.items) return;
@@ -99,6 +230,10 @@ __device__ __forceinline__ void append_rows(const Args& a) {
   }
   int8_t* kc = a.kc + slot * a.kcs[0] + kvh * a.kcs[1] + at * a.kcs[2];
   int8_t* vc = a.vc + slot * a.vcs[0] + kvh * a.vcs[1] + at * a.vcs[2];
+  if constexpr (TOKEN) {
+    token_row<T, ROPE>(a, kn, vn, kc, vc, a.params + b * a.ps[0] + kvh * a.ps[1] + pos * a.ps[2], pos, j);
+    return;
+  }
   const float ks = a.ks[0], ko = a.ko ? rne(a.ko[0]) : 0.0f;
   const float vs = a.vs[0], vo = a.vo ? rne(a.vo[0]) : 0.0f;
 
@@ -107,24 +242,8 @@ __device__ __forceinline__ void append_rows(const Args& a) {
     append16<T>(kn + j * 16, kc + j * 16, ks, ko, a.klo, a.khi);
   } else {
     const int64_t half = a.E / 2;
-    const T* cr = static_cast<const T*>(a.cos) + pos * a.E;
-    const T* sr = static_cast<const T*>(a.sin) + pos * a.E;
-    Chunk<T, 8> x1c, x2c, cl, ch, sl, sh;
-    x1c.load(kn + j * 8);
-    x2c.load(kn + half + j * 8);
-    cl.load(cr + j * 8);
-    ch.load(cr + half + j * 8);
-    sl.load(sr + j * 8);
-    sh.load(sr + half + j * 8);
     float ol[8], oh[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float x1 = x1c.get(i), x2 = x2c.get(i);
-      const float p = rd<T>(x1 * cl.get(i)), q = rd<T>((-x2) * sl.get(i));
-      const float r = rd<T>(x2 * ch.get(i)), t = rd<T>(x1 * sh.get(i));
-      ol[i] = rd<T>(p + q);
-      oh[i] = rd<T>(r + t);
-    }
+    rotate_halves<T>(a, kn, pos, j, ol, oh);
     Chunk<int8_t, 8> yl, yh;
     quantize_chunk_to_bytes<8>(ol, ks, ko, a.klo, a.khi, yl);
     quantize_chunk_to_bytes<8>(oh, ks, ko, a.klo, a.khi, yh);
@@ -144,6 +263,12 @@ __global__ __launch_bounds__(kBlock) void kv_paged_store_kernel(PagedStoreArgs a
   append_rows<T, ROPE, true>(a);
 }
 
+// (its name does not hold "kv_append" either)
+template <typename T, bool ROPE>
+__global__ __launch_bounds__(kBlock) void kv_token_store_kernel(TokenStoreArgs a) {
+  append_rows<T, ROPE, false, true>(a);
+}
+
 bool bits_ok(double bits) { return bits >= 2.0 && bits <= 8.0 && bits == (double)(int)bits; }
 
 // Each rule of the two entry points once: it takes the entry point's name for its message and returns the first failing status. An
@@ -158,15 +283,26 @@ int check_shape(const char* name, int dt, const int64_t* strides, int64_t E, int
   return FFQ_OK;
 }
 
-// The two quantizers and the rotary tables; `positions` is how the entry point words what the tables need a row for
-int check_quantizers_and_tables(const char* name, const float* k_scale, double k_num_bits, const float* v_scale, double v_num_bits, const void* cos_table,
-                                const void* sin_table, int64_t table_rows, int64_t capacity, const char* positions) {
+// The two bit-widths
+int check_bits(const char* name, double k_num_bits, double v_num_bits) {
   if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "%s: the quantizers need an integral bit-width in 2..8", name);
-  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "%s: a quantizer (and its offset) needs its scale", name);
+  return FFQ_OK;
+}
+
+// The rotary tables; `positions` is how the entry point words what the tables need a row for
+int check_tables(const char* name, const void* cos_table, const void* sin_table, int64_t table_rows, int64_t capacity, const char* positions) {
   if (!cos_table != !sin_table) return fail(FFQ_ERR_ARG, "%s: the rotary tables come as a pair", name);
   if (cos_table && table_rows < capacity)
     return fail(FFQ_ERR_ARG, "%s: the rotary tables need a row for every %s (%lld < %lld)", name, positions, (long long)table_rows, (long long)capacity);
   return FFQ_OK;
+}
+
+// The two static quantizers and the rotary tables
+int check_quantizers_and_tables(const char* name, const float* k_scale, double k_num_bits, const float* v_scale, double v_num_bits, const void* cos_table,
+                                const void* sin_table, int64_t table_rows, int64_t capacity, const char* positions) {
+  if (int rc = check_bits(name, k_num_bits, v_num_bits)) return rc;
+  if (!k_scale || !v_scale) return fail(FFQ_ERR_ARG, "%s: a quantizer (and its offset) needs its scale", name);
+  return check_tables(name, cos_table, sin_table, table_rows, capacity, positions);
 }
 
 // The sizes, the alignment, the twelve strides, then the NULL check. `rows`: the new rows and the caches (16-byte aligned, not NULL);
@@ -259,4 +395,31 @@ extern "C" int ffq_kv_paged_append(const void* k_new, const void* v_new, int dt,
   a.pg = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
   if (dt == FFQ_F16) return launch_rows(kv_paged_store_kernel<f16_t, true>, kv_paged_store_kernel<f16_t, false>, a, "kv_paged_store_kernel", s);
   return launch_rows(kv_paged_store_kernel<bf16_t, true>, kv_paged_store_kernel<bf16_t, false>, a, "kv_paged_store_kernel", s);
+}
+
+extern "C" int ffq_kv_token_append(const void* k_new, const void* v_new, int dt, void* k_cache, void* v_cache, void* params, const void* lens,
+                                   int64_t batch, int64_t kv_heads, int64_t L, int64_t S_max, int64_t E, const int64_t* strides, double k_num_bits,
+                                   int k_symmetric, double v_num_bits, int v_symmetric, const void* cos_table, const void* sin_table,
+                                   int64_t table_rows, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = check_shape("kv_token_append", dt, strides, E, batch, kv_heads, L, S_max)) return rc;
+  if (int rc = check_bits("kv_token_append", k_num_bits, v_num_bits)) return rc;
+  if ((k_symmetric != 0 && k_symmetric != 1) || (v_symmetric != 0 && v_symmetric != 1))
+    return fail(FFQ_ERR_ARG, "kv_token_append: symmetric is 0 (scale and offset) or 1 (scale alone)");
+  if (int rc = check_tables("kv_token_append", cos_table, sin_table, table_rows, S_max, "cache position")) return rc;
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (int rc = check_sizes_and_buffers("kv_token_append", batch, kv_heads, L, S_max, E, strides, {k_new, v_new, k_cache, v_cache, params}, cos_table, sin_table, {lens}, "lens")) return rc;
+  for (int i = 12; i < 15; ++i)
+    if (strides[i] < 0 || strides[i] % 4) return fail(FFQ_ERR_ARG, "kv_token_append: the strides of params must be non-negative multiples of 16 bytes");
+  if (S_max == 0) return FFQ_OK;  // (no position to write to)
+
+  TokenStoreArgs a;
+  fill(a, k_new, v_new, k_cache, v_cache, lens, batch, kv_heads, L, S_max, E, strides, nullptr, nullptr, k_num_bits, nullptr, nullptr, v_num_bits,
+       cos_table, sin_table);
+  a.params = static_cast<float*>(params);
+  for (int i = 0; i < 3; ++i) a.ps[i] = strides[12 + i];
+  a.krange = make_range_args(FFQ_F32, 1, k_num_bits, k_symmetric, 0, FFQ_F32, FFQ_F32, 1);
+  a.vrange = make_range_args(FFQ_F32, 1, v_num_bits, v_symmetric, 0, FFQ_F32, FFQ_F32, 1);
+  if (dt == FFQ_F16) return launch_rows(kv_token_store_kernel<f16_t, true>, kv_token_store_kernel<f16_t, false>, a, "kv_token_store_kernel", s);
+  return launch_rows(kv_token_store_kernel<bf16_t, true>, kv_token_store_kernel<bf16_t, false>, a, "kv_token_store_kernel", s);
 }

@@ -38,7 +38,13 @@
 // wave's 32 keys, P = 16 gives two), and the keys of a table entry outside the pool are neither loaded nor scored (-inf, as a bool
 // mask would). The key order, the arithmetic, the LDS and the combine kernel are the dense form's: the same bits at the same split count.
 //
-// Host side: the three entry points fill one DecodeCall from their own parameter lists, run the shared rules (check_operands,
+// ffq_kv_token_decode (include/ffq_kv_token.h) is ffq_kv_decode over codes whose (scale, offset) live per position in an fp32 store
+// beside them. kv_token_partial_kernel is decode_partial instantiated with TOKEN: stage_load loads the lane's key position's four
+// floats (k_scale, k_offset, v_scale, v_offset) with one 16-byte load beside the K and V codes (zeros for a position that is not
+// loaded), and the tile's dks / dko / dvs / dvo come out of those staging registers when the tile is consumed, each lane's own. Nothing
+// else differs: the same bits as the dense form wherever the parameters agree.
+//
+// Host side: the entry points fill one DecodeCall from their own parameter lists, run the shared rules (check_operands,
 // check_rows, check_quantizer_and_splits, check_sizes_and_buffers, check_layout_and_workspace) in the order their error tables pin,
 // with their own steps in between, and hand the call to enqueue(); launch_partial is the one partial launch (docs/kernels.md).
 #include "ffq_affine.h"
@@ -48,6 +54,7 @@
 
 #include "../../include/ffq_kv_cache.h"
 #include "../../include/ffq_kv_paged.h"
+#include "../../include/ffq_kv_token.h"
 #include "../../include/ffq_sdpa_decode.h"
 
 #include <math.h>
@@ -178,9 +185,17 @@ struct PagedDecodeArgs : DecodeArgs {
   Paging pg;
 };
 
-// The body of both partial kernels. PAGED changes where a lane finds its key row (stage_load) and adds one mask, the keys of a page
-// the table does not place inside the pool; the arithmetic and the key order are the dense form's
-template <int E, bool F16, bool PAGED, typename Args>
+// Per-position parameters (include/ffq_kv_token.h): deq_s[1..2] / deq_o[1..2] are unused, `params` is the fp32 store
+// [batch, kv_heads, S, 4] of (k_scale, k_offset, v_scale, v_offset) with the (batch, head, row) strides ps
+struct TokenDecodeArgs : DecodeArgs {
+  const float* params;
+  int64_t ps[3];
+};
+
+// The body of the partial kernels. PAGED changes where a lane finds its key row (stage_load) and adds one mask, the keys of a page
+// the table does not place inside the pool; the arithmetic and the key order are the dense form's. TOKEN changes where a lane finds
+// the (scale, offset) of its key row: staged beside the codes, one 16-byte load per lane and tile
+template <int E, bool F16, bool PAGED, bool TOKEN = false, typename Args>
 __device__ __forceinline__ void decode_partial(const Args& a) {
   constexpr int T = E / 16;   // MFMA k-steps of QK^T
   constexpr int U = E / 32;   // 16-byte loads per key row and lane
@@ -218,8 +233,11 @@ __device__ __forceinline__ void decode_partial(const Args& a) {
 
   const bool deq_q = a.deq_s[0] != nullptr;
   const float dqs = deq_q ? a.deq_s[0][0] : 1.0f, dqo = (deq_q && a.deq_o[0]) ? rne(a.deq_o[0][0]) : 0.0f;
-  const float dks = a.deq_s[1][0], dko = (a.deq_o[1] ? rne(a.deq_o[1][0]) : 0.0f) - 128.0f;  // (biased: dequant4)
-  const float dvs = a.deq_s[2][0], dvo = (a.deq_o[2] ? rne(a.deq_o[2][0]) : 0.0f) - 128.0f;
+  float dks = 0.0f, dko = 0.0f, dvs = 0.0f, dvo = 0.0f;  // (TOKEN: this lane's key row's, out of the staging registers)
+  if constexpr (!TOKEN) {
+    dks = a.deq_s[1][0], dko = (a.deq_o[1] ? rne(a.deq_o[1][0]) : 0.0f) - 128.0f;  // (biased: dequant4)
+    dvs = a.deq_s[2][0], dvo = (a.deq_o[2] ? rne(a.deq_o[2][0]) : 0.0f) - 128.0f;
+  }
   const float alpha = a.c * a.c;
 
   // ---- Q fragments: step t = 2u + j takes columns [(2u + h) * 16 + 8j, +8) of row `row` (the slices of the K loads)
@@ -250,6 +268,9 @@ __device__ __forceinline__ void decode_partial(const Args& a) {
   const int8_t* vbase = a.v + (PAGED ? 0 : (int64_t)b * a.vs[0]) + (int64_t)kvh * a.vs[1] + h * 16;
   u32x4 sk[U], sv[U];
   uint32_t staged_ok = 0;
+  [[maybe_unused]] dc_f32x4 sprm = {0.0f, 0.0f, 0.0f, 0.0f};  // (TOKEN) the staged key row's (k_scale, k_offset, v_scale, v_offset)
+  [[maybe_unused]] const float* pbase = nullptr;
+  if constexpr (TOKEN) pbase = a.params + (int64_t)b * a.ps[0] + (int64_t)kvh * a.ps[1];
   auto stage_load = [&](int32_t it) {
     const int32_t key = k_begin + it * kTile + (int32_t)wave * kWaveKeys + (int32_t)r32;
     bool in = key < k_end;
@@ -262,6 +283,10 @@ __device__ __forceinline__ void decode_partial(const Args& a) {
       k_page = (int64_t)page * a.ks[0];
       v_page = (int64_t)page * a.vs[0];
       staged_ok = (uint32_t)__ballot(in);  // (both halves of the wave hold the same 32 keys)
+    }
+    if constexpr (TOKEN) {
+      sprm = dc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (in) sprm = *reinterpret_cast<const dc_f32x4*>(pbase + (int64_t)at * a.ps[2]);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -290,6 +315,10 @@ __device__ __forceinline__ void decode_partial(const Args& a) {
     // this tile's operands out of the staging registers, the next tile's loads into them
     dc_bf16x8 kf[T];
     u32x4 vw[U][2];
+    if constexpr (TOKEN) {  // (the offsets are stored rounded; biased as above)
+      dks = sprm.x; dko = sprm.y - 128.0f;
+      dvs = sprm.z; dvo = sprm.w - 128.0f;
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       u32x4 lo, hi;
@@ -473,6 +502,12 @@ __global__ __launch_bounds__(kThreads) void kv_paged_partial_kernel(PagedDecodeA
   decode_partial<E, F16, true>(a);
 }
 
+// (its name holds none of the names the dense and the paged kernels are counted by)
+template <int E, bool F16>
+__global__ __launch_bounds__(kThreads) void kv_token_partial_kernel(TokenDecodeArgs a) {
+  decode_partial<E, F16, false, true>(a);
+}
+
 struct CombineArgs {
   const float* ws_o;
   const float* ws_m;
@@ -564,6 +599,8 @@ struct DecodeCall {
   void* workspace;
   size_t workspace_bytes;
   const Paging* paging = nullptr;
+  const float* params = nullptr;  // (ffq_kv_token_decode) the per-position store and its three strides
+  const int64_t* param_strides = nullptr;
 };
 
 int64_t rows_of(const DecodeCall& c) { return c.L * (c.q_heads / c.kv_heads); }
@@ -648,11 +685,18 @@ int enqueue(const DecodeCall& c, hipStream_t s) {
   a.ws_l = a.ws_m + parts * rows;
   a.pg = c.paging ? *c.paging : Paging{};
   const bool f16 = c.dt == FFQ_F16;
-  if (c.paging && c.E == 64) launch_partial(kv_paged_partial_kernel<64, true>, kv_paged_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
+  if (c.params) {
+    TokenDecodeArgs t;
+    static_cast<DecodeArgs&>(t) = a;
+    t.params = c.params;
+    for (int i = 0; i < 3; ++i) t.ps[i] = c.param_strides[i];
+    if (c.E == 64) launch_partial(kv_token_partial_kernel<64, true>, kv_token_partial_kernel<64, false>, f16, t, (unsigned)parts, s);
+    else launch_partial(kv_token_partial_kernel<128, true>, kv_token_partial_kernel<128, false>, f16, t, (unsigned)parts, s);
+  } else if (c.paging && c.E == 64) launch_partial(kv_paged_partial_kernel<64, true>, kv_paged_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
   else if (c.paging) launch_partial(kv_paged_partial_kernel<128, true>, kv_paged_partial_kernel<128, false>, f16, a, (unsigned)parts, s);
   else if (c.E == 64) launch_partial<DecodeArgs>(sdpa_decode_partial_kernel<64, true>, sdpa_decode_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
   else launch_partial<DecodeArgs>(sdpa_decode_partial_kernel<128, true>, sdpa_decode_partial_kernel<128, false>, f16, a, (unsigned)parts, s);
-  if (int rc = check_launch(c.paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel")) return rc;
+  if (int rc = check_launch(c.params ? "kv_token_partial_kernel" : c.paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel")) return rc;
 
   CombineArgs m;
   m.ws_o = a.ws_o; m.ws_m = a.ws_m; m.ws_l = a.ws_l;
@@ -754,5 +798,34 @@ extern "C" int ffq_kv_paged_decode(const void* q, int q_dt, const void* k_pool, 
   if (int rc = check_layout_and_workspace("kv_paged_decode", c, aligned4(lens) && aligned4(block_table), " (lens, block_table: 4-byte)")) return rc;
   const Paging paging = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
   c.paging = &paging;
+  return enqueue(c, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ffq_kv_token_decode(const void* q, int q_dt, const void* k, const void* v, int dt, const float* q_scale, const float* q_offset,
+                                   const void* params, const void* lens, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t L, int64_t S_max,
+                                   int64_t E, const int64_t* strides, int causal, double sqrt_scale, const float* out_scale, const float* out_offset,
+                                   double out_num_bits, int64_t splits, int64_t plan_len, void* out, void* workspace, size_t workspace_bytes_given,
+                                   void* stream) {
+  // the tables of the shared rules: the query's own pair, and the store in the place of the scales of k and v (it holds them)
+  const float* const deq_scale[3] = {q_scale, static_cast<const float*>(params), static_cast<const float*>(params)};
+  const float* const deq_offset[3] = {q_offset, nullptr, nullptr};
+  DecodeCall c;
+  c.q = q; c.q_dt = q_dt; c.k = k; c.v = v; c.dt = dt; c.deq_scale = deq_scale; c.deq_offset = deq_offset;
+  c.batch = batch; c.q_heads = q_heads; c.kv_heads = kv_heads; c.L = L; c.keys = S_max; c.E = E; c.strides = strides;
+  c.lens = static_cast<const int32_t*>(lens); c.mask_kind = causal ? MASK_CAUSAL : MASK_NONE;
+  c.sqrt_scale = sqrt_scale; c.out_scale = out_scale; c.out_offset = out_offset; c.out_num_bits = out_num_bits;
+  c.splits = splits; c.plan_len = plan_len; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes_given;
+  c.params = static_cast<const float*>(params); c.param_strides = strides ? strides + 12 : nullptr;
+  if (int rc = check_operands("kv_token_decode", c)) return rc;
+  if (int rc = check_rows("kv_token_decode", c)) return rc;
+  if (causal != 0 && causal != 1) return fail(FFQ_ERR_ARG, "kv_token_decode: causal is 0 (every key) or 1 (bottom-right)");
+  if (int rc = check_quantizer_and_splits("kv_token_decode", c)) return rc;
+  if (plan_len < 0 || plan_len > S_max) return fail(FFQ_ERR_ARG, "kv_token_decode: plan_len must be 0 (S_max) or 1..S_max");
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (S_max == 0) return fail(FFQ_ERR_ARG, "kv_token_decode: S_max must be >= 1");
+  if (int rc = check_sizes_and_buffers("kv_token_decode", c, lens != nullptr)) return rc;
+  for (int i = 12; i < 15; ++i)
+    if (strides[i] < 0 || strides[i] % 4) return fail(FFQ_ERR_ARG, "kv_token_decode: the strides of params must be non-negative multiples of 16 bytes");
+  if (int rc = check_layout_and_workspace("kv_token_decode", c, aligned16(params) && aligned4(lens), " (lens: 4-byte)")) return rc;
   return enqueue(c, static_cast<hipStream_t>(stream));
 }

@@ -34,3 +34,4 @@ from fastforward_amd.nn.conv import QuantizedConv3d as QuantizedConv3d  # isort:
 from fastforward_amd.nn.conv import quantized_conv3d_modules as quantized_conv3d_modules  # isort: skip
 from fastforward_amd.nn.kv_cache import QuantizedKVCache as QuantizedKVCache  # isort: skip
 from fastforward_amd.nn.kv_cache import PagedQuantizedKVCache as PagedQuantizedKVCache  # isort: skip
+from fastforward_amd.nn.kv_cache import DynamicQuantizedKVCache as DynamicQuantizedKVCache  # isort: skip

@@ -15,6 +15,11 @@ that lacks the entry points, not a fast path.
 (``ops.kv_paged_append`` / ``ops.kv_paged_decode``, include/ffq_kv_paged.h): a sequence owns only the pages it uses, a finished one
 gives them back without a copy, and sequences can share the pages of a common prefix. Its page bookkeeping is host code that runs
 outside a captured step; ``composed_paged_append`` / ``composed_paged_attend`` gather the pages into a dense view and run the chain above.
+
+``DynamicQuantizedKVCache`` is the dense cache with two ``DynamicLinearQuantizer``s: every appended row gets its own
+``(scale, offset)``, computed on the device from the row's min / max and kept in an fp32 store ``[B, H, S_max, 4]`` beside the codes
+(``ops.kv_token_append`` / ``ops.kv_token_decode``, include/ffq_kv_token.h), so nothing is calibrated ahead of serving.
+``composed_token_append`` / ``composed_token_attend`` are its chain from the quantizer modules themselves.
 """
 
 from __future__ import annotations
@@ -24,7 +29,10 @@ from typing import Any, Sequence
 import torch
 
 from fastforward_amd import _native, ops
+from fastforward_amd.nn.dynamic_linear_quantizer import DynamicLinearQuantizer
 from fastforward_amd.nn.linear_quantizer import LinearQuantizer
+from fastforward_amd.quantization.affine import AffineQuantizationFunction, StaticAffineQuantParams
+from fastforward_amd.quantization.function import QuantizationContext
 from fastforward_amd.quantized_tensor import QuantizedTensor
 
 LAYOUTS = ("bhse", "bshe")
@@ -116,14 +124,19 @@ class _CacheBase:
 
     _SYMBOLS: tuple[str, str]
 
-    def __init__(self, dtype: torch.dtype, head_dim: int, key_quantizer: LinearQuantizer, value_quantizer: LinearQuantizer) -> None:
+    def _quantizer_rule(self, quantizer: Any, what: str) -> tuple:
+        """What the class's append call takes for one quantizer, else ValueError: the per-tensor static rule unless a subclass has its own."""
+        return _quantizer_params(quantizer, what)
+
+    def __init__(self, dtype: torch.dtype, head_dim: int, key_quantizer: Any, value_quantizer: Any) -> None:
         name = type(self).__name__
         if dtype not in _VALUES:
             raise ValueError(f"{name}: the data dtype is bf16 or fp16, got {dtype}")
         if head_dim not in (64, 128):
             raise ValueError(f"{name}: head_dim must be 64 or 128, got {head_dim}")
-        _quantizer_params(key_quantizer, "key")
-        _quantizer_params(value_quantizer, "value")
+        self.head_dim = head_dim
+        self._quantizer_rule(key_quantizer, "key")
+        self._quantizer_rule(value_quantizer, "value")
         self.key_quantizer, self.value_quantizer, self.dtype = key_quantizer, value_quantizer, dtype
 
     def _native(self, *tensors: torch.Tensor) -> bool:
@@ -138,7 +151,7 @@ class _CacheBase:
             raise ValueError(f"{name}.append: key / value are {rows}, got {tuple(key.shape)}, {tuple(value.shape)}")
         if key.dtype != self.dtype or value.dtype != self.dtype:
             raise ValueError(f"{name}.append: the new rows are plain {self.dtype} values, got {key.dtype}, {value.dtype}")
-        params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
+        params = self._quantizer_rule(self.key_quantizer, "key"), self._quantizer_rule(self.value_quantizer, "value")
         self.lengths.add_(key.shape[2])
         return params
 
@@ -161,7 +174,7 @@ class _CacheBase:
         raw, q_dequant = kernels._dequant(query)
         if not self._native(raw):
             return self._composed_attend(query, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer if fused else None)
-        k_params, v_params = _quantizer_params(self.key_quantizer, "key"), _quantizer_params(self.value_quantizer, "value")
+        k_params, v_params = self._quantizer_rule(self.key_quantizer, "key"), self._quantizer_rule(self.value_quantizer, "value")
         return self._native_attend(raw, is_causal, scale, fused or None, (q_dequant, k_params[:2], v_params[:2]), splits, plan_len)
 
 
@@ -391,3 +404,148 @@ class PagedQuantizedKVCache(_CacheBase):
         table = self.block_table if seq is None else self.block_table[seq:seq + 1]
         k, v = gather_pages(self.k_pool, table), gather_pages(self.v_pool, table)
         return (k, v) if seq is None else (k[0], v[0])
+
+
+# ---- the same cache with a dynamic quantizer per row ---------------------------------------------------------------------------------------
+def _dynamic_spec(quantizer: Any, what: str, head_dim: int) -> tuple[float, bool]:
+    """(bits, symmetric) of a dynamic quantizer the per-row append kernel reproduces, else ValueError."""
+    name = "DynamicQuantizedKVCache"
+    if not isinstance(quantizer, DynamicLinearQuantizer):
+        raise ValueError(f"{name}: the {what} quantizer must be a DynamicLinearQuantizer, got {type(quantizer).__name__}")
+    bits = quantizer.num_bits
+    probe = torch.Size((2, 3, 5, head_dim))
+    try:
+        tile = quantizer.granularity.tile_size(probe)
+    except Exception:  # (a granularity that does not take a 4-D tensor at all)
+        tile = None
+    if (quantizer.quantized_dtype != torch.int8 or not isinstance(bits, (int, float)) or bits != int(bits) or not 2 <= bits <= 8
+            or quantizer.parameter_inference_fn is not None or isinstance(tile, str) or tile is None or tuple(tile) != (1, 1, 1, head_dim)
+            or (quantizer.symmetric and quantizer.allow_one_sided)):
+        raise ValueError(
+            f"{name}: the {what} quantizer must be a DynamicLinearQuantizer with quantized_dtype=torch.int8, an integral bit-width in 2..8, no "
+            f"parameter_inference_fn, a granularity of one tile per row ((1, 1, 1, {head_dim}) of [B, H, L, E]: PerChannel((0, 1, 2)) or PerTile), "
+            "and asymmetric or symmetric with allow_one_sided=False"
+        )
+    return float(bits), bool(quantizer.symmetric)
+
+
+def _wrap_rows(codes: torch.Tensor, scale: torch.Tensor, offset: torch.Tensor, quantizer: DynamicLinearQuantizer, dtype: torch.dtype) -> QuantizedTensor:
+    """The QuantizedTensor `quantizer` returns for rows whose codes [B, H, n, E] and per-row parameters [B, H, n] are given."""
+    static = StaticAffineQuantParams(scale=scale.reshape(-1).contiguous(), offset=offset.reshape(-1).contiguous(), num_bits=quantizer.num_bits,
+                                     granularity=quantizer.granularity, quantized_dtype=quantizer.quantized_dtype, dequantize_dtype=dtype)
+    return QuantizedTensor(codes, QuantizationContext(AffineQuantizationFunction, static))
+
+
+def composed_token_append(k_cache: torch.Tensor, v_cache: torch.Tensor, params: torch.Tensor, lengths: torch.Tensor, key: torch.Tensor,
+                          value: torch.Tensor, key_quantizer: DynamicLinearQuantizer, value_quantizer: DynamicLinearQuantizer,
+                          rope: Rope | None = None) -> None:
+    """``ops.kv_token_append`` from existing pieces: per batch the rows that land inside the cache, rotated with torch ops, quantized by
+    the dynamic quantizer modules themselves, codes and per-row parameters copied to their positions. `lengths` already counts the L new
+    rows; it is read on the host."""
+    L, S_max = key.shape[2], k_cache.shape[2]
+    with torch.no_grad():
+        for b, n in enumerate(lengths.tolist()):
+            rows = [l for l in range(L) if 0 <= n - L + l < S_max]
+            if not rows:
+                continue
+            at = torch.tensor([n - L + l for l in rows], device=key.device)
+            take = torch.tensor(rows, device=key.device)
+            k_rows, v_rows = key[b:b + 1].index_select(2, take), value[b:b + 1].index_select(2, take)
+            if rope is not None:
+                k_rows = _rotate(k_rows, rope[0].index_select(0, at), rope[1].index_select(0, at))
+            for first, (cache, quantizer, data) in enumerate(((k_cache, key_quantizer, k_rows), (v_cache, value_quantizer, v_rows))):
+                quantized = quantizer(data.contiguous())
+                args = quantized.quant_args()
+                cache[b].index_copy_(1, at, quantized.raw_data[0])
+                shape = (cache.shape[1], len(rows))
+                offset = torch.zeros(shape, device=key.device) if args.offset is None else args.offset.float().reshape(shape)
+                params[b, :, :, 2 * first].index_copy_(1, at, args.scale.float().reshape(shape))
+                params[b, :, :, 2 * first + 1].index_copy_(1, at, offset)
+
+
+def composed_token_attend(query: Any, k_cache: torch.Tensor, v_cache: torch.Tensor, params: torch.Tensor, lengths: torch.Tensor,
+                          key_quantizer: DynamicLinearQuantizer, value_quantizer: DynamicLinearQuantizer, dtype: torch.dtype, is_causal: bool = True,
+                          scale: float | None = None, output_quantizer: Any = None) -> torch.Tensor:
+    """``ops.kv_token_decode`` from existing pieces: per batch, ``scaled_dot_product_attention`` over the ``[:, :, :S_b]`` slices wrapped
+    with their per-row parameters, with a bottom-right bool mask; exact zeros for a sequence without keys. `lengths` is read on the host."""
+    from fastforward_amd.nn import functional as F
+
+    B, H, L, E = query.shape
+    HKV, S_max = k_cache.shape[1], k_cache.shape[2]
+    out = torch.zeros((B, H, L, E), dtype=dtype, device=k_cache.device)
+    extra = {} if output_quantizer is None else dict(output_quantizer=output_quantizer)
+    with torch.no_grad():
+        for b, n in enumerate(lengths.tolist()):
+            S = min(max(n, 0), S_max)
+            if S == 0:
+                continue
+            rows = params[b:b + 1, :, :S]
+            keys = _wrap_rows(k_cache[b:b + 1, :, :S], rows[..., 0], rows[..., 1], key_quantizer, dtype)
+            values = _wrap_rows(v_cache[b:b + 1, :, :S], rows[..., 2], rows[..., 3], value_quantizer, dtype)
+            mask = _bottom_right(L, S, k_cache.device) if is_causal else None
+            got = F.scaled_dot_product_attention(query[b:b + 1], keys, values, attn_mask=mask, scale=scale, enable_gqa=H != HKV,
+                                                 strict_quantization=False, **extra)
+            out[b] = (got.dequantize() if isinstance(got, QuantizedTensor) else got)[0].to(dtype)
+    return out
+
+
+class DynamicQuantizedKVCache(_CacheBase):
+    """:class:`QuantizedKVCache` with two ``DynamicLinearQuantizer``s: int8 K / V codes for `batch` sequences of up to `max_len`
+    positions, every (sequence, head, position) row quantized with its own ``(scale, offset)`` from the row's min / max when it is
+    appended. ``params`` is the fp32 ``[B, H, S_max, 4]`` view of ``(k_scale, k_offset, v_scale, v_offset)`` per position (``"bshe"``
+    allocates ``[B, S_max, H, 4]``, like the codes). The quantizers hold ``quantized_dtype=torch.int8``, an integral bit-width in 2..8, no
+    ``parameter_inference_fn``, a granularity of one tile per row (``PerChannel((0, 1, 2))`` or ``PerTile((1, 1, 1, E))``), and are
+    asymmetric, or symmetric with ``allow_one_sided=False``. ``append`` and ``attend`` are one launch each and read nothing on the host."""
+
+    _SYMBOLS = ("ffq_kv_token_append", "ffq_kv_token_decode")
+
+    def __init__(self, batch: int, kv_heads: int, max_len: int, head_dim: int, key_quantizer: DynamicLinearQuantizer,
+                 value_quantizer: DynamicLinearQuantizer, dtype: torch.dtype = torch.bfloat16, device: torch.device | str = "cuda",
+                 layout: str = "bhse") -> None:
+        if layout not in LAYOUTS:
+            raise ValueError(f"DynamicQuantizedKVCache: layout is one of {LAYOUTS}, got {layout!r}")
+        if min(batch, kv_heads, max_len) < 1:
+            raise ValueError(f"DynamicQuantizedKVCache: batch, kv_heads and max_len are positive, got {batch}, {kv_heads}, {max_len}")
+        super().__init__(dtype, head_dim, key_quantizer, value_quantizer)
+        self.layout, self.max_len = layout, max_len
+        lead = (batch, kv_heads, max_len) if layout == "bhse" else (batch, max_len, kv_heads)
+        buffers = [torch.zeros((*lead, head_dim), dtype=torch.int8, device=device) for _ in range(2)]
+        buffers.append(torch.zeros((*lead, 4), dtype=torch.float32, device=device))
+        self.k_cache, self.v_cache, self.params = (t if layout == "bhse" else t.transpose(1, 2) for t in buffers)
+        self.lengths = torch.zeros(batch, dtype=torch.int32, device=device)
+
+    def _quantizer_rule(self, quantizer: Any, what: str) -> tuple[float, bool]:
+        return _dynamic_spec(quantizer, what, self.head_dim)
+
+    def reset(self, lengths: torch.Tensor | Sequence[int] | None = None) -> None:
+        """Every sequence back to length 0, or to `lengths` (codes and parameters stay where they are)."""
+        QuantizedKVCache.reset(self, lengths)  # type: ignore[arg-type]
+
+    def append(self, key: torch.Tensor, value: torch.Tensor, rope: Rope | None = None) -> None:
+        """:meth:`QuantizedKVCache.append` with every row's own parameters: ``lengths += L``, then row l of batch b goes to position
+        ``lengths[b] - L + l`` with the codes and the ``(scale, offset)`` its dynamic quantizer gives that row (K rotated first with
+        ``rope``); rows outside ``[0, max_len)`` are dropped and their parameters stay as they were."""
+        k_spec, v_spec = self._new_rows(key, value, self.k_cache, f"[B, H, L, E] rows of a {tuple(self.k_cache.shape)} cache")
+        if self._native(key, value):
+            ops.kv_token_append(key.detach(), value.detach(), self.k_cache, self.v_cache, self.params, self.lengths, k_spec, v_spec, rope=rope)
+        else:
+            composed_token_append(self.k_cache, self.v_cache, self.params, self.lengths, key.detach(), value.detach(), self.key_quantizer,
+                                  self.value_quantizer, rope)
+
+    def _native_attend(self, raw, is_causal, scale, output_quantizer, dequant, splits, plan_len) -> torch.Tensor:
+        return ops.kv_token_decode(raw, self.k_cache, self.v_cache, self.params, self.lengths, is_causal, scale, output_quantizer, dequant[0], self.dtype,
+                                   splits, plan_len)
+
+    def _composed_attend(self, query: Any, **how: Any) -> torch.Tensor:
+        return composed_token_attend(query, self.k_cache, self.v_cache, self.params, self.lengths, self.key_quantizer, self.value_quantizer,
+                                     self.dtype, **how)
+
+    def keys(self, length: int) -> QuantizedTensor:
+        """The first `length` positions of every sequence's keys as the QuantizedTensor the key quantizer would have returned for those
+        rows: the codes with one (scale, offset) per row."""
+        rows = self.params[:, :, :length]
+        return _wrap_rows(self.k_cache[:, :, :length], rows[..., 0], rows[..., 1], self.key_quantizer, self.dtype)
+
+    def values(self, length: int) -> QuantizedTensor:
+        rows = self.params[:, :, :length]
+        return _wrap_rows(self.v_cache[:, :, :length], rows[..., 2], rows[..., 3], self.value_quantizer, self.dtype)

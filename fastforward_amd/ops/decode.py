@@ -112,11 +112,13 @@ def _split_workspace(B: int, HKV: int, rows: int, E: int, keys: int, splits: int
 
 def _run_decode(symbol: str, query: torch.Tensor, k: torch.Tensor, v: torch.Tensor, others: Sequence[torch.Tensor | None], dt: torch.dtype,
                 shape: tuple[int, ...], plan_keys: int, splits: int, scale: float | None, dequant: Sequence[Dequant | None], output_quantizer,
-                extents: tuple, selection: tuple, split_args: tuple | None = None) -> torch.Tensor:
+                extents: tuple, selection: tuple, split_args: tuple | None = None, row_params: torch.Tensor | None = None) -> torch.Tensor:
     """The tail of the three decode wrappers, after their checks: the tables, the library, the split count and the workspace, the
     output, and the call of `symbol`. `others` are the entry point's own tensors (a mask; lens; lens and the block table); `extents`
     and `selection` are its own arguments on either side of the strides; `split_args` is what it takes in the place of the split
-    count (``splits`` and ``plan_len`` as given, for the cache forms)."""
+    count (``splits`` and ``plan_len`` as given, for the cache forms). `row_params` (``ffq_kv_token_decode``): the per-position
+    parameter store; the entry point then takes the query's two pointers in the place of the two tables, and the store's strides at the
+    end of a table of fifteen."""
     B, H, HKV, L, E, rows = shape
     deq_s, deq_o, out_s, out_o, bits, keep = _decode_tables(dequant, output_quantizer)
     lib, stream = _base._prepare(query, k, v, *others, *keep)
@@ -124,10 +126,14 @@ def _run_decode(symbol: str, query: torch.Tensor, k: torch.Tensor, v: torch.Tens
     count, nbytes, workspace = _split_workspace(B, HKV, rows, E, plan_keys, splits, query.device)
     out = torch.empty((B, H, L, E), dtype=dt, device=query.device)
     strides = (ctypes.c_int64 * 9)(*_strides(query), *_strides(k), *_strides(v))
+    tables: tuple = (deq_s, deq_o)
+    if row_params is not None:
+        strides = (ctypes.c_int64 * 15)(*strides, 0, 0, 0, *_strides(row_params))
+        tables = (deq_s[0], deq_o[0])
     sqrt_scale = math.sqrt(1.0 / math.sqrt(E) if scale is None else scale)  # the math path's scale_factor_sqrt
     lib.check(
         entry(
-            _ptr(query), _tag(query.dtype), _ptr(k), _ptr(v), _tag(dt), deq_s, deq_o, *extents, strides, *selection, sqrt_scale, _ptr(out_s),
+            _ptr(query), _tag(query.dtype), _ptr(k), _ptr(v), _tag(dt), *tables, *extents, strides, *selection, sqrt_scale, _ptr(out_s),
             _ptr(out_o), bits, *(split_args or (count,)), _ptr(out), _ptr(workspace), nbytes, stream,
         )
     )

@@ -8,7 +8,12 @@ neither: the caller advances it with ``lens.add_(L)`` on the stream ahead of ``k
 
 ``kv_paged_append`` / ``kv_paged_decode`` (include/ffq_kv_paged.h) are the same two calls over K / V held in fixed-size pages: two
 pools ``[num_pages, H, P, E]`` shared by every sequence and an int32 block table ``[B, max_pages]`` on the device, read by the kernels
-and never on the host. The codes and the attention's bits are those of the dense calls."""
+and never on the host. The codes and the attention's bits are those of the dense calls.
+
+``kv_token_append`` / ``kv_token_decode`` (include/ffq_kv_token.h) are the dense calls with one DYNAMIC ``(scale, offset)`` per
+(sequence, kv head, position) for K and for V, kept in an fp32 store ``[B, H, S_max, 4]`` beside the codes: the append computes them on
+the device from every new row's own min / max (the codes and parameters of ``quantize_dynamic_by_tile`` with the tile ``(1, 1, 1, E)``),
+the decode reads them back per key row."""
 
 from __future__ import annotations
 
@@ -25,6 +30,7 @@ from fastforward_amd.ops.modules import _entry
 from fastforward_amd.ops.sdpa import _scalar, _strides
 
 Quantizer = tuple[torch.Tensor, "torch.Tensor | None", float]
+Spec = tuple[float, bool]  # (num_bits, symmetric) of a dynamic per-row quantizer
 
 
 def _lens_ok(lens: torch.Tensor, B: int) -> bool:
@@ -43,6 +49,22 @@ def _quantizer_args(name: str, k_quantizer: Quantizer, v_quantizer: Quantizer) -
         keep += [t for t in (s, o) if t is not None]
         params += [_ptr(s), _ptr(o), bits]
     return params, keep
+
+
+def _spec_args(name: str, k_spec: Spec, v_spec: Spec) -> list:
+    """[k bits, k symmetric, v bits, v symmetric] as ``ffq_kv_token_append`` takes them."""
+    args: list = []
+    for spec, what in ((k_spec, "key"), (v_spec, "value")):
+        bits = float(spec[0])
+        if not (2 <= bits <= 8 and bits == int(bits)):
+            raise RuntimeError(f"{name}: the {what} quantizer needs an integral bit-width in 2..8, got {bits}")
+        args += [bits, int(bool(spec[1]))]
+    return args
+
+
+def _params_ok(params: torch.Tensor, B: int, HKV: int, S_max: int) -> bool:
+    return (params.dtype == torch.float32 and tuple(params.shape) == (B, HKV, S_max, 4) and params.stride(3) == 1
+            and not any(st % 4 for st in _strides(params)) and params.data_ptr() % 16 == 0)
 
 
 def _rope_tables(name: str, rope: tuple[torch.Tensor, torch.Tensor] | None, dt: torch.dtype, rows: int, E: int):
@@ -94,16 +116,23 @@ def _check_new_rows(name: str, k_new: torch.Tensor, v_new: torch.Tensor, k_store
 
 
 def _run_append(name: str, k_new: torch.Tensor, v_new: torch.Tensor, k_store: torch.Tensor, v_store: torch.Tensor, tables: Sequence[torch.Tensor],
-                capacity: int, k_quantizer: Quantizer, v_quantizer: Quantizer, rope: tuple[torch.Tensor, torch.Tensor] | None, extents: tuple) -> None:
-    """The tail of both append wrappers, after their checks: the rotary tables (`capacity` rows), the quantizers, the library and the
-    call of ``ffq_<name>``. `tables` are the entry point's int32 tensors (lens; lens and the block table), `extents` its arguments
-    between them and the strides."""
+                capacity: int, k_quantizer: Quantizer | Spec, v_quantizer: Quantizer | Spec, rope: tuple[torch.Tensor, torch.Tensor] | None,
+                extents: tuple, row_params: torch.Tensor | None = None) -> None:
+    """The tail of the append wrappers, after their checks: the rotary tables (`capacity` rows), the quantizers, the library and the
+    call of ``ffq_<name>``. `tables` are the entry point's tensors between the stores and the extents (lens; lens and the block table;
+    the parameter store and lens), `extents` its arguments between them and the strides. `row_params` (``kv_token_append``): the
+    parameter store, whose strides end the table; the quantizers are then ``(num_bits, symmetric)`` specs."""
     dt, E = k_new.dtype, k_new.shape[3]
     cos, sin = _rope_tables(name, rope, dt, capacity, E)
-    params, keep = _quantizer_args(name, k_quantizer, v_quantizer)
+    if row_params is None:
+        params, keep = _quantizer_args(name, k_quantizer, v_quantizer)
+    else:
+        params, keep = _spec_args(name, k_quantizer, v_quantizer), []
     lib, stream = _base._prepare(k_new, v_new, k_store, v_store, *tables, cos, sin, *keep)
     entry = _entry(lib, f"ffq_{name}")
     strides = (ctypes.c_int64 * 12)(*_strides(k_new), *_strides(v_new), *_strides(k_store), *_strides(v_store))
+    if row_params is not None:
+        strides = (ctypes.c_int64 * 15)(*strides, *_strides(row_params))
     lib.check(
         entry(
             _ptr(k_new), _ptr(v_new), _tag(dt), _ptr(k_store), _ptr(v_store), *(_ptr(t) for t in tables), *extents, strides, *params, _ptr(cos),
@@ -114,6 +143,8 @@ def _run_append(name: str, k_new: torch.Tensor, v_new: torch.Tensor, k_store: to
     # written through raw pointers: tell the version counters
     torch.autograd.graph.increment_version(k_store)
     torch.autograd.graph.increment_version(v_store)
+    if row_params is not None:
+        torch.autograd.graph.increment_version(row_params)
 
 
 def kv_append(
@@ -243,3 +274,74 @@ def kv_paged_decode(
     return _run_decode("ffq_kv_paged_decode", query, k_pool, v_pool, (lens, block_table), dt, (B, H, HKV, L, E, rows), plan_len or C, splits, scale,
                        dequant, output_quantizer, (_ptr(lens), _ptr(block_table), B, H, HKV, L, num_pages, P, max_pages, table_stride, E),
                        (int(bool(is_causal)),), (splits, plan_len or 0))
+
+
+def kv_token_append(
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    params: torch.Tensor,
+    lens: torch.Tensor,
+    k_spec: Spec,
+    v_spec: Spec,
+    rope: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> None:
+    """One call of ``ffq_kv_token_append``: :func:`kv_append` with a dynamic quantizer per row. The operands are :func:`kv_append`'s;
+    `params` is fp32 ``[B, H, S_max, 4]`` (the last dimension contiguous, positions 16-byte aligned, any other strides) and receives
+    ``(k_scale, k_offset, v_scale, v_offset)`` of every row written; ``k_spec`` / ``v_spec`` are ``(num_bits, symmetric)``, 2..8 bits.
+    The codes and the parameters of a row are those of ``quantize_dynamic_by_tile(row, (1, 1, 1, E), num_bits, symmetric, False,
+    torch.int8)``, K rotated first with ``rope``. A row outside ``[0, S_max)`` is skipped and its parameters stay as they were."""
+    name = "kv_token_append"
+    if k_new.dim() != 4 or v_new.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise RuntimeError(f"{name}: the new rows and the caches are 4-D [B, H, L|S_max, E]")
+    if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8:
+        raise RuntimeError(f"{name}: the caches hold int8 codes, got {k_cache.dtype}, {v_cache.dtype}")
+    (B, HKV, L, E), S_max = k_new.shape, k_cache.shape[2]
+    if tuple(v_new.shape) != (B, HKV, L, E) or tuple(k_cache.shape) != (B, HKV, S_max, E) or tuple(v_cache.shape) != (B, HKV, S_max, E):
+        raise RuntimeError(f"{name}: shapes {tuple(k_new.shape)}, {tuple(v_new.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)} do not fit")
+    if not _params_ok(params, B, HKV, S_max):
+        raise RuntimeError(f"{name}: params is fp32 [{B}, {HKV}, {S_max}, 4] with 16-byte aligned positions, got {params.dtype} {tuple(params.shape)}")
+    _check_new_rows(name, k_new, v_new, k_cache, v_cache, lens)
+    _run_append(name, k_new, v_new, k_cache, v_cache, (params, lens), S_max, k_spec, v_spec, rope, (B, HKV, L, S_max, E), row_params=params)
+
+
+def kv_token_decode(
+    query: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    params: torch.Tensor,
+    lens: torch.Tensor,
+    is_causal: bool = False,
+    scale: float | None = None,
+    output_quantizer: tuple[torch.Tensor, torch.Tensor | None, float] | None = None,
+    q_dequant: Dequant | None = None,
+    dtype: torch.dtype | None = None,
+    splits: int = 0,
+    plan_len: int | None = None,
+) -> torch.Tensor:
+    """One call of ``ffq_kv_token_decode``: :func:`kv_decode` over codes whose ``(scale, offset)`` live per position in `params` (fp32
+    ``[B, H, S_max, 4]``, as :func:`kv_token_append` writes them). ``q_dequant`` is the query's own ``(scale, offset)`` when it holds
+    codes. Lengths, causality, ``splits`` / ``plan_len``, the output quantizer and the exact zeros are :func:`kv_decode`'s; with every
+    position's parameters equal the result is bit-equal to it."""
+    name = "kv_token_decode"
+    if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise RuntimeError(f"{name}: q / k / v are 4-D [B, H, L|S_max, E]")
+    if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8:
+        raise RuntimeError(f"{name}: k / v are int8 codes, got {k_cache.dtype}, {v_cache.dtype}")
+    S_max = k_cache.shape[2]
+    dequant = (q_dequant, None, None)
+    dt, B, H, L, E, HKV, rows = _check_decode(name, query, k_cache, v_cache, dequant, dtype, k_cache.shape[1], splits)
+    if k_cache.shape[0] != B or k_cache.shape[3] != E or tuple(v_cache.shape) != (B, HKV, S_max, E):
+        raise RuntimeError(f"{name}: shapes {tuple(query.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)} do not fit")
+    if min(B, L, S_max) < 1:
+        raise RuntimeError(f"{name}: empty operands {tuple(query.shape)}, {tuple(k_cache.shape)}")
+    if not _params_ok(params, B, HKV, S_max):
+        raise RuntimeError(f"{name}: params is fp32 [{B}, {HKV}, {S_max}, 4] with 16-byte aligned positions, got {params.dtype} {tuple(params.shape)}")
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    if plan_len is not None and not 1 <= plan_len <= S_max:
+        raise RuntimeError(f"{name}: plan_len is a key count in 1..{S_max}, got {plan_len}")
+    return _run_decode("ffq_kv_token_decode", query, k_cache, v_cache, (params, lens), dt, (B, H, HKV, L, E, rows), plan_len or S_max, splits, scale,
+                       dequant, output_quantizer, (_ptr(params), _ptr(lens), B, H, HKV, L, S_max, E), (int(bool(is_causal)),), (splits, plan_len or 0),
+                       row_params=params)
