@@ -15,6 +15,7 @@
 #define FFQ_NT_STREAMS 1  // nt loads (ffq_vec.h)
 #endif
 #include "ffq_common.h"
+#include "ffq_quantizer_host.h"
 #include "ffq_vec.h"
 
 #include <math.h>
@@ -225,65 +226,54 @@ extern "C" int ffq_quantize_by_tile_backward(const void* data, const void* outpu
   TileInfo info;
   int rc = analyse(tiling, &info);
   if (rc) return rc;
-  if (!(dt == FFQ_F32 || dt == FFQ_BF16 || dt == FFQ_F16)) return fail(FFQ_ERR_DTYPE, "backward is built for f32 / bf16 / f16 data");
-  if (info.numel != 0) {
-    if ((rc = check_param_numel("scale", scale_numel, info.ntiles))) return rc;
-    if (offset && (rc = check_param_numel("offset", offset_numel, info.ntiles))) return rc;
-  }
+  if (!is_f32_bf16_f16(dt)) return fail(FFQ_ERR_DTYPE, "backward is built for f32 / bf16 / f16 data");
+  if ((rc = check_param_counts(info, scale_numel, offset != nullptr, offset_numel))) return rc;
   if (info.numel == 0) return FFQ_OK;
-  if (!data || !output_grad || !scale || !dinput || !dscale) return fail(FFQ_ERR_ARG, "NULL buffer");
+  if ((rc = check_buffers({data, output_grad, scale, dinput, dscale}))) return rc;
   if (offset && !doffset) return fail(FFQ_ERR_ARG, "doffset is required when offset is given");
   uint32_t nchunks, units, nparts;
   int per_block;
-  const double lo_d = -pow(2.0, num_bits - 1.0);
+  const ClampBounds bounds = clamp_bounds(num_bits);
+  const float lo = (float)bounds.lo, hi = (float)bounds.hi;
+  const uint32_t ss = param_stride(scale_numel), os = param_stride(offset_numel);
   // small problems of a few tiles (an eager quantizer of a small model: the host pays per launch, bench.py host_us_per_op) take the by-tile
   // kernel as well: ONE launch instead of the streaming pass + its finalize (round 6: 11.8 us per call on the host with two launches)
   const bool small = backward_small(info);
-  if (small || !backward_plan(info, &nchunks, &per_block, &units, &nparts) || !aligned16(data) || !aligned16(output_grad) || !aligned16(dinput) ||
+  if (small || !backward_plan(info, &nchunks, &per_block, &units, &nparts) || !aligned16(data, output_grad) || !aligned16(dinput) ||
       (scale_numel == 1 && info.ntiles != 1)) {
     // strided channels, N-d tiles, odd sizes, broadcast parameters: the by-tile kernel
     const TileWalk w = make_tile_walk(tiling);
     const int lane_per_tile = w.tile_elems < 64;
     const int64_t blocks = lane_per_tile ? (info.ntiles + kBlock - 1) / kBlock : info.ntiles;
     if (blocks >= ((int64_t)1 << 31)) return fail(FFQ_ERR_DTYPE, "too many tiles for the by-tile backward kernel");
-    const uint32_t ss = scale_numel == 1 ? 0u : 1u, os = offset_numel == 1 ? 0u : 1u;
-#define FFQ_BWD_TILES(T)                                                                                             \
-  do {                                                                                                               \
-    if (offset) quantize_backward_tiles_kernel<T, true><<<(unsigned)blocks, kBlock, 0, s>>>(static_cast<const T*>(data), static_cast<const T*>(output_grad), static_cast<T*>(dinput), scale, offset, dscale, doffset, w, info.ntiles, (float)lo_d, (float)(-lo_d - 1.0), ss, os, lane_per_tile); \
-    else quantize_backward_tiles_kernel<T, false><<<(unsigned)blocks, kBlock, 0, s>>>(static_cast<const T*>(data), static_cast<const T*>(output_grad), static_cast<T*>(dinput), scale, offset, dscale, doffset, w, info.ntiles, (float)lo_d, (float)(-lo_d - 1.0), ss, os, lane_per_tile); \
-  } while (0)
-    switch (dt) {
-      case FFQ_F32: FFQ_BWD_TILES(float); break;
-      case FFQ_BF16: FFQ_BWD_TILES(bf16_t); break;
-      default: FFQ_BWD_TILES(f16_t); break;
-    }
-#undef FFQ_BWD_TILES
+    for_float_dtype(dt, [&](auto t) {
+      using T = typename decltype(t)::type;
+      const T* x = static_cast<const T*>(data);
+      const T* g = static_cast<const T*>(output_grad);
+      if (offset) quantize_backward_tiles_kernel<T, true><<<(unsigned)blocks, kBlock, 0, s>>>(x, g, static_cast<T*>(dinput), scale, offset, dscale, doffset, w, info.ntiles, lo, hi, ss, os, lane_per_tile);
+      else quantize_backward_tiles_kernel<T, false><<<(unsigned)blocks, kBlock, 0, s>>>(x, g, static_cast<T*>(dinput), scale, offset, dscale, doffset, w, info.ntiles, lo, hi, ss, os, lane_per_tile);
+    });
     return check_launch("quantize_backward_tiles_kernel");
   }
   const size_t need = (size_t)nparts * sizeof(Partial2);
   if (!workspace || workspace_bytes < need) return fail(FFQ_ERR_WORKSPACE, "backward needs %zu workspace bytes, got %zu", need, workspace_bytes);
   BwdArgs a;
-  const double lo = -pow(2.0, num_bits - 1.0);
-  a.lo = (float)lo; a.hi = (float)(-lo - 1.0);
+  a.lo = lo; a.hi = hi;
   a.nchunks = nchunks;
-  a.scale_stride = scale_numel == 1 ? 0u : 1u;
-  a.offset_stride = offset_numel == 1 ? 0u : 1u;
+  a.scale_stride = ss;
+  a.offset_stride = os;
   a.rows = info.layout == LAYOUT_ROWS;
   a.chunks_per_run = make_fastdiv(a.rows ? (uint32_t)(info.run / 8) : 1u);
   a.per_block = per_block;
   Partial2* parts = static_cast<Partial2*>(workspace);
   const unsigned grid = (nchunks + kBlock - 1) / kBlock;
-#define FFQ_BWD(T)                                                                                                   \
-  do {                                                                                                               \
-    if (offset) quantize_backward_kernel<T, true><<<grid, kBlock, 0, s>>>(static_cast<const T*>(data), static_cast<const T*>(output_grad), static_cast<T*>(dinput), scale, offset, parts, a); \
-    else quantize_backward_kernel<T, false><<<grid, kBlock, 0, s>>>(static_cast<const T*>(data), static_cast<const T*>(output_grad), static_cast<T*>(dinput), scale, offset, parts, a); \
-  } while (0)
-  switch (dt) {
-    case FFQ_F32: FFQ_BWD(float); break;
-    case FFQ_BF16: FFQ_BWD(bf16_t); break;
-    default: FFQ_BWD(f16_t); break;
-  }
-#undef FFQ_BWD
+  for_float_dtype(dt, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const T* x = static_cast<const T*>(data);
+    const T* g = static_cast<const T*>(output_grad);
+    if (offset) quantize_backward_kernel<T, true><<<grid, kBlock, 0, s>>>(x, g, static_cast<T*>(dinput), scale, offset, parts, a);
+    else quantize_backward_kernel<T, false><<<grid, kBlock, 0, s>>>(x, g, static_cast<T*>(dinput), scale, offset, parts, a);
+  });
   if ((rc = check_launch("quantize_backward_kernel"))) return rc;
   const uint32_t ntiles = (uint32_t)info.ntiles;
   if (units <= 32)

@@ -8,9 +8,8 @@
 // The add and the multiply are two separately rounded fp32 operations (no FMA), and `q + 0.0f` is
 // kept when there is no offset because it turns -0.0 into +0.0 exactly like the eager chain.
 #include "ffq_common.h"
+#include "ffq_quantizer_host.h"
 #include "ffq_vec.h"
-
-#include <stdlib.h>
 
 namespace ffq {
 
@@ -160,185 +159,111 @@ __global__ __launch_bounds__(kBlock) void dequantize_generic_kernel(const void* 
 }
 
 template <typename TIn, typename TOut, int E, int U>
-static int dq_launch_stream_u(const TIn* in, TOut* out, const float* scale, int64_t scale_numel,
-                              const float* offset, int64_t offset_numel, const TileInfo& info,
-                              hipStream_t stream) {
-  DqStreamArgs a;
-  a.nchunks = (uint32_t)(info.numel / E);
-  a.scale_stride = scale_numel == 1 ? 0u : 1u;
-  a.offset_stride = offset_numel == 1 ? 0u : 1u;
-  a.chunks_per_run = make_fastdiv(1);
-  a.channels = make_fastdiv(1);
-  const unsigned grid = (unsigned)((a.nchunks + kBlock * U - 1) / (kBlock * U));
-  const dim3 block(kBlock);
+static int dq_launch_stream_u(const AffineCall& c) {
+  const DqStreamArgs a = stream_args<DqStreamArgs>(c, E);
+  const unsigned grid = grid_for(a.nchunks, kBlock * U);
+  const TIn* in = static_cast<const TIn*>(c.data);
+  TOut* out = static_cast<TOut*>(c.out);
+  const float* scale = static_cast<const float*>(c.scale);
+  const float* offset = static_cast<const float*>(c.offset);
 #define FFQ_LAUNCH(LAYOUT)                                                                             \
   do {                                                                                                 \
     if (offset)                                                                                        \
-      dequantize_stream_kernel<TIn, TOut, LAYOUT, E, U, true><<<grid, block, 0, stream>>>(in, out, scale, offset, a); \
+      dequantize_stream_kernel<TIn, TOut, LAYOUT, E, U, true><<<grid, kBlock, 0, c.stream>>>(in, out, scale, offset, a); \
     else                                                                                               \
-      dequantize_stream_kernel<TIn, TOut, LAYOUT, E, U, false><<<grid, block, 0, stream>>>(in, out, scale, offset, a); \
+      dequantize_stream_kernel<TIn, TOut, LAYOUT, E, U, false><<<grid, kBlock, 0, c.stream>>>(in, out, scale, offset, a); \
   } while (0)
-  switch (info.layout) {
+  switch (c.info.layout) {
     case LAYOUT_SCALAR: FFQ_LAUNCH(LAYOUT_SCALAR); break;
-    case LAYOUT_ROWS:
-      a.chunks_per_run = make_fastdiv((uint32_t)(info.run / E));
-      FFQ_LAUNCH(LAYOUT_ROWS);
-      break;
-    default:
-      a.chunks_per_run = make_fastdiv((uint32_t)(info.inner / E));
-      a.channels = make_fastdiv((uint32_t)info.channels);
-      FFQ_LAUNCH(LAYOUT_CHANNEL);
-      break;
+    case LAYOUT_ROWS: FFQ_LAUNCH(LAYOUT_ROWS); break;
+    default: FFQ_LAUNCH(LAYOUT_CHANNEL); break;
   }
 #undef FFQ_LAUNCH
   return check_launch("dequantize_stream_kernel");
 }
 
-// chunks per lane: short blocks win on MI355X (same finding as ffq_quantize.hip::launch_stream)
 template <typename TIn, typename TOut, int E>
-static int dq_launch_stream(const TIn* in, TOut* out, const float* scale, int64_t scale_numel,
-                            const float* offset, int64_t offset_numel, const TileInfo& info,
-                            hipStream_t stream) {
-#ifdef FFQ_EXPERIMENTS  // 2 / 4 chunks per lane: tuning builds only (the product instantiates the one form it launches)
-  int u = 1;
-  if (const char* e = getenv("FFQ_STREAM_U")) u = atoi(e) ? atoi(e) : 1;
-  switch (u) {
-    case 1: return dq_launch_stream_u<TIn, TOut, E, 1>(in, out, scale, scale_numel, offset, offset_numel, info, stream);
-    case 4: return dq_launch_stream_u<TIn, TOut, E, 4>(in, out, scale, scale_numel, offset, offset_numel, info, stream);
-    default: return dq_launch_stream_u<TIn, TOut, E, 2>(in, out, scale, scale_numel, offset, offset_numel, info, stream);
+static int dq_launch_stream(const AffineCall& c) {
+  if constexpr (kExperiments) {
+    switch (stream_chunks_per_lane()) {
+      case 1: return dq_launch_stream_u<TIn, TOut, E, 1>(c);
+      case 4: return dq_launch_stream_u<TIn, TOut, E, 4>(c);
+      default: return dq_launch_stream_u<TIn, TOut, E, 2>(c);
+    }
+  } else {
+    return dq_launch_stream_u<TIn, TOut, E, 1>(c);
   }
-#else
-  return dq_launch_stream_u<TIn, TOut, E, 1>(in, out, scale, scale_numel, offset, offset_numel, info, stream);
-#endif
 }
 
 template <typename TIn, typename TOut, int E>
-static int dq_launch_columns(const TIn* in, TOut* out, const float* scale, int64_t scale_numel,
-                             const float* offset, int64_t offset_numel, const TileInfo& info,
-                             hipStream_t stream) {
-  DqColumnArgs a;
-  a.col_chunks = (uint32_t)(info.channels / E);
-  a.rows = (uint32_t)(info.numel / info.channels);
-  a.scale_stride = scale_numel == 1 ? 0u : 1u;
-  a.offset_stride = offset_numel == 1 ? 0u : 1u;
-  a.col_chunks_div = make_fastdiv(a.col_chunks);
-  uint32_t groups = (a.rows + 7) / 8;
-  if (groups < 1) groups = 1;
-  a.row_groups = groups;
-  const uint64_t lanes = (uint64_t)groups * a.col_chunks;
-  const unsigned grid = (unsigned)((lanes + kBlock - 1) / kBlock);
+static int dq_launch_columns(const AffineCall& c) {
+  const DqColumnArgs a = affine_column_args<DqColumnArgs>(c, E);
+  const TIn* in = static_cast<const TIn*>(c.data);
+  TOut* out = static_cast<TOut*>(c.out);
+  const float* scale = static_cast<const float*>(c.scale);
+  const float* offset = static_cast<const float*>(c.offset);
   if (offset)
-    dequantize_columns_kernel<TIn, TOut, E, true><<<grid, dim3(kBlock), 0, stream>>>(in, out, scale, offset, a);
+    dequantize_columns_kernel<TIn, TOut, E, true><<<column_grid(a), kBlock, 0, c.stream>>>(in, out, scale, offset, a);
   else
-    dequantize_columns_kernel<TIn, TOut, E, false><<<grid, dim3(kBlock), 0, stream>>>(in, out, scale, offset, a);
+    dequantize_columns_kernel<TIn, TOut, E, false><<<column_grid(a), kBlock, 0, c.stream>>>(in, out, scale, offset, a);
   return check_launch("dequantize_columns_kernel");
 }
 
-template <typename TIn, typename TOut, int E>
-static int dq_dispatch_fast_e(const void* data, const void* scale, int64_t scale_numel, const void* offset,
-                              int64_t offset_numel, const TileInfo& info, void* out, hipStream_t stream,
-                              int64_t* done) {
-  *done = 0;
-  const TIn* in = static_cast<const TIn*>(data);
-  TOut* o = static_cast<TOut*>(out);
-  const float* s = static_cast<const float*>(scale);
-  const float* f = static_cast<const float*>(offset);
-  if (info.layout == LAYOUT_SCALAR || (info.layout == LAYOUT_ROWS && info.run % E == 0) ||
-      (info.layout == LAYOUT_CHANNEL && info.inner % E == 0)) {
-    if (info.numel / E == 0) return FFQ_OK;
-    *done = info.layout == LAYOUT_SCALAR ? (info.numel / E) * E : info.numel;
-    return dq_launch_stream<TIn, TOut, E>(in, o, s, scale_numel, f, offset_numel, info, stream);
-  }
-  return FFQ_OK;
-}
-
+// the kernel stream_route() chose, on the types of this call; 16-code chunks exist in tuning builds only (FFQ_DQ_E16)
 template <typename TIn, typename TOut>
-static int dq_dispatch_fast(const void* data, const void* scale, int64_t scale_numel, const void* offset,
-                            int64_t offset_numel, const TileInfo& info, void* out, hipStream_t stream,
-                            int64_t* done) {
-  *done = 0;
-  if (info.numel >= ((int64_t)1 << 32) - 4096) return FFQ_OK;
-  if (!aligned16(data) || !aligned16(out)) return FFQ_OK;
-  int rc = FFQ_OK;
-  // 8 codes per chunk: an 8 B load and ONE dense 16 B store per lane beats 16 codes per chunk (16 B
-  // load, two half-dense 16 B stores): 30.1 vs 32.1 us on [14336, 4096] int8 -> bf16 (FFQ_DQ_E16=1 to compare)
-#ifdef FFQ_EXPERIMENTS
-  const char* e16 = getenv("FFQ_DQ_E16");
-  if (sizeof(TIn) == 1 && e16 && e16[0] == '1') {
-    rc = dq_dispatch_fast_e<TIn, TOut, 16>(data, scale, scale_numel, offset, offset_numel, info, out, stream, done);
-    if (rc || *done) return rc;
+static int dq_launch_route(const AffineCall& c, const StreamRoute& route) {
+  if (route.kernel == ROUTE_STREAM) {
+    if constexpr (kExperiments && sizeof(TIn) == 1) {
+      if (route.chunk == 16) return dq_launch_stream<TIn, TOut, 16>(c);
+    }
+    return dq_launch_stream<TIn, TOut, 8>(c);
   }
-#endif
-  rc = dq_dispatch_fast_e<TIn, TOut, 8>(data, scale, scale_numel, offset, offset_numel, info, out, stream, done);
-  if (rc || *done) return rc;
-  if (info.layout == LAYOUT_CHANNEL && info.inner == 1 && info.channels % 8 == 0) {
-    *done = info.numel;
-    return dq_launch_columns<TIn, TOut, 8>(static_cast<const TIn*>(data), static_cast<TOut*>(out),
-                                           static_cast<const float*>(scale), scale_numel,
-                                           static_cast<const float*>(offset), offset_numel, info, stream);
-  }
-  return FFQ_OK;
-}
-
-template <typename TIn>
-static int dq_dispatch_out(int out_dt, const void* data, const void* scale, int64_t scale_numel,
-                           const void* offset, int64_t offset_numel, const TileInfo& info, void* out,
-                           hipStream_t stream, int64_t* done) {
-  switch (out_dt) {
-    case FFQ_F32: return dq_dispatch_fast<TIn, float>(data, scale, scale_numel, offset, offset_numel, info, out, stream, done);
-    case FFQ_BF16: return dq_dispatch_fast<TIn, bf16_t>(data, scale, scale_numel, offset, offset_numel, info, out, stream, done);
-    case FFQ_F16: return dq_dispatch_fast<TIn, f16_t>(data, scale, scale_numel, offset, offset_numel, info, out, stream, done);
-    default: *done = 0; return FFQ_OK;
-  }
+  return dq_launch_columns<TIn, TOut, 8>(c);
 }
 
 int dequantize_impl(const void* data, int data_dt, const void* scale, int scale_dt, int64_t scale_numel,
                     const void* offset, int offset_dt, int64_t offset_numel, const ffq_tiling* tiling,
                     void* out, int out_dt, hipStream_t stream) {
-  TileInfo info;
-  int rc = analyse(tiling, &info);
+  AffineCall c;
+  int rc = analyse(tiling, &c.info);
   if (rc) return rc;
-  if (!dt_valid(data_dt) || !dt_valid(scale_dt) || !dt_valid(out_dt) || (offset && !dt_valid(offset_dt)))
-    return fail(FFQ_ERR_ARG, "bad dtype tag");
-  if (info.numel != 0) {
-    if ((rc = check_param_numel("scale", scale_numel, info.ntiles))) return rc;
-    if (offset && (rc = check_param_numel("offset", offset_numel, info.ntiles))) return rc;
-  }
   const int off_dt = offset ? offset_dt : scale_dt;
+  if ((rc = check_tags({data_dt, scale_dt, out_dt, off_dt}))) return rc;
+  if ((rc = check_param_counts(c.info, scale_numel, offset != nullptr, offset_numel))) return rc;
   // (row + offset[:, None]) * scale[:, None]                                           (:182)
   const int add_dt = ffq_promote_types(data_dt, off_dt);
   const int mul_dt = ffq_promote_types(add_dt, scale_dt);
   if (!dt_is_float(mul_dt)) return fail(FFQ_ERR_DTYPE, "integer-only dequantize is not built");
-  if (info.numel == 0) return FFQ_OK;
-  if (!data || !scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
+  if (c.info.numel == 0) return FFQ_OK;
+  if ((rc = check_buffers({data, scale, out}))) return rc;
+  c.data = data; c.scale = scale; c.offset = offset; c.out = out;
+  c.scale_numel = scale_numel; c.offset_numel = offset_numel;
+  c.lo = c.hi = 0.0f;
+  c.stream = stream;
 
-  const bool fast_types = add_dt == FFQ_F32 && mul_dt == FFQ_F32 && scale_dt == FFQ_F32 &&
-                          (!offset || offset_dt == FFQ_F32) && !generic_kernels_forced();
+  // the streaming kernels: fp32 stages + fp32 parameters on a route stream_route() finds; everything else goes to the generic kernel
   int64_t done = 0;
-  if (fast_types) {
-    switch (data_dt) {
-      case FFQ_I8: rc = dq_dispatch_out<int8_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, out, stream, &done); break;
-      case FFQ_I16: rc = dq_dispatch_out<int16_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, out, stream, &done); break;
-      case FFQ_I32: rc = dq_dispatch_out<int32_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, out, stream, &done); break;
-      case FFQ_F32: rc = dq_dispatch_out<float>(out_dt, data, scale, scale_numel, offset, offset_numel, info, out, stream, &done); break;
-      case FFQ_BF16: rc = dq_dispatch_out<bf16_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, out, stream, &done); break;
-      case FFQ_F16: rc = dq_dispatch_out<f16_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, out, stream, &done); break;
-      default: break;
-    }
+  if (add_dt == FFQ_F32 && mul_dt == FFQ_F32 && scale_dt == FFQ_F32 && off_dt == FFQ_F32) {
+    const StreamRoute route = stream_route(c.info, {dt_size(data_dt), dt_size(out_dt), aligned16(data), aligned16(out), generic_kernels_forced(),
+                                                    experiment_knob("FFQ_DQ_E16", 0) == 1});
+    bool launched = false;
+    if (route.kernel != ROUTE_NONE)
+      for_dtype<int8_t, int16_t, int32_t, float, bf16_t, f16_t>(data_dt, [&](auto tin) {
+        using TIn = typename decltype(tin)::type;
+        launched = for_float_dtype(out_dt, [&](auto tout) { rc = dq_launch_route<TIn, typename decltype(tout)::type>(c, route); });
+      });
     if (rc) return rc;
+    if (launched) done = route.covered;
   }
-  const int64_t rest = info.numel - done;
-  if (rest <= 0) return FFQ_OK;
+  if (done >= c.info.numel) return FFQ_OK;
   DqGenericArgs a;
   a.data_dt = data_dt; a.scale_dt = scale_dt; a.offset_dt = offset_dt; a.out_dt = out_dt;
   a.add_dt = add_dt; a.mul_dt = mul_dt;
   a.has_offset = offset != nullptr;
-  a.start = done; a.count = rest;
+  a.start = done; a.count = c.info.numel - done;
   a.scale_numel = scale_numel; a.offset_numel = offset_numel;
   a.g = make_generic(tiling);
-  int64_t blocks = (rest + kBlock - 1) / kBlock;
-  if (blocks > 8192) blocks = 8192;
-  dequantize_generic_kernel<<<dim3((unsigned)blocks), dim3(kBlock), 0, stream>>>(data, scale, offset, out, a);
+  dequantize_generic_kernel<<<generic_grid(a.count), kBlock, 0, stream>>>(data, scale, offset, out, a);
   return check_launch("dequantize_generic_kernel");
 }
 

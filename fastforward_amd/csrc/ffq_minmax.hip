@@ -17,10 +17,10 @@
 #include "ffq_affine.h"
 #include "ffq_common.h"
 #include "ffq_extrema.h"
+#include "ffq_quantizer_host.h"
 #include "ffq_vec.h"
 
 #include <math.h>
-#include <stdlib.h>
 
 namespace ffq {
 
@@ -484,8 +484,7 @@ static MinMaxPlan plan_for(const TileInfo& info, int data_dt) {
   p.lanes_per_tile = 0;
   p.partials = 0;
   p.workspace = sizeof(GenericCell) * (size_t)info.ntiles;
-  const bool fast_dt = data_dt == FFQ_F32 || data_dt == FFQ_BF16 || data_dt == FFQ_F16;
-  if (!fast_dt || info.numel >= ((int64_t)1 << 32) - 4096 || generic_kernels_forced()) return p;
+  if (!is_f32_bf16_f16(data_dt) || !fits_chunk_index(info.numel) || generic_kernels_forced()) return p;
   if (info.layout == LAYOUT_SCALAR) {
     const uint32_t nchunks = (uint32_t)(info.numel / kE);
     uint32_t blocks = (nchunks + kBlock * 4 - 1) / (kBlock * 4);
@@ -517,10 +516,7 @@ static MinMaxPlan plan_for(const TileInfo& info, int data_dt) {
     return p;
   }
   if (info.layout == LAYOUT_CHANNEL && info.inner == 1 && info.channels % kE == 0) {
-    const uint32_t rows = (uint32_t)(info.numel / info.channels);
-    uint32_t groups = (rows + 15) / 16;
-    if (groups > 64) groups = 64;
-    if (groups < 1) groups = 1;
+    const uint32_t groups = row_groups(column_rows(info), 16, 64);  // 16 rows per lane, at most 64 Partials per channel
     p.plan = PLAN_COLUMNS;
     p.partials = groups;
     p.workspace = sizeof(Partial) * (size_t)groups * (size_t)info.channels;
@@ -591,13 +587,8 @@ static int run_fast(const MinMaxPlan& p, const TileInfo& info, const void* data,
       break;
     }
     default: {  // PLAN_COLUMNS
-      ColsArgs a;
-      a.col_chunks = (uint32_t)(info.channels / kE);
-      a.rows = (uint32_t)(info.numel / info.channels);
-      a.row_groups = p.partials;
-      a.col_chunks_div = make_fastdiv(a.col_chunks);
-      const uint64_t lanes = (uint64_t)a.row_groups * a.col_chunks;
-      minmax_columns_partial_kernel<T, kE><<<(unsigned)((lanes + kBlock - 1) / kBlock), kBlock, 0, stream>>>(in, partial, a);
+      const ColsArgs a = column_args<ColsArgs>(info, kE, p.partials);
+      minmax_columns_partial_kernel<T, kE><<<column_grid(a), kBlock, 0, stream>>>(in, partial, a);
       minmax_finalize_kernel<T><<<(unsigned)((info.channels + 3) / 4), kBlock, 0, stream>>>(
           partial, (uint32_t)info.channels, p.partials, mn_out, mx_out, accumulate, flags);
       break;
@@ -612,29 +603,24 @@ static int minmax_impl(const void* data, int data_dt, const ffq_tiling* tiling, 
   TileInfo info;
   int rc = analyse(tiling, &info);
   if (rc) return rc;
-  if (!dt_valid(data_dt)) return fail(FFQ_ERR_ARG, "bad dtype tag");
+  if ((rc = check_tags({data_dt}))) return rc;
   if (info.numel == 0) return fail(FFQ_ERR_EMPTY, "min/max of an empty tensor");
-  if (!data || !mn || !mx) return fail(FFQ_ERR_ARG, "NULL buffer");
+  if ((rc = check_buffers({data, mn, mx}))) return rc;
   const MinMaxPlan p = plan_for(info, data_dt);
   if (p.workspace > workspace_bytes || (p.workspace && !workspace))
     return fail(FFQ_ERR_WORKSPACE, "min/max needs %zu workspace bytes, got %zu", p.workspace, workspace_bytes);
-  if (p.plan != PLAN_GENERIC && !aligned16(data)) {
-    // misaligned view: fall through to the element-wise kernels
-  } else if (p.plan != PLAN_GENERIC) {
-    switch (data_dt) {
-      case FFQ_F32: return run_fast<float>(p, info, data, mn, mx, accumulate, flags, workspace, stream, ex);
-      case FFQ_BF16: return run_fast<bf16_t>(p, info, data, mn, mx, accumulate, flags, workspace, stream, ex);
-      default: return run_fast<f16_t>(p, info, data, mn, mx, accumulate, flags, workspace, stream, ex);
-    }
+  if (p.plan != PLAN_GENERIC && aligned16(data)) {  // (a misaligned view falls through to the element-wise kernels)
+    for_float_dtype(data_dt, [&](auto t) {
+      rc = run_fast<typename decltype(t)::type>(p, info, data, mn, mx, accumulate, flags, workspace, stream, ex);
+    });
+    return rc;
   }
   const size_t need = sizeof(GenericCell) * (size_t)info.ntiles;
   if (need > workspace_bytes) return fail(FFQ_ERR_WORKSPACE, "min/max needs %zu workspace bytes, got %zu", need, workspace_bytes);
   GenericCell* cells = static_cast<GenericCell*>(workspace);
   const unsigned tb = (unsigned)((info.ntiles + kBlock - 1) / kBlock);
   minmax_generic_init_kernel<<<tb, kBlock, 0, stream>>>(cells, info.ntiles);
-  int64_t blocks = (info.numel + kBlock - 1) / kBlock;
-  if (blocks > 8192) blocks = 8192;
-  minmax_generic_scatter_kernel<<<(unsigned)blocks, kBlock, 0, stream>>>(data, data_dt, info.numel, make_generic(tiling), cells);
+  minmax_generic_scatter_kernel<<<generic_grid(info.numel), kBlock, 0, stream>>>(data, data_dt, info.numel, make_generic(tiling), cells);
   minmax_generic_finalize_kernel<<<tb, kBlock, 0, stream>>>(cells, info.ntiles, mn, mx, data_dt, accumulate, flags);
   return check_launch("minmax_generic");
 }
@@ -781,19 +767,17 @@ static int parameters_impl(const void* min_range, const void* max_range, int ran
                            void* offset_out, int offset_dt, int round_offset, void* workspace, size_t workspace_bytes,
                            hipStream_t stream) {
   if (!min_range || !max_range || !scale_out || ntiles <= 0) return fail(FFQ_ERR_ARG, "bad argument");
-  if (!dt_valid(range_dt) || !dt_valid(scale_dt) || (offset_out && !dt_valid(offset_dt)))
-    return fail(FFQ_ERR_ARG, "bad dtype tag");
+  if (int rc = check_tags({range_dt, scale_dt, offset_out ? offset_dt : scale_dt})) return rc;
   const RangeArgs a = make_range_args(range_dt, ntiles, num_bits, symmetric, allow_one_sided, scale_dt, offset_dt, round_offset);
-  const bool typed = range_dt == FFQ_F32 || range_dt == FFQ_BF16 || range_dt == FFQ_F16;
-  if (typed && ntiles > kRangeGridTiles && !generic_kernels_forced()) {
+  if (is_f32_bf16_f16(range_dt) && ntiles > kRangeGridTiles && !generic_kernels_forced()) {
     const size_t need = parameters_workspace(ntiles, symmetric, allow_one_sided);
     float* partial = need ? static_cast<float*>(workspace) : nullptr;
     if (!need || (workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 3u) == 0)) {
-      switch (range_dt) {
-        case FFQ_F32: return parameters_grid<float>(min_range, max_range, scale_out, offset_out, a, partial, stream);
-        case FFQ_BF16: return parameters_grid<bf16_t>(min_range, max_range, scale_out, offset_out, a, partial, stream);
-        default: return parameters_grid<f16_t>(min_range, max_range, scale_out, offset_out, a, partial, stream);
-      }
+      int rc = FFQ_OK;
+      for_float_dtype(range_dt, [&](auto t) {
+        rc = parameters_grid<typename decltype(t)::type>(min_range, max_range, scale_out, offset_out, a, partial, stream);
+      });
+      return rc;
     }
     // no scratch for the global decision: the one-block kernel below decides it in LDS (never fails for lack of scratch)
   }
@@ -1074,17 +1058,6 @@ static bool launch_dynamic_rows(const void* data, void* out, float* scale_out, f
   return true;
 }
 
-template <typename TIn>
-static bool launch_dynamic_rows_out(int out_dt, const void* data, void* out, float* scale_out, float* offset_out,
-                                    const TileInfo& info, const DynRowsArgs& a, int32_t* ticket, hipStream_t stream) {
-  switch (out_dt) {
-    case FFQ_I8: return launch_dynamic_rows<TIn, int8_t>(data, out, scale_out, offset_out, info, a, ticket, stream);
-    case FFQ_F32: return launch_dynamic_rows<TIn, float>(data, out, scale_out, offset_out, info, a, ticket, stream);
-    case FFQ_BF16: return launch_dynamic_rows<TIn, bf16_t>(data, out, scale_out, offset_out, info, a, ticket, stream);
-    default: return false;
-  }
-}
-
 // true: the one-launch kernel was enqueued (*rc holds the launch status); false: the caller composes A4 -> A5 -> A1
 static bool dynamic_one_launch(const void* data, int data_dt, const TileInfo& info, double num_bits, int symmetric,
                                int allow_one_sided, void* out, int out_dt, float* scale_out, float* offset_out,
@@ -1094,23 +1067,22 @@ static bool dynamic_one_launch(const void* data, int data_dt, const TileInfo& in
   // the one decision that is global over the tiles (range.py:100) takes two ticket words (DYN_GUESS / DYN_SETTLE); a single tile
   // answers it in the reduction's last block (below)
   if (symmetric && allow_one_sided && (!ticket || info.ntiles == 1)) return false;
-  if (num_bits != floor(num_bits) || num_bits < 1 || num_bits > 32 || generic_kernels_forced()) return false;
-  if (!aligned16(data) || !aligned16(out)) return false;
+  if (!streaming_bits(num_bits) || !aligned16(data, out)) return false;
   DynRowsArgs a;
   a.ntiles = (uint32_t)info.ntiles;
   a.chunks_per_run = 0;
-  const double lo = -pow(2.0, num_bits - 1.0);
-  a.lo = (float)lo; a.hi = (float)(-lo - 1.0);
+  const ClampBounds bounds = clamp_bounds(num_bits);
+  a.lo = (float)bounds.lo; a.hi = (float)bounds.hi;
   // A3 rounds the offset it returns (_quantizer_impl.py:275); a static quantizer's parameter keeps its fraction (range.py:121)
   a.range = make_range_args(data_dt, info.ntiles, num_bits, symmetric, allow_one_sided, FFQ_F32, FFQ_F32, run_min ? 0 : 1);
   a.run_min = run_min; a.run_max = run_max; a.flags = flags;
   bool done = false;
-  switch (data_dt) {
-    case FFQ_BF16: done = launch_dynamic_rows_out<bf16_t>(out_dt, data, out, scale_out, offset_out, info, a, ticket, stream); break;
-    case FFQ_F16: done = launch_dynamic_rows_out<f16_t>(out_dt, data, out, scale_out, offset_out, info, a, ticket, stream); break;
-    case FFQ_F32: done = launch_dynamic_rows_out<float>(out_dt, data, out, scale_out, offset_out, info, a, ticket, stream); break;
-    default: break;
-  }
+  for_dtype<bf16_t, f16_t, float>(data_dt, [&](auto tin) {
+    using TIn = typename decltype(tin)::type;
+    for_dtype<int8_t, float, bf16_t>(out_dt, [&](auto tout) {
+      done = launch_dynamic_rows<TIn, typename decltype(tout)::type>(data, out, scale_out, offset_out, info, a, ticket, stream);
+    });
+  });
   if (done) *rc = check_launch("quantize_dynamic_rows_kernel");
   return done;
 }
@@ -1160,14 +1132,12 @@ int ffq_running_minmax_step(const void* data, int data_dt, const ffq_tiling* til
 int ffq_running_minmax_quantize(const void* data, int data_dt, const ffq_tiling* tiling, void* min_inout, void* max_inout,
                                 int32_t* status_flags, double num_bits, int symmetric, int allow_one_sided, float* scale_out,
                                 float* offset_out, void* out, int out_dt, int32_t* ticket, void* stream) {
-  if (!data || !min_inout || !max_inout || !scale_out || !offset_out || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!dt_valid(data_dt) || !dt_valid(out_dt)) return fail(FFQ_ERR_ARG, "bad dtype tag");
+  int rc = check_buffers({data, min_inout, max_inout, scale_out, offset_out, out});
+  if (rc || (rc = check_tags({data_dt, out_dt}))) return rc;
   TileInfo info;
-  int rc = analyse(tiling, &info);
-  if (rc) return rc;
+  if ((rc = analyse(tiling, &info))) return rc;
   if (info.numel == 0) return fail(FFQ_ERR_DTYPE, "running min/max + quantize: empty tensor (take the two steps)");
-  if (!ffq_can_support_bitwidth(out_dt, num_bits))
-    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", out_dt, num_bits);
+  if ((rc = check_container(out_dt, num_bits))) return rc;
   if (info.ntiles == 1 || !dynamic_one_launch(data, data_dt, info, num_bits, symmetric, allow_one_sided, out, out_dt, scale_out, offset_out, ticket,
                                               static_cast<hipStream_t>(stream), &rc, min_inout, max_inout, status_flags))
     return fail(FFQ_ERR_DTYPE, "running min/max + quantize: tiling outside the one-pass kernel (take ffq_running_minmax_step, then ffq_quantize_by_tile)");
@@ -1187,15 +1157,15 @@ int ffq_parameters_for_range(const void* min_range, const void* max_range, int r
                          static_cast<hipStream_t>(stream));
 }
 
-// workspace layout: [ minmax scratch | min (ntiles, data dtype) | max (ntiles, data dtype) ]
+// the composed route's workspace (dynamic_workspace, ffq_quantizer_host.h): the reduction's scratch, which A5's grid form reuses
+static DynamicWorkspace dynamic_layout(const ffq_tiling* tiling, const TileInfo& info, int data_dt) {
+  return dynamic_workspace(minmax_workspace(tiling, data_dt), parameters_workspace(info.ntiles, 1, 1), info.ntiles, data_dt);
+}
+
 size_t ffq_quantize_dynamic_workspace_bytes(const ffq_tiling* tiling, int data_dt) {
   TileInfo info;
   if (analyse(tiling, &info) || info.numel == 0) return 0;
-  size_t mm = minmax_workspace(tiling, data_dt);
-  const size_t a5 = (parameters_workspace(info.ntiles, 1, 1) + 255) & ~(size_t)255;
-  if (mm < a5) mm = a5;
-  const size_t ranges = (((size_t)info.ntiles * dt_size(data_dt)) + 255) & ~(size_t)255;
-  return mm + 2 * ranges;
+  return dynamic_layout(tiling, info, data_dt).total;
 }
 
 int ffq_quantize_dynamic_by_tile(const void* data, int data_dt, const ffq_tiling* tiling, double num_bits,
@@ -1208,21 +1178,18 @@ int ffq_quantize_dynamic_by_tile(const void* data, int data_dt, const ffq_tiling
   if (rc) return rc;
   // torch.min over an empty row raises IndexError -> QuantizationError                 (:259-264)
   if (info.numel == 0) return fail(FFQ_ERR_EMPTY, "Cannot dynamically quantize an empty tensor");
-  if (!data || !out || !scale_out || !offset_out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!dt_valid(data_dt) || !dt_valid(out_dt)) return fail(FFQ_ERR_ARG, "bad dtype tag");
-  if (!ffq_can_support_bitwidth(out_dt, num_bits))
-    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.",
-                out_dt, num_bits);
+  if ((rc = check_buffers({data, out, scale_out, offset_out}))) return rc;
+  if ((rc = check_tags({data_dt, out_dt}))) return rc;
+  if ((rc = check_container(out_dt, num_bits))) return rc;
   // contiguous-run tiles that fit a block's registers and no global one-sided decision: ONE launch, 3 B/elem
   if (dynamic_one_launch(data, data_dt, info, num_bits, symmetric, allow_one_sided, out, out_dt, scale_out, offset_out, ticket, s, &rc)) return rc;
-  const size_t need = ffq_quantize_dynamic_workspace_bytes(tiling, data_dt);
-  if (need > workspace_bytes || !workspace)
-    return fail(FFQ_ERR_WORKSPACE, "dynamic quantize needs %zu workspace bytes, got %zu", need, workspace_bytes);
-  const size_t ranges = (((size_t)info.ntiles * dt_size(data_dt)) + 255) & ~(size_t)255;
-  const size_t mm = need - 2 * ranges;
+  const DynamicWorkspace w = dynamic_layout(tiling, info, data_dt);
+  if (w.total > workspace_bytes || !workspace)
+    return fail(FFQ_ERR_WORKSPACE, "dynamic quantize needs %zu workspace bytes, got %zu", w.total, workspace_bytes);
   char* base = static_cast<char*>(workspace);
-  void* mn = base + mm;
-  void* mx = base + mm + ranges;
+  void* mn = base + w.min;
+  void* mx = base + w.max;
+  const size_t mm = w.min;  // the scratch is what lies in front of the ranges
   // one tile and a ticket word: the reduction's last block also evaluates A5 (round(offset) included)   (:266-275)
   StepExtras ex;
   ex.ticket = ticket;

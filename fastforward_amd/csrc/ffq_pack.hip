@@ -10,6 +10,7 @@
 #endif
 #include "ffq_affine.h"
 #include "ffq_common.h"
+#include "ffq_quantizer_host.h"
 #include "ffq_vec.h"
 
 #include <math.h>
@@ -190,11 +191,7 @@ __global__ __launch_bounds__(kBlock) void unpack_dequantize_int4_kernel(const ui
 // quantize+pack 5.25-5.31 with 16, 5.20-5.29 with 8 and 4.6-4.7 with 8 x 2 items per lane (a second reciprocal per 8
 // elements, and short blocks beat unrolled ones here as in A1) — so the two directions take different shapes.
 static int pack4_item(int dt, bool unpack) {
-#ifdef FFQ_EXPERIMENTS
-  static const int forced = getenv("FFQ_PACK_ITEM") ? atoi(getenv("FFQ_PACK_ITEM")) : 0;
-#else
-  constexpr int forced = 0;
-#endif
+  const int forced = experiment_knob("FFQ_PACK_ITEM", 0);
   if (dt == FFQ_F32) return 16;
   if (forced == 8 || forced == 16) return forced;
   return unpack ? 8 : 16;
@@ -206,11 +203,8 @@ static int pack4_plan(const ffq_tiling* tiling, int64_t block, int64_t scale_num
   int rc = analyse(tiling, &info);
   if (rc) return rc;
   *numel = info.numel;
-  if (block <= 0 || (block & 1) || info.numel % block) return fail(FFQ_ERR_ARG, "numel %% block != 0 or odd block");
-  if (info.numel != 0) {
-    if ((rc = check_param_numel("scale", scale_numel, info.ntiles))) return rc;
-    if (offset && (rc = check_param_numel("offset", offset_numel, info.ntiles))) return rc;
-  }
+  if ((rc = check_pack_block(info.numel, block))) return rc;
+  if ((rc = check_param_counts(info, scale_numel, offset != nullptr, offset_numel))) return rc;
   const bool layout_ok = info.layout == LAYOUT_SCALAR || (info.layout == LAYOUT_ROWS && info.run % 16 == 0);
   if (!layout_ok || block % 32 != 0 || info.numel >= ((int64_t)1 << 32))
     return fail(FFQ_ERR_DTYPE, "fused 4-bit kernels cover per-tensor / contiguous-run tiles (run %% 16 == 0) and block %% 32 == 0");
@@ -219,8 +213,8 @@ static int pack4_plan(const ffq_tiling* tiling, int64_t block, int64_t scale_num
   a->items_per_block = make_fastdiv((uint32_t)(block / (2 * item)));
   a->rows = info.layout == LAYOUT_ROWS;
   a->chunks_per_run = make_fastdiv(a->rows ? (uint32_t)(info.run / 16) : 1u);
-  a->scale_stride = scale_numel == 1 ? 0u : 1u;
-  a->offset_stride = offset_numel == 1 ? 0u : 1u;
+  a->scale_stride = param_stride(scale_numel);
+  a->offset_stride = param_stride(offset_numel);
   return FFQ_OK;
 }
 
@@ -295,54 +289,38 @@ static unsigned grid_of(int64_t items) {
 
 using namespace ffq;
 
-extern "C" int ffq_pack_int4(const void* codes, int codes_dt, int64_t numel, int64_t block, uint8_t* packed,
-                             void* stream) {
+// A7 in either direction: PACK reads `codes` and writes `packed`, otherwise the other way round. One lane per packed word where
+// the blocks are whole words and both pointers are 4-byte aligned, the element-wise kernel otherwise.
+template <bool PACK>
+static int pack4_either(void* codes, int codes_dt, int64_t numel, int64_t block, uint8_t* packed, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!dt_valid(codes_dt)) return fail(FFQ_ERR_ARG, "bad dtype tag");
-  if (block <= 0 || (block & 1) || numel < 0 || numel % block) return fail(FFQ_ERR_ARG, "numel %% block != 0 or odd block");
+  int rc = check_tags({codes_dt});
+  if (rc || (rc = check_pack_block(numel, block))) return rc;
   if (numel == 0) return FFQ_OK;
-  if (!codes || !packed) return fail(FFQ_ERR_ARG, "NULL buffer");
+  if ((rc = check_buffers({codes, packed}))) return rc;
   const int64_t nbytes = numel / 2;
-  if (fast_ok(codes, packed, numel, block) && (codes_dt == FFQ_I8 || codes_dt == FFQ_BF16 || codes_dt == FFQ_F16 || codes_dt == FFQ_F32)) {
+  const bool by_words = fast_ok(codes, packed, numel, block) && for_dtype<int8_t, bf16_t, f16_t, float>(codes_dt, [&](auto t) {
+    using T = typename decltype(t)::type;
     const uint32_t nwords = (uint32_t)(nbytes / 4);
     const FastDiv wpb = make_fastdiv((uint32_t)(block / 8));
-    uint32_t* out = reinterpret_cast<uint32_t*>(packed);
-    const unsigned grid = grid_of(nwords);
-    switch (codes_dt) {
-      case FFQ_I8: pack_int4_kernel<int8_t><<<grid, kBlock, 0, s>>>((const int8_t*)codes, out, nwords, wpb, (uint32_t)block); break;
-      case FFQ_BF16: pack_int4_kernel<bf16_t><<<grid, kBlock, 0, s>>>((const bf16_t*)codes, out, nwords, wpb, (uint32_t)block); break;
-      case FFQ_F16: pack_int4_kernel<f16_t><<<grid, kBlock, 0, s>>>((const f16_t*)codes, out, nwords, wpb, (uint32_t)block); break;
-      default: pack_int4_kernel<float><<<grid, kBlock, 0, s>>>((const float*)codes, out, nwords, wpb, (uint32_t)block); break;
-    }
-    return check_launch("pack_int4_kernel");
-  }
-  pack_int4_generic_kernel<<<grid_of(nbytes), kBlock, 0, s>>>(codes, codes_dt, packed, nbytes, block);
-  return check_launch("pack_int4_generic_kernel");
+    uint32_t* words = reinterpret_cast<uint32_t*>(packed);
+    if constexpr (PACK) pack_int4_kernel<T><<<grid_of(nwords), kBlock, 0, s>>>(static_cast<const T*>(codes), words, nwords, wpb, (uint32_t)block);
+    else unpack_int4_kernel<T><<<grid_of(nwords), kBlock, 0, s>>>(words, static_cast<T*>(codes), nwords, wpb, (uint32_t)block);
+  });
+  if (by_words) return check_launch(PACK ? "pack_int4_kernel" : "unpack_int4_kernel");
+  if constexpr (PACK) pack_int4_generic_kernel<<<grid_of(nbytes), kBlock, 0, s>>>(codes, codes_dt, packed, nbytes, block);
+  else unpack_int4_generic_kernel<<<grid_of(nbytes), kBlock, 0, s>>>(packed, codes, codes_dt, nbytes, block);
+  return check_launch(PACK ? "pack_int4_generic_kernel" : "unpack_int4_generic_kernel");
+}
+
+extern "C" int ffq_pack_int4(const void* codes, int codes_dt, int64_t numel, int64_t block, uint8_t* packed,
+                             void* stream) {
+  return pack4_either<true>(const_cast<void*>(codes), codes_dt, numel, block, packed, stream);
 }
 
 extern "C" int ffq_unpack_int4(const uint8_t* packed, int64_t numel, int64_t block, void* codes_out, int codes_dt,
                                void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!dt_valid(codes_dt)) return fail(FFQ_ERR_ARG, "bad dtype tag");
-  if (block <= 0 || (block & 1) || numel < 0 || numel % block) return fail(FFQ_ERR_ARG, "numel %% block != 0 or odd block");
-  if (numel == 0) return FFQ_OK;
-  if (!codes_out || !packed) return fail(FFQ_ERR_ARG, "NULL buffer");
-  const int64_t nbytes = numel / 2;
-  if (fast_ok(codes_out, packed, numel, block) && (codes_dt == FFQ_I8 || codes_dt == FFQ_BF16 || codes_dt == FFQ_F16 || codes_dt == FFQ_F32)) {
-    const uint32_t nwords = (uint32_t)(nbytes / 4);
-    const FastDiv wpb = make_fastdiv((uint32_t)(block / 8));
-    const uint32_t* in = reinterpret_cast<const uint32_t*>(packed);
-    const unsigned grid = grid_of(nwords);
-    switch (codes_dt) {
-      case FFQ_I8: unpack_int4_kernel<int8_t><<<grid, kBlock, 0, s>>>(in, (int8_t*)codes_out, nwords, wpb, (uint32_t)block); break;
-      case FFQ_BF16: unpack_int4_kernel<bf16_t><<<grid, kBlock, 0, s>>>(in, (bf16_t*)codes_out, nwords, wpb, (uint32_t)block); break;
-      case FFQ_F16: unpack_int4_kernel<f16_t><<<grid, kBlock, 0, s>>>(in, (f16_t*)codes_out, nwords, wpb, (uint32_t)block); break;
-      default: unpack_int4_kernel<float><<<grid, kBlock, 0, s>>>(in, (float*)codes_out, nwords, wpb, (uint32_t)block); break;
-    }
-    return check_launch("unpack_int4_kernel");
-  }
-  unpack_int4_generic_kernel<<<grid_of(nbytes), kBlock, 0, s>>>(packed, codes_out, codes_dt, nbytes, block);
-  return check_launch("unpack_int4_generic_kernel");
+  return pack4_either<false>(codes_out, codes_dt, numel, block, const_cast<uint8_t*>(packed), stream);
 }
 
 extern "C" int ffq_quantize_pack_int4(const void* data, int data_dt, const float* scale, int64_t scale_numel,
@@ -355,8 +333,8 @@ extern "C" int ffq_quantize_pack_int4(const void* data, int data_dt, const float
   int rc = pack4_plan(tiling, block, scale_numel, offset, offset_numel, &a, &numel, item);
   if (rc) return rc;
   if (numel == 0) return FFQ_OK;
-  if (!data || !scale || !packed) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!(data_dt == FFQ_BF16 || data_dt == FFQ_F16 || data_dt == FFQ_F32) || !aligned16(data) || !aligned16(packed))
+  if ((rc = check_buffers({data, scale, packed}))) return rc;
+  if (!is_f32_bf16_f16(data_dt) || !aligned16(data, packed))
     return fail(FFQ_ERR_DTYPE, "fused quantize+pack is built for 16-byte aligned f32 / bf16 / f16 data");
   const unsigned grid = (a.nitems + kBlock - 1) / kBlock;
 #define FFQ_QP(T, I)                                                                                                \
@@ -364,11 +342,13 @@ extern "C" int ffq_quantize_pack_int4(const void* data, int data_dt, const float
     if (offset) quantize_pack_int4_kernel<T, true, I><<<grid, kBlock, 0, s>>>(static_cast<const T*>(data), scale, offset, packed, a); \
     else quantize_pack_int4_kernel<T, false, I><<<grid, kBlock, 0, s>>>(static_cast<const T*>(data), scale, offset, packed, a);       \
   } while (0)
-  switch (data_dt) {
-    case FFQ_BF16: if (item == 8) FFQ_QP(bf16_t, 8); else FFQ_QP(bf16_t, 16); break;
-    case FFQ_F16: if (item == 8) FFQ_QP(f16_t, 8); else FFQ_QP(f16_t, 16); break;
-    default: FFQ_QP(float, 16); break;
-  }
+  for_dtype<bf16_t, f16_t, float>(data_dt, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (sizeof(T) == 2) {  // (fp32 moves 16 elements of each half per lane whatever the knob says)
+      if (item == 8) { FFQ_QP(T, 8); return; }
+    }
+    FFQ_QP(T, 16);
+  });
 #undef FFQ_QP
   return check_launch("quantize_pack_int4_kernel");
 }
@@ -383,8 +363,8 @@ extern "C" int ffq_unpack_dequantize_int4(const uint8_t* packed, const float* sc
   int rc = pack4_plan(tiling, block, scale_numel, offset, offset_numel, &a, &numel, item);
   if (rc) return rc;
   if (numel == 0) return FFQ_OK;
-  if (!packed || !scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!(out_dt == FFQ_BF16 || out_dt == FFQ_F16 || out_dt == FFQ_F32) || !aligned16(out) || !aligned16(packed))
+  if ((rc = check_buffers({packed, scale, out}))) return rc;
+  if (!is_f32_bf16_f16(out_dt) || !aligned16(out, packed))
     return fail(FFQ_ERR_DTYPE, "fused unpack+dequantize is built for 16-byte aligned f32 / bf16 / f16 outputs");
   const unsigned grid = (a.nitems + kBlock - 1) / kBlock;
 #define FFQ_UD(T, I)                                                                                                \
@@ -392,11 +372,13 @@ extern "C" int ffq_unpack_dequantize_int4(const uint8_t* packed, const float* sc
     if (offset) unpack_dequantize_int4_kernel<T, true, I><<<grid, kBlock, 0, s>>>(packed, scale, offset, static_cast<T*>(out), a); \
     else unpack_dequantize_int4_kernel<T, false, I><<<grid, kBlock, 0, s>>>(packed, scale, offset, static_cast<T*>(out), a);       \
   } while (0)
-  switch (out_dt) {
-    case FFQ_BF16: if (item == 8) FFQ_UD(bf16_t, 8); else FFQ_UD(bf16_t, 16); break;
-    case FFQ_F16: if (item == 8) FFQ_UD(f16_t, 8); else FFQ_UD(f16_t, 16); break;
-    default: FFQ_UD(float, 16); break;
-  }
+  for_dtype<bf16_t, f16_t, float>(out_dt, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (sizeof(T) == 2) {  // (fp32 moves 16 elements of each half per lane whatever the knob says)
+      if (item == 8) { FFQ_UD(T, 8); return; }
+    }
+    FFQ_UD(T, 16);
+  });
 #undef FFQ_UD
   return check_launch("unpack_dequantize_int4_kernel");
 }
@@ -406,8 +388,8 @@ extern "C" int ffq_pack_gguf_blocks(const int8_t* codes, const float* scales, in
   if (format != 4 && format != 8) return fail(FFQ_ERR_ARG, "GGUF block format must be 4 (Q4_0) or 8 (Q8_0)");
   if (nblocks < 0 || nblocks >= ((int64_t)1 << 31)) return fail(FFQ_ERR_ARG, "bad block count");
   if (nblocks == 0) return FFQ_OK;
-  if (!codes || !scales || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(codes) || !aligned16(out)) return fail(FFQ_ERR_ARG, "codes and output must be 16-byte aligned");
+  if (int rc = check_buffers({codes, scales, out})) return rc;
+  if (!aligned16(codes, out)) return fail(FFQ_ERR_ARG, "codes and output must be 16-byte aligned");
   const unsigned grid = (unsigned)((nblocks + kBlock - 1) / kBlock);
   if (format == 4) pack_gguf_blocks_kernel<4><<<grid, kBlock, 0, s>>>(codes, scales, out, (uint32_t)nblocks);
   else pack_gguf_blocks_kernel<8><<<grid, kBlock, 0, s>>>(codes, scales, out, (uint32_t)nblocks);

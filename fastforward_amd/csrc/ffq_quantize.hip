@@ -15,10 +15,10 @@
 //                            intermediate rounding of the eager chain reproduced
 #include "ffq_affine.h"
 #include "ffq_common.h"
+#include "ffq_quantizer_host.h"
 #include "ffq_vec.h"
 
 #include <math.h>
-#include <stdlib.h>
 
 namespace ffq {
 
@@ -183,96 +183,36 @@ __global__ __launch_bounds__(kBlock) void quantize_generic_kernel(const void* __
 
 // (-DFFQ_EXPERIMENTS builds) FFQ_DIV_MODE=0 forces the compiler's IEEE division sequence in the streaming kernels;
 // the default is the Markstein iteration (bit-identical, see Divider).
-static int div_mode() {
-#ifdef FFQ_EXPERIMENTS
-  static const int mode = [] {
-    const char* e = getenv("FFQ_DIV_MODE");
-    return e ? atoi(e) : 1;
-  }();
-  return mode;
-#else
-  return 1;
-#endif
-}
-
-static unsigned grid_for(int64_t work_items, int per_block) {
-  int64_t blocks = (work_items + per_block - 1) / per_block;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
-
-static int launch_generic(const void* data, int data_dt, const void* scale, int scale_dt,
-                          int64_t scale_numel, const void* offset, int offset_dt, int64_t offset_numel,
-                          const ffq_tiling* tiling, double lo, double hi, int div_dt, int sub_dt,
-                          void* out, int out_dt, int64_t start, int64_t count, hipStream_t stream) {
-  if (count <= 0) return FFQ_OK;
-  GenericArgs a;
-  a.data_dt = data_dt; a.scale_dt = scale_dt; a.offset_dt = offset_dt; a.out_dt = out_dt;
-  a.div_dt = div_dt; a.sub_dt = sub_dt;
-  a.has_offset = offset != nullptr;
-  a.start = start; a.count = count;
-  a.scale_numel = scale_numel; a.offset_numel = offset_numel;
-  a.lo = lo; a.hi = hi;
-  a.g = make_generic(tiling);
-  int64_t blocks = (count + kBlock - 1) / kBlock;
-  if (blocks > 8192) blocks = 8192;
-  quantize_generic_kernel<<<dim3((unsigned)blocks), dim3(kBlock), 0, stream>>>(data, scale, offset, out, a);
-  return check_launch("quantize_generic_kernel");
-}
-
-// chunks per lane: measured on MI355X (interleaved A/B): short blocks win. Also measured and rejected for 2-byte ->
-// 1-byte: two coalesced 16-B loads per lane (chunks l and l + 64) with a lane-pair exchange into 16-B stores (4.2-5.3 TB/s)
-// or with two 8-B stores (4.1-5.4 TB/s) against 6.0 TB/s for the 16-element chunk below —
-// bf16 -> int8 [14336, 4096]: E=16/U=1 29.2 us vs E=16/U=2 32.4 us vs E=8/U=4 34.3 us; U=1 also wins for
-// bf16 -> bf16 (38.5 vs 41.0 us at U=4) and per-tensor activations (33.2 vs 39.2 us).
-static int stream_u_override() {
-#ifdef FFQ_EXPERIMENTS
-  const char* e = getenv("FFQ_STREAM_U");
-  return e ? atoi(e) : 0;
-#else
-  return 0;
-#endif
-}
+static int div_mode() { return experiment_knob("FFQ_DIV_MODE", 1); }
 
 template <typename TIn, typename TOut, int E, int U>
-static int launch_stream_u(const TIn* in, TOut* out, const float* scale, int64_t scale_numel,
-                           const float* offset, int64_t offset_numel, const TileInfo& info, float lo,
-                           float hi, hipStream_t stream) {
-  StreamArgs a;
-  a.lo = lo; a.hi = hi;
-  a.nchunks = (uint32_t)(info.numel / E);
-  a.scale_stride = scale_numel == 1 ? 0u : 1u;
-  a.offset_stride = offset_numel == 1 ? 0u : 1u;
-  a.chunks_per_run = make_fastdiv(1);
-  a.channels = make_fastdiv(1);
+static int launch_stream_u(const AffineCall& c) {
+  const StreamArgs a = stream_args<StreamArgs>(c, E);
   const unsigned grid = grid_for(a.nchunks, kBlock * U);
-  const dim3 block(kBlock);
+  const TIn* in = static_cast<const TIn*>(c.data);
+  TOut* out = static_cast<TOut*>(c.out);
+  const float* scale = static_cast<const float*>(c.scale);
+  const float* offset = static_cast<const float*>(c.offset);
 #define FFQ_LAUNCH_D(LAYOUT, D)                                                                      \
   do {                                                                                               \
     if (offset)                                                                                      \
-      quantize_stream_kernel<TIn, TOut, LAYOUT, E, U, true, D><<<grid, block, 0, stream>>>(in, out, scale, offset, a); \
+      quantize_stream_kernel<TIn, TOut, LAYOUT, E, U, true, D><<<grid, kBlock, 0, c.stream>>>(in, out, scale, offset, a); \
     else                                                                                             \
-      quantize_stream_kernel<TIn, TOut, LAYOUT, E, U, false, D><<<grid, block, 0, stream>>>(in, out, scale, offset, a); \
+      quantize_stream_kernel<TIn, TOut, LAYOUT, E, U, false, D><<<grid, kBlock, 0, c.stream>>>(in, out, scale, offset, a); \
   } while (0)
-#ifdef FFQ_EXPERIMENTS  // the IEEE-division form of the streaming kernels exists in tuning builds only (round 4: 1,637 -> ~500 device kernels)
+  // the IEEE-division form of the streaming kernels exists in tuning builds only (round 4: 1,637 -> ~500 device kernels)
 #define FFQ_LAUNCH(LAYOUT)                                                                           \
   do {                                                                                               \
-    if (div_mode() == 1) FFQ_LAUNCH_D(LAYOUT, 1); else FFQ_LAUNCH_D(LAYOUT, 0);                      \
+    if constexpr (kExperiments) {                                                                    \
+      if (div_mode() == 1) FFQ_LAUNCH_D(LAYOUT, 1); else FFQ_LAUNCH_D(LAYOUT, 0);                    \
+    } else {                                                                                         \
+      FFQ_LAUNCH_D(LAYOUT, 1);                                                                       \
+    }                                                                                                \
   } while (0)
-#else
-#define FFQ_LAUNCH(LAYOUT) FFQ_LAUNCH_D(LAYOUT, 1)
-#endif
-  switch (info.layout) {
+  switch (c.info.layout) {
     case LAYOUT_SCALAR: FFQ_LAUNCH(LAYOUT_SCALAR); break;
-    case LAYOUT_ROWS:
-      a.chunks_per_run = make_fastdiv((uint32_t)(info.run / E));
-      FFQ_LAUNCH(LAYOUT_ROWS);
-      break;
-    default:
-      a.chunks_per_run = make_fastdiv((uint32_t)(info.inner / E));
-      a.channels = make_fastdiv((uint32_t)info.channels);
-      FFQ_LAUNCH(LAYOUT_CHANNEL);
-      break;
+    case LAYOUT_ROWS: FFQ_LAUNCH(LAYOUT_ROWS); break;
+    default: FFQ_LAUNCH(LAYOUT_CHANNEL); break;
   }
 #undef FFQ_LAUNCH
 #undef FFQ_LAUNCH_D
@@ -280,147 +220,91 @@ static int launch_stream_u(const TIn* in, TOut* out, const float* scale, int64_t
 }
 
 template <typename TIn, typename TOut, int E>
-static int launch_stream(const TIn* in, TOut* out, const float* scale, int64_t scale_numel,
-                         const float* offset, int64_t offset_numel, const TileInfo& info, float lo,
-                         float hi, hipStream_t stream) {
-#ifdef FFQ_EXPERIMENTS  // chunks per lane: one in the product (measured fastest, see above); 2 / 4 in tuning builds only
-  int u = stream_u_override();
-  if (u == 0) u = 1;
-  switch (u) {
-    case 1: return launch_stream_u<TIn, TOut, E, 1>(in, out, scale, scale_numel, offset, offset_numel, info, lo, hi, stream);
-    case 4: return launch_stream_u<TIn, TOut, E, 4>(in, out, scale, scale_numel, offset, offset_numel, info, lo, hi, stream);
-    default: return launch_stream_u<TIn, TOut, E, 2>(in, out, scale, scale_numel, offset, offset_numel, info, lo, hi, stream);
+static int launch_stream(const AffineCall& c) {
+  if constexpr (kExperiments) {
+    switch (stream_chunks_per_lane()) {
+      case 1: return launch_stream_u<TIn, TOut, E, 1>(c);
+      case 4: return launch_stream_u<TIn, TOut, E, 4>(c);
+      default: return launch_stream_u<TIn, TOut, E, 2>(c);
+    }
+  } else {
+    return launch_stream_u<TIn, TOut, E, 1>(c);
   }
-#else
-  return launch_stream_u<TIn, TOut, E, 1>(in, out, scale, scale_numel, offset, offset_numel, info, lo, hi, stream);
-#endif
 }
 
 template <typename TIn, typename TOut, int E>
-static int launch_columns(const TIn* in, TOut* out, const float* scale, int64_t scale_numel,
-                          const float* offset, int64_t offset_numel, const TileInfo& info, float lo,
-                          float hi, hipStream_t stream) {
-  ColumnArgs a;
-  a.lo = lo; a.hi = hi;
-  a.col_chunks = (uint32_t)(info.channels / E);
-  a.rows = (uint32_t)(info.numel / info.channels);
-  a.scale_stride = scale_numel == 1 ? 0u : 1u;
-  a.offset_stride = offset_numel == 1 ? 0u : 1u;
-  a.col_chunks_div = make_fastdiv(a.col_chunks);
-  // ~8 rows per lane amortise the 2*E parameter loads; never more groups than rows.
-  uint32_t groups = (a.rows + 7) / 8;
-  if (groups < 1) groups = 1;
-  a.row_groups = groups;
-  const uint64_t lanes = (uint64_t)groups * a.col_chunks;
-  const unsigned grid = grid_for((int64_t)lanes, kBlock);
+static int launch_columns(const AffineCall& c) {
+  const ColumnArgs a = affine_column_args<ColumnArgs>(c, E);
+  const TIn* in = static_cast<const TIn*>(c.data);
+  TOut* out = static_cast<TOut*>(c.out);
+  const float* scale = static_cast<const float*>(c.scale);
+  const float* offset = static_cast<const float*>(c.offset);
   if (offset)
-    quantize_columns_kernel<TIn, TOut, E, true><<<grid, dim3(kBlock), 0, stream>>>(in, out, scale, offset, a);
+    quantize_columns_kernel<TIn, TOut, E, true><<<column_grid(a), kBlock, 0, c.stream>>>(in, out, scale, offset, a);
   else
-    quantize_columns_kernel<TIn, TOut, E, false><<<grid, dim3(kBlock), 0, stream>>>(in, out, scale, offset, a);
+    quantize_columns_kernel<TIn, TOut, E, false><<<column_grid(a), kBlock, 0, c.stream>>>(in, out, scale, offset, a);
   return check_launch("quantize_columns_kernel");
 }
 
-// Decide whether the streaming kernels apply: fp32 stages + fp32 parameters + 16 B alignment + a
-// layout whose tiles never split a chunk; everything else goes to the generic kernel.
-template <typename TIn, typename TOut, int E>
-static int dispatch_fast_e(const void* data, const void* scale, int64_t scale_numel, const void* offset,
-                           int64_t offset_numel, const TileInfo& info, float lo, float hi, void* out,
-                           hipStream_t stream, int64_t* done) {
-  *done = 0;
-  const TIn* in = static_cast<const TIn*>(data);
-  TOut* o = static_cast<TOut*>(out);
-  const float* s = static_cast<const float*>(scale);
-  const float* f = static_cast<const float*>(offset);
-  if (info.layout == LAYOUT_SCALAR || (info.layout == LAYOUT_ROWS && info.run % E == 0) ||
-      (info.layout == LAYOUT_CHANNEL && info.inner % E == 0)) {
-    if (info.numel / E == 0) return FFQ_OK;
-    // only the SCALAR layout can leave a tail (numel % E); ROWS / CHANNEL tiles are whole chunks
-    *done = info.layout == LAYOUT_SCALAR ? (info.numel / E) * E : info.numel;
-    return launch_stream<TIn, TOut, E>(in, o, s, scale_numel, f, offset_numel, info, lo, hi, stream);
-  }
-  return FFQ_OK;
-}
-
-// Decide whether the streaming kernels apply: fp32 stages + fp32 parameters + 16 B alignment + a
-// layout whose tiles never split a chunk; everything else goes to the generic kernel.
-// One-byte containers use 16-element chunks so that the store is 16 B per lane as well.
+// the kernel stream_route() chose, on the types of this call; 16-element chunks exist for one-byte containers only
 template <typename TIn, typename TOut>
-static int dispatch_fast(const void* data, const void* scale, int64_t scale_numel, const void* offset,
-                         int64_t offset_numel, const TileInfo& info, float lo, float hi, void* out,
-                         hipStream_t stream, int64_t* done) {
-  *done = 0;
-  if (info.numel >= ((int64_t)1 << 32) - 4096) return FFQ_OK;  // 32-bit chunk index
-  if (!aligned16(data) || !aligned16(out)) return FFQ_OK;
-  int rc = FFQ_OK;
-  if constexpr (sizeof(TOut) == 1) {
-    rc = dispatch_fast_e<TIn, TOut, 16>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, done);
-    if (rc || *done) return rc;
+static int launch_route(const AffineCall& c, const StreamRoute& route) {
+  if (route.kernel == ROUTE_STREAM) {
+    if constexpr (sizeof(TOut) == 1) {
+      if (route.chunk == 16) return launch_stream<TIn, TOut, 16>(c);
+    }
+    return launch_stream<TIn, TOut, 8>(c);
   }
-  rc = dispatch_fast_e<TIn, TOut, 8>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, done);
-  if (rc || *done) return rc;
-  if (info.layout == LAYOUT_CHANNEL && info.inner == 1 && info.channels % 8 == 0) {
-    *done = info.numel;
-    return launch_columns<TIn, TOut, 8>(static_cast<const TIn*>(data), static_cast<TOut*>(out),
-                                        static_cast<const float*>(scale), scale_numel,
-                                        static_cast<const float*>(offset), offset_numel, info, lo, hi, stream);
-  }
-  return FFQ_OK;
-}
-
-template <typename TIn>
-static int dispatch_out(int out_dt, const void* data, const void* scale, int64_t scale_numel,
-                        const void* offset, int64_t offset_numel, const TileInfo& info, float lo,
-                        float hi, void* out, hipStream_t stream, int64_t* handled) {
-  switch (out_dt) {
-    case FFQ_F32: return dispatch_fast<TIn, float>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, handled);
-    case FFQ_BF16: return dispatch_fast<TIn, bf16_t>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, handled);
-    case FFQ_F16: return dispatch_fast<TIn, f16_t>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, handled);
-    case FFQ_I8: return dispatch_fast<TIn, int8_t>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, handled);
-    case FFQ_I16: return dispatch_fast<TIn, int16_t>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, handled);
-    case FFQ_I32: return dispatch_fast<TIn, int32_t>(data, scale, scale_numel, offset, offset_numel, info, lo, hi, out, stream, handled);
-    default: *handled = 0; return FFQ_OK;
-  }
+  return launch_columns<TIn, TOut, 8>(c);
 }
 
 int quantize_impl(const void* data, int data_dt, const void* scale, int scale_dt, int64_t scale_numel,
                   const void* offset, int offset_dt, int64_t offset_numel, const ffq_tiling* tiling,
                   double num_bits, void* out, int out_dt, hipStream_t stream) {
-  TileInfo info;
-  int rc = analyse(tiling, &info);
+  AffineCall c;
+  int rc = analyse(tiling, &c.info);
   if (rc) return rc;
-  if (!dt_valid(data_dt) || !dt_valid(scale_dt) || !dt_valid(out_dt) || (offset && !dt_valid(offset_dt)))
-    return fail(FFQ_ERR_ARG, "bad dtype tag");
-  if (info.numel != 0) {
-    if ((rc = check_param_numel("scale", scale_numel, info.ntiles))) return rc;
-    if (offset && (rc = check_param_numel("offset", offset_numel, info.ntiles))) return rc;
-  }
   const int off_dt = offset ? offset_dt : scale_dt;
-  // min_threshold = -(2 ** (num_bits - 1)); max_threshold = -min_threshold - 1      (:158-159)
-  const double lo = -pow(2.0, num_bits - 1.0), hi = -lo - 1.0;
+  if ((rc = check_tags({data_dt, scale_dt, out_dt, off_dt}))) return rc;
+  if ((rc = check_param_counts(c.info, scale_numel, offset != nullptr, offset_numel))) return rc;
+  const ClampBounds bounds = clamp_bounds(num_bits);
   int div_dt = ffq_promote_types(data_dt, scale_dt);
   if (!dt_is_float(div_dt)) div_dt = FFQ_F32;  // integer / integer is a true division in float
   const int sub_dt = ffq_promote_types(div_dt, off_dt);
-  if (!ffq_can_support_bitwidth(out_dt, num_bits))
-    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.",
-                out_dt, num_bits);
-  if (info.numel == 0) return FFQ_OK;
-  if (!data || !scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
+  if ((rc = check_container(out_dt, num_bits))) return rc;
+  if (c.info.numel == 0) return FFQ_OK;
+  if ((rc = check_buffers({data, scale, out}))) return rc;
+  c.data = data; c.scale = scale; c.offset = offset; c.out = out;
+  c.scale_numel = scale_numel; c.offset_numel = offset_numel;
+  c.lo = (float)bounds.lo; c.hi = (float)bounds.hi;
+  c.stream = stream;
 
-  const bool fast_types = num_bits == floor(num_bits) && num_bits >= 1 && num_bits <= 32 &&
-                          div_dt == FFQ_F32 && sub_dt == FFQ_F32 && scale_dt == FFQ_F32 &&
-                          (!offset || offset_dt == FFQ_F32) && !generic_kernels_forced();
+  // the streaming kernels: fp32 stages + fp32 parameters on a route stream_route() finds; everything else goes to the generic kernel
   int64_t done = 0;
-  if (fast_types) {
-    switch (data_dt) {
-      case FFQ_F32: rc = dispatch_out<float>(out_dt, data, scale, scale_numel, offset, offset_numel, info, (float)lo, (float)hi, out, stream, &done); break;
-      case FFQ_BF16: rc = dispatch_out<bf16_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, (float)lo, (float)hi, out, stream, &done); break;
-      case FFQ_F16: rc = dispatch_out<f16_t>(out_dt, data, scale, scale_numel, offset, offset_numel, info, (float)lo, (float)hi, out, stream, &done); break;
-      default: break;
-    }
+  if (div_dt == FFQ_F32 && sub_dt == FFQ_F32 && scale_dt == FFQ_F32 && off_dt == FFQ_F32) {
+    const StreamRoute route = stream_route(c.info, {dt_size(data_dt), dt_size(out_dt), aligned16(data), aligned16(out), !streaming_bits(num_bits), false});
+    bool launched = false;
+    if (route.kernel != ROUTE_NONE)
+      for_float_dtype(data_dt, [&](auto tin) {
+        using TIn = typename decltype(tin)::type;
+        launched = for_dtype<float, bf16_t, f16_t, int8_t, int16_t, int32_t>(out_dt, [&](auto tout) {
+          rc = launch_route<TIn, typename decltype(tout)::type>(c, route);
+        });
+      });
     if (rc) return rc;
+    if (launched) done = route.covered;
   }
-  return launch_generic(data, data_dt, scale, scale_dt, scale_numel, offset, offset_dt, offset_numel,
-                        tiling, lo, hi, div_dt, sub_dt, out, out_dt, done, info.numel - done, stream);
+  if (done >= c.info.numel) return FFQ_OK;
+  GenericArgs a;
+  a.data_dt = data_dt; a.scale_dt = scale_dt; a.offset_dt = offset_dt; a.out_dt = out_dt;
+  a.div_dt = div_dt; a.sub_dt = sub_dt;
+  a.has_offset = offset != nullptr;
+  a.start = done; a.count = c.info.numel - done;
+  a.scale_numel = scale_numel; a.offset_numel = offset_numel;
+  a.lo = bounds.lo; a.hi = bounds.hi;
+  a.g = make_generic(tiling);
+  quantize_generic_kernel<<<generic_grid(a.count), kBlock, 0, stream>>>(data, scale, offset, out, a);
+  return check_launch("quantize_generic_kernel");
 }
 
 // A1 for a [rows, cols] weight with one parameter pair per row, int8 container, that also leaves the row sums of the codes
@@ -618,22 +502,21 @@ extern "C" int ffq_quantize_by_tile_unless_same(const void* data, int data_dt, c
                                                 void* stream) {
   using namespace ffq;
   if (numel < 0) return fail(FFQ_ERR_ARG, "negative extent");
-  if (!ffq_can_support_bitwidth(FFQ_I8, num_bits))
-    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", FFQ_I8, num_bits);
+  if (int rc = check_container(FFQ_I8, num_bits)) return rc;
   if (numel == 0) return FFQ_OK;
-  if (!data || !scale || !earlier_scale || !out) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (num_bits != floor(num_bits) || num_bits < 1 || numel % 16 != 0 || numel / 16 >= ((int64_t)1 << 32) - 4096 || !aligned16(data) || !aligned16(out) ||
-      !(data_dt == FFQ_F32 || data_dt == FFQ_BF16 || data_dt == FFQ_F16))
+  if (int rc = check_buffers({data, scale, earlier_scale, out})) return rc;
+  if (!integral_bits(num_bits) || numel % 16 != 0 || !fits_chunk_index(numel / 16) || !aligned16(data, out) || !is_f32_bf16_f16(data_dt))
     return fail(FFQ_ERR_DTYPE, "quantize unless same: whole 16-element chunks of f32 / bf16 / f16 data, 16-byte aligned (else ffq_quantize_by_tile)");
-  const double lo = -pow(2.0, num_bits - 1.0), hi = -lo - 1.0;
+  const ClampBounds bounds = clamp_bounds(num_bits);
   const uint32_t nchunks = (uint32_t)(numel / 16);
   unsigned grid = grid_for(nchunks, kBlock);
   if (grid > kUnlessSameBlocks) grid = kUnlessSameBlocks;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const float lo = (float)bounds.lo, hi = (float)bounds.hi;
   switch (data_dt) {
-    case FFQ_F32: quantize_unless_same_kernel<float><<<grid, kBlock, 0, s>>>(static_cast<const float*>(data), out, scale, offset, earlier_scale, earlier_offset, (float)lo, (float)hi, nchunks); break;
-    case FFQ_BF16: quantize_unless_same_kernel<bf16_t><<<grid, kBlock, 0, s>>>(static_cast<const bf16_t*>(data), out, scale, offset, earlier_scale, earlier_offset, (float)lo, (float)hi, nchunks); break;
-    default: quantize_unless_same_kernel<f16_t><<<grid, kBlock, 0, s>>>(static_cast<const f16_t*>(data), out, scale, offset, earlier_scale, earlier_offset, (float)lo, (float)hi, nchunks); break;
+    case FFQ_F32: quantize_unless_same_kernel<float><<<grid, kBlock, 0, s>>>(static_cast<const float*>(data), out, scale, offset, earlier_scale, earlier_offset, lo, hi, nchunks); break;
+    case FFQ_BF16: quantize_unless_same_kernel<bf16_t><<<grid, kBlock, 0, s>>>(static_cast<const bf16_t*>(data), out, scale, offset, earlier_scale, earlier_offset, lo, hi, nchunks); break;
+    default: quantize_unless_same_kernel<f16_t><<<grid, kBlock, 0, s>>>(static_cast<const f16_t*>(data), out, scale, offset, earlier_scale, earlier_offset, lo, hi, nchunks); break;
   }
   return check_launch("quantize_unless_same_kernel");
 }
@@ -645,19 +528,18 @@ extern "C" int ffq_quantize_rows_rowsum(const void* data, int data_dt, const flo
   if (rows < 0 || cols < 0) return fail(FFQ_ERR_ARG, "negative extent");
   if (data_dt != FFQ_BF16) return fail(FFQ_ERR_DTYPE, "fused weight quantize + row sums is built for bf16 weights");
   if (cols % 1024 != 0) return fail(FFQ_ERR_DTYPE, "fused weight quantize + row sums needs cols %% 1024 == 0");
-  if (!ffq_can_support_bitwidth(FFQ_I8, num_bits))
-    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", FFQ_I8, num_bits);
+  if (int rc = check_container(FFQ_I8, num_bits)) return rc;
   // the kernel clamps BEFORE it rounds (quantize_chunk_to_bytes), which equals the reference's round-then-clamp only for integer clamp
   // bounds: a fractional bit width goes back to ffq_quantize_by_tile
-  if (num_bits != floor(num_bits) || num_bits < 1) return fail(FFQ_ERR_DTYPE, "fused weight quantize + row sums needs an integral bit width (else ffq_quantize_by_tile)");
+  if (!integral_bits(num_bits)) return fail(FFQ_ERR_DTYPE, "fused weight quantize + row sums needs an integral bit width (else ffq_quantize_by_tile)");
   if (rows == 0 || cols == 0) return FFQ_OK;
-  if (!data || !scale || !codes || !rowsum) return fail(FFQ_ERR_ARG, "NULL buffer");
-  if (!aligned16(data) || !aligned16(codes)) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+  if (int rc = check_buffers({data, scale, codes, rowsum})) return rc;
+  if (!aligned16(data, codes)) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
   const int64_t nchunks = rows * cols / 16;
   if (nchunks >= ((int64_t)1 << 32)) return fail(FFQ_ERR_ARG, "too many elements for one launch");
   StreamArgs a;
-  const double lo = -pow(2.0, num_bits - 1.0);
-  a.lo = (float)lo; a.hi = (float)(-lo - 1.0);
+  const ClampBounds bounds = clamp_bounds(num_bits);
+  a.lo = (float)bounds.lo; a.hi = (float)bounds.hi;
   a.nchunks = (uint32_t)nchunks;
   a.scale_stride = 1; a.offset_stride = 1;
   a.chunks_per_run = make_fastdiv((uint32_t)(cols / 16));
@@ -674,14 +556,13 @@ extern "C" int ffq_quantize_rows_batch(const ffq_rows_batch* batch, int data_dt,
   if (!batch || batch->count < 0 || batch->count > FFQ_MAX_BATCH) return fail(FFQ_ERR_ARG, "batch count must be 0..%d", FFQ_MAX_BATCH);
   if (batch->count == 0) return FFQ_OK;
   if (data_dt != FFQ_BF16) return fail(FFQ_ERR_DTYPE, "batched weight quantization is built for bf16 weights");
-  if (!ffq_can_support_bitwidth(FFQ_I8, batch->num_bits))
-    return fail(FFQ_ERR_PRECISION, "Provided dtype (%d) is not enough to store %g bits quantized values.", FFQ_I8, batch->num_bits);
-  if (batch->num_bits != floor(batch->num_bits) || batch->num_bits < 1)  // clamp-before-round needs integer bounds (see ffq_quantize_rows_rowsum)
+  if (int rc = check_container(FFQ_I8, batch->num_bits)) return rc;
+  if (!integral_bits(batch->num_bits))  // clamp-before-round needs integer bounds (see ffq_quantize_rows_rowsum)
     return fail(FFQ_ERR_DTYPE, "batched weight quantization needs an integral bit width (else ffq_quantize_by_tile per weight)");
   BatchArgs a;
   a.count = batch->count;
-  const double lo = -pow(2.0, batch->num_bits - 1.0);
-  a.lo = (float)lo; a.hi = (float)(-lo - 1.0);
+  const ClampBounds bounds = clamp_bounds(batch->num_bits);
+  a.lo = (float)bounds.lo; a.hi = (float)bounds.hi;
   uint64_t blocks = 0;
   const bool rowsums = batch->rowsum[0] != nullptr;
   for (int i = 0; i < batch->count; ++i) {
@@ -691,7 +572,7 @@ extern "C" int ffq_quantize_rows_batch(const ffq_rows_batch* batch, int data_dt,
     if (rows <= 0 || cols <= 0 || cols % 16 != 0 || (rows * cols / 16) % kBlock != 0)
       return fail(FFQ_ERR_DTYPE, "batched weight quantization needs rows * cols %% %d == 0 and cols %% 16 == 0", 16 * kBlock);
     if (!batch->data[i] || !batch->scale[i] || !batch->codes[i]) return fail(FFQ_ERR_ARG, "NULL buffer in batch member %d", i);
-    if (!aligned16(batch->data[i]) || !aligned16(batch->codes[i])) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
+    if (!aligned16(batch->data[i], batch->codes[i])) return fail(FFQ_ERR_ARG, "buffers must be 16-byte aligned");
     a.m[i].in = static_cast<const bf16_t*>(batch->data[i]);
     a.m[i].out = batch->codes[i];
     a.m[i].scale = batch->scale[i];
