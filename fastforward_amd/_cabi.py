@@ -365,6 +365,22 @@ SIGNATURES_KV_TOKEN: dict[str, tuple[object, list[object]]] = {
     ),
 }
 
+# name -> (restype, argtypes); mirrors include/ffq_kv_paged_token.h one to one: the tenth header's table (the paged cache of
+# ffq_kv_paged.h with the per-position parameters of ffq_kv_token.h in a third pool), bound as SIGNATURES_3D is (None on a library
+# without the symbol).
+SIGNATURES_PAGED_TOKEN: dict[str, tuple[object, list[object]]] = {
+    "ffq_kv_paged_token_append": (
+        _i,
+        [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _d, _i, _d, _i, _vp, _vp, _i64,
+         _vp],
+    ),
+    "ffq_kv_paged_token_decode": (
+        _i,
+        [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _i, _d, _vp,
+         _vp, _d, _i64, _i64, _vp, _vp, _sz, _vp],
+    ),
+}
+
 SDPA_DECODE_MAX_ROWS = 32  # FFQ_SDPA_DECODE_MAX_ROWS
 SDPA_DECODE_KEY_TILE = 128  # FFQ_SDPA_DECODE_KEY_TILE
 SDPA_DECODE_MAX_SPLITS = 64  # FFQ_SDPA_DECODE_MAX_SPLITS
@@ -398,7 +414,7 @@ class FFQLibrary:
             setattr(self, name, None)
         for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items(),
                                           *SIGNATURES_UNFOLD.items(), *SIGNATURES_DECODE.items(), *SIGNATURES_KV.items(), *SIGNATURES_PAGED.items(),
-                                          *SIGNATURES_KV_TOKEN.items()):
+                                          *SIGNATURES_KV_TOKEN.items(), *SIGNATURES_PAGED_TOKEN.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

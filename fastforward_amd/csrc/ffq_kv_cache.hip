@@ -22,6 +22,10 @@
 // and the row's first lane writes (k_scale, k_offset, v_scale, v_offset) with one 16-byte store. In the rotary path the lane's 16
 // elements are the two 8-element halves it rotated, after their rounding to the data dtype. No LDS, no scratch.
 //
+// kv_paged_token_store_kernel (ffq_kv_paged_token_append, include/ffq_kv_paged_token.h) is the body with both: the row's codes and its
+// four parameters go to row pos % P of page table[b][pos / P] of three pools, and a row whose table entry lies outside the pool is
+// dropped before any load, its parameters with it. The reduction, A5, A1 and the one 16-byte store are the dense token kernel's.
+//
 // Host side: the entry points run the shared rules (check_shape, check_quantizers_and_tables, check_sizes_and_buffers) in the order
 // their error tables pin, with their own steps in between, fill() the kernel's arguments and launch through launch_rows.
 #include "ffq_affine.h"
@@ -32,6 +36,7 @@
 
 #include "../../include/ffq_kv_cache.h"
 #include "../../include/ffq_kv_paged.h"
+#include "../../include/ffq_kv_paged_token.h"
 #include "../../include/ffq_kv_token.h"
 
 #include <math.h>
@@ -90,6 +95,11 @@ struct TokenStoreArgs : AppendArgs {
   float* params;
   int64_t ps[3];
   RangeArgs krange, vrange;
+};
+
+// Both (include/ffq_kv_paged_token.h): `params` is the parameter pool and ps its (page, head, row) strides
+struct PagedTokenStoreArgs : TokenStoreArgs {
+  Paging pg;
 };
 
 typedef __attribute__((ext_vector_type(4))) float kv_f32x4;
@@ -208,7 +218,8 @@ __device__ __forceinline__ void token_row(const TokenStoreArgs& a, const T* kn, 
 
 // The body of both kernels. PAGED changes where a row's codes go: page table[b][pos / P], row pos % P of the pools; a row whose table
 // entry lies outside the pool is dropped like one outside [0, S_max), before any load
-// TOKEN (kv_token_store_kernel): the row's parameters are its own, computed here (token_row)
+// TOKEN (kv_token_store_kernel): the row's parameters are its own, computed here (token_row); with PAGED they go where the codes go,
+// row `at` of page `slot` of the parameter pool
 template <typename T, bool ROPE, bool PAGED, bool TOKEN = false, typename Args>
 __device__ __forceinline__ void append_rows(const Args& a) {
   const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -231,7 +242,7 @@ __device__ __forceinline__ void append_rows(const Args& a) {
   int8_t* kc = a.kc + slot * a.kcs[0] + kvh * a.kcs[1] + at * a.kcs[2];
   int8_t* vc = a.vc + slot * a.vcs[0] + kvh * a.vcs[1] + at * a.vcs[2];
   if constexpr (TOKEN) {
-    token_row<T, ROPE>(a, kn, vn, kc, vc, a.params + b * a.ps[0] + kvh * a.ps[1] + pos * a.ps[2], pos, j);
+    token_row<T, ROPE>(a, kn, vn, kc, vc, a.params + slot * a.ps[0] + kvh * a.ps[1] + at * a.ps[2], pos, j);
     return;
   }
   const float ks = a.ks[0], ko = a.ko ? rne(a.ko[0]) : 0.0f;
@@ -269,6 +280,12 @@ __global__ __launch_bounds__(kBlock) void kv_token_store_kernel(TokenStoreArgs a
   append_rows<T, ROPE, false, true>(a);
 }
 
+// (its name holds none of the names the other three are counted by)
+template <typename T, bool ROPE>
+__global__ __launch_bounds__(kBlock) void kv_paged_token_store_kernel(PagedTokenStoreArgs a) {
+  append_rows<T, ROPE, true, true>(a);
+}
+
 bool bits_ok(double bits) { return bits >= 2.0 && bits <= 8.0 && bits == (double)(int)bits; }
 
 // Each rule of the two entry points once: it takes the entry point's name for its message and returns the first failing status. An
@@ -286,6 +303,20 @@ int check_shape(const char* name, int dt, const int64_t* strides, int64_t E, int
 // The two bit-widths
 int check_bits(const char* name, double k_num_bits, double v_num_bits) {
   if (!bits_ok(k_num_bits) || !bits_ok(v_num_bits)) return fail(FFQ_ERR_ARG, "%s: the quantizers need an integral bit-width in 2..8", name);
+  return FFQ_OK;
+}
+
+// The two symmetric flags of dynamic quantizers
+int check_symmetric(const char* name, int k_symmetric, int v_symmetric) {
+  if ((k_symmetric != 0 && k_symmetric != 1) || (v_symmetric != 0 && v_symmetric != 1))
+    return fail(FFQ_ERR_ARG, "%s: symmetric is 0 (scale and offset) or 1 (scale alone)", name);
+  return FFQ_OK;
+}
+
+// The three strides of a parameter store (entries 12..14), `store` as the entry point names it
+int check_param_strides(const char* name, const int64_t* strides, const char* store) {
+  for (int i = 12; i < 15; ++i)
+    if (strides[i] < 0 || strides[i] % 4) return fail(FFQ_ERR_ARG, "%s: the strides of %s must be non-negative multiples of 16 bytes", name, store);
   return FFQ_OK;
 }
 
@@ -351,6 +382,14 @@ void fill(AppendArgs& a, const void* k_new, const void* v_new, void* k_cache, vo
   a.vlo = (float)-vhalf; a.vhi = (float)(vhalf - 1.0);
 }
 
+// what the two entry points with per-position parameters add to fill(): the store (or pool), its strides and A5's constants
+void fill_token(TokenStoreArgs& a, void* params, const int64_t* strides, double k_num_bits, int k_symmetric, double v_num_bits, int v_symmetric) {
+  a.params = static_cast<float*>(params);
+  for (int i = 0; i < 3; ++i) a.ps[i] = strides[12 + i];
+  a.krange = make_range_args(FFQ_F32, 1, k_num_bits, k_symmetric, 0, FFQ_F32, FFQ_F32, 1);
+  a.vrange = make_range_args(FFQ_F32, 1, v_num_bits, v_symmetric, 0, FFQ_F32, FFQ_F32, 1);
+}
+
 }  // namespace
 }  // namespace ffq
 
@@ -404,22 +443,45 @@ extern "C" int ffq_kv_token_append(const void* k_new, const void* v_new, int dt,
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = check_shape("kv_token_append", dt, strides, E, batch, kv_heads, L, S_max)) return rc;
   if (int rc = check_bits("kv_token_append", k_num_bits, v_num_bits)) return rc;
-  if ((k_symmetric != 0 && k_symmetric != 1) || (v_symmetric != 0 && v_symmetric != 1))
-    return fail(FFQ_ERR_ARG, "kv_token_append: symmetric is 0 (scale and offset) or 1 (scale alone)");
+  if (int rc = check_symmetric("kv_token_append", k_symmetric, v_symmetric)) return rc;
   if (int rc = check_tables("kv_token_append", cos_table, sin_table, table_rows, S_max, "cache position")) return rc;
   if (batch == 0 || L == 0) return FFQ_OK;
   if (int rc = check_sizes_and_buffers("kv_token_append", batch, kv_heads, L, S_max, E, strides, {k_new, v_new, k_cache, v_cache, params}, cos_table, sin_table, {lens}, "lens")) return rc;
-  for (int i = 12; i < 15; ++i)
-    if (strides[i] < 0 || strides[i] % 4) return fail(FFQ_ERR_ARG, "kv_token_append: the strides of params must be non-negative multiples of 16 bytes");
+  if (int rc = check_param_strides("kv_token_append", strides, "params")) return rc;
   if (S_max == 0) return FFQ_OK;  // (no position to write to)
 
   TokenStoreArgs a;
   fill(a, k_new, v_new, k_cache, v_cache, lens, batch, kv_heads, L, S_max, E, strides, nullptr, nullptr, k_num_bits, nullptr, nullptr, v_num_bits,
        cos_table, sin_table);
-  a.params = static_cast<float*>(params);
-  for (int i = 0; i < 3; ++i) a.ps[i] = strides[12 + i];
-  a.krange = make_range_args(FFQ_F32, 1, k_num_bits, k_symmetric, 0, FFQ_F32, FFQ_F32, 1);
-  a.vrange = make_range_args(FFQ_F32, 1, v_num_bits, v_symmetric, 0, FFQ_F32, FFQ_F32, 1);
+  fill_token(a, params, strides, k_num_bits, k_symmetric, v_num_bits, v_symmetric);
   if (dt == FFQ_F16) return launch_rows(kv_token_store_kernel<f16_t, true>, kv_token_store_kernel<f16_t, false>, a, "kv_token_store_kernel", s);
   return launch_rows(kv_token_store_kernel<bf16_t, true>, kv_token_store_kernel<bf16_t, false>, a, "kv_token_store_kernel", s);
+}
+
+extern "C" int ffq_kv_paged_token_append(const void* k_new, const void* v_new, int dt, void* k_pool, void* v_pool, void* param_pool, const void* lens,
+                                         const void* block_table, int64_t batch, int64_t kv_heads, int64_t L, int64_t num_pages, int64_t P,
+                                         int64_t max_pages, int64_t table_stride, int64_t E, const int64_t* strides, double k_num_bits,
+                                         int k_symmetric, double v_num_bits, int v_symmetric, const void* cos_table, const void* sin_table,
+                                         int64_t table_rows, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = check_shape("kv_paged_token_append", dt, strides, E, batch, kv_heads, L, 0)) return rc;
+  if (const char* why = paging_error(num_pages, P, max_pages, table_stride)) return fail(FFQ_ERR_ARG, "kv_paged_token_append: %s", why);
+  const int64_t C = max_pages * P;  // a sequence's capacity, in the place of S_max (below 2^30)
+  if (int rc = check_bits("kv_paged_token_append", k_num_bits, v_num_bits)) return rc;
+  if (int rc = check_symmetric("kv_paged_token_append", k_symmetric, v_symmetric)) return rc;
+  if (int rc = check_tables("kv_paged_token_append", cos_table, sin_table, table_rows, C, "position of a sequence")) return rc;
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (int rc = check_sizes_and_buffers("kv_paged_token_append", batch, kv_heads, L, C, E, strides, {k_new, v_new, k_pool, v_pool, param_pool}, cos_table,
+                                       sin_table, {lens, block_table}, "lens, block_table"))
+    return rc;
+  if (int rc = check_param_strides("kv_paged_token_append", strides, "param_pool")) return rc;
+
+  PagedTokenStoreArgs a;
+  fill(a, k_new, v_new, k_pool, v_pool, lens, batch, kv_heads, L, C, E, strides, nullptr, nullptr, k_num_bits, nullptr, nullptr, v_num_bits, cos_table,
+       sin_table);
+  fill_token(a, param_pool, strides, k_num_bits, k_symmetric, v_num_bits, v_symmetric);
+  a.pg = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
+  if (dt == FFQ_F16)
+    return launch_rows(kv_paged_token_store_kernel<f16_t, true>, kv_paged_token_store_kernel<f16_t, false>, a, "kv_paged_token_store_kernel", s);
+  return launch_rows(kv_paged_token_store_kernel<bf16_t, true>, kv_paged_token_store_kernel<bf16_t, false>, a, "kv_paged_token_store_kernel", s);
 }

@@ -1,5 +1,5 @@
-// ffq_paging.h — what the two paged kernels (kv_paged_store_kernel in ffq_kv_cache.hip, kv_paged_partial_kernel in
-// ffq_sdpa_decode.hip) share: how a sequence's position is found in a pool of fixed-size pages (include/ffq_kv_paged.h), and the
+// ffq_paging.h — what the paged kernels (kv_paged_store_kernel and kv_paged_token_store_kernel in ffq_kv_cache.hip,
+// kv_paged_partial_kernel and kv_paged_token_partial_kernel in ffq_sdpa_decode.hip) share: how a sequence's position is found in a pool of fixed-size pages (include/ffq_kv_paged.h), and the
 // alignment rule of the int32 tables (lens, block_table) that the host side of both files checks.
 //
 // Position `pos` of sequence b lives in pool page table[b][pos >> page_shift] at row pos & (P - 1). A kernel reads a table entry

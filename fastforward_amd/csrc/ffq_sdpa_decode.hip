@@ -44,6 +44,12 @@
 // loaded), and the tile's dks / dko / dvs / dvo come out of those staging registers when the tile is consumed, each lane's own. Nothing
 // else differs: the same bits as the dense form wherever the parameters agree.
 //
+// ffq_kv_paged_token_decode (include/ffq_kv_paged_token.h) is ffq_kv_token_decode over pages. kv_paged_token_partial_kernel is
+// decode_partial instantiated with PAGED and TOKEN: the lane's four floats come from row key % P of page table[b][key / P] of the
+// parameter pool, one 16-byte load beside the K and V loads under the same `in` flag (the length, the split's end, a page outside the
+// pool), so the parameters of a key that is not loaded are not loaded either. At P = 16 a wave's 32 keys span two pages; the page is per
+// lane already. The key order, the arithmetic, the LDS and the combine kernel are unchanged.
+//
 // Host side: the entry points fill one DecodeCall from their own parameter lists, run the shared rules (check_operands,
 // check_rows, check_quantizer_and_splits, check_sizes_and_buffers, check_layout_and_workspace) in the order their error tables pin,
 // with their own steps in between, and hand the call to enqueue(); launch_partial is the one partial launch (docs/kernels.md).
@@ -54,6 +60,7 @@
 
 #include "../../include/ffq_kv_cache.h"
 #include "../../include/ffq_kv_paged.h"
+#include "../../include/ffq_kv_paged_token.h"
 #include "../../include/ffq_kv_token.h"
 #include "../../include/ffq_sdpa_decode.h"
 
@@ -192,9 +199,15 @@ struct TokenDecodeArgs : DecodeArgs {
   int64_t ps[3];
 };
 
+// Both (include/ffq_kv_paged_token.h): `params` is the parameter pool [num_pages, kv_heads, P, 4] and ps its (page, head, row) strides
+struct PagedTokenDecodeArgs : TokenDecodeArgs {
+  Paging pg;
+};
+
 // The body of the partial kernels. PAGED changes where a lane finds its key row (stage_load) and adds one mask, the keys of a page
 // the table does not place inside the pool; the arithmetic and the key order are the dense form's. TOKEN changes where a lane finds
-// the (scale, offset) of its key row: staged beside the codes, one 16-byte load per lane and tile
+// the (scale, offset) of its key row: staged beside the codes, one 16-byte load per lane and tile (with PAGED: out of the key's page
+// of the parameter pool)
 template <int E, bool F16, bool PAGED, bool TOKEN = false, typename Args>
 __device__ __forceinline__ void decode_partial(const Args& a) {
   constexpr int T = E / 16;   // MFMA k-steps of QK^T
@@ -270,23 +283,25 @@ __device__ __forceinline__ void decode_partial(const Args& a) {
   uint32_t staged_ok = 0;
   [[maybe_unused]] dc_f32x4 sprm = {0.0f, 0.0f, 0.0f, 0.0f};  // (TOKEN) the staged key row's (k_scale, k_offset, v_scale, v_offset)
   [[maybe_unused]] const float* pbase = nullptr;
-  if constexpr (TOKEN) pbase = a.params + (int64_t)b * a.ps[0] + (int64_t)kvh * a.ps[1];
+  if constexpr (TOKEN) pbase = a.params + (PAGED ? 0 : (int64_t)b * a.ps[0]) + (int64_t)kvh * a.ps[1];
   auto stage_load = [&](int32_t it) {
     const int32_t key = k_begin + it * kTile + (int32_t)wave * kWaveKeys + (int32_t)r32;
     bool in = key < k_end;
     int32_t at = key;                   // the row inside the cache, or inside its page
     int64_t k_page = 0, v_page = 0;     // (paged) where the page starts in each pool
+    [[maybe_unused]] int64_t p_page = 0;
     if constexpr (PAGED) {
       const int32_t page = in ? page_of(a.pg, b, key) : -1;
       in = page >= 0;
       at = key & ((1 << a.pg.page_shift) - 1);
       k_page = (int64_t)page * a.ks[0];
       v_page = (int64_t)page * a.vs[0];
+      if constexpr (TOKEN) p_page = (int64_t)page * a.ps[0];
       staged_ok = (uint32_t)__ballot(in);  // (both halves of the wave hold the same 32 keys)
     }
     if constexpr (TOKEN) {
       sprm = dc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (in) sprm = *reinterpret_cast<const dc_f32x4*>(pbase + (int64_t)at * a.ps[2]);
+      if (in) sprm = *reinterpret_cast<const dc_f32x4*>(pbase + p_page + (int64_t)at * a.ps[2]);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -508,6 +523,12 @@ __global__ __launch_bounds__(kThreads) void kv_token_partial_kernel(TokenDecodeA
   decode_partial<E, F16, false, true>(a);
 }
 
+// (its name holds none of the names the other three are counted by)
+template <int E, bool F16>
+__global__ __launch_bounds__(kThreads) void kv_paged_token_partial_kernel(PagedTokenDecodeArgs a) {
+  decode_partial<E, F16, true, true>(a);
+}
+
 struct CombineArgs {
   const float* ws_o;
   const float* ws_m;
@@ -599,7 +620,7 @@ struct DecodeCall {
   void* workspace;
   size_t workspace_bytes;
   const Paging* paging = nullptr;
-  const float* params = nullptr;  // (ffq_kv_token_decode) the per-position store and its three strides
+  const float* params = nullptr;  // (ffq_kv_token_decode, ffq_kv_paged_token_decode) the per-position store or pool and its three strides
   const int64_t* param_strides = nullptr;
 };
 
@@ -656,7 +677,15 @@ int check_layout_and_workspace(const char* name, DecodeCall& c, bool words_align
   return FFQ_OK;
 }
 
-// one partial launch: `f16` / `bf16` are the dense or the paged kernel's two instantiations at the call's E
+// The three strides of the parameter store (c.param_strides), `store` as the entry point names it
+int check_param_strides(const char* name, const DecodeCall& c, const char* store) {
+  for (int i = 0; i < 3; ++i)
+    if (c.param_strides[i] < 0 || c.param_strides[i] % 4)
+      return fail(FFQ_ERR_ARG, "%s: the strides of %s must be non-negative multiples of 16 bytes", name, store);
+  return FFQ_OK;
+}
+
+// one partial launch: `f16` / `bf16` are the two instantiations of one of the four partial kernels at the call's E
 template <typename Args>
 void launch_partial(void (*f16)(Args), void (*bf16)(Args), bool is_f16, const Args& a, unsigned blocks, hipStream_t s) {
   auto kernel = is_f16 ? f16 : bf16;
@@ -686,17 +715,20 @@ int enqueue(const DecodeCall& c, hipStream_t s) {
   a.pg = c.paging ? *c.paging : Paging{};
   const bool f16 = c.dt == FFQ_F16;
   if (c.params) {
-    TokenDecodeArgs t;
+    PagedTokenDecodeArgs t;  // (the dense token kernels take its TokenDecodeArgs)
     static_cast<DecodeArgs&>(t) = a;
     t.params = c.params;
     for (int i = 0; i < 3; ++i) t.ps[i] = c.param_strides[i];
-    if (c.E == 64) launch_partial(kv_token_partial_kernel<64, true>, kv_token_partial_kernel<64, false>, f16, t, (unsigned)parts, s);
-    else launch_partial(kv_token_partial_kernel<128, true>, kv_token_partial_kernel<128, false>, f16, t, (unsigned)parts, s);
+    t.pg = a.pg;
+    if (c.paging && c.E == 64) launch_partial(kv_paged_token_partial_kernel<64, true>, kv_paged_token_partial_kernel<64, false>, f16, t, (unsigned)parts, s);
+    else if (c.paging) launch_partial(kv_paged_token_partial_kernel<128, true>, kv_paged_token_partial_kernel<128, false>, f16, t, (unsigned)parts, s);
+    else if (c.E == 64) launch_partial<TokenDecodeArgs>(kv_token_partial_kernel<64, true>, kv_token_partial_kernel<64, false>, f16, t, (unsigned)parts, s);
+    else launch_partial<TokenDecodeArgs>(kv_token_partial_kernel<128, true>, kv_token_partial_kernel<128, false>, f16, t, (unsigned)parts, s);
   } else if (c.paging && c.E == 64) launch_partial(kv_paged_partial_kernel<64, true>, kv_paged_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
   else if (c.paging) launch_partial(kv_paged_partial_kernel<128, true>, kv_paged_partial_kernel<128, false>, f16, a, (unsigned)parts, s);
   else if (c.E == 64) launch_partial<DecodeArgs>(sdpa_decode_partial_kernel<64, true>, sdpa_decode_partial_kernel<64, false>, f16, a, (unsigned)parts, s);
   else launch_partial<DecodeArgs>(sdpa_decode_partial_kernel<128, true>, sdpa_decode_partial_kernel<128, false>, f16, a, (unsigned)parts, s);
-  if (int rc = check_launch(c.params ? "kv_token_partial_kernel" : c.paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel")) return rc;
+  if (int rc = check_launch(c.params && c.paging ? "kv_paged_token_partial_kernel" : c.params ? "kv_token_partial_kernel" : c.paging ? "kv_paged_partial_kernel" : "sdpa_decode_partial_kernel")) return rc;
 
   CombineArgs m;
   m.ws_o = a.ws_o; m.ws_m = a.ws_m; m.ws_l = a.ws_l;
@@ -824,8 +856,41 @@ extern "C" int ffq_kv_token_decode(const void* q, int q_dt, const void* k, const
   if (batch == 0 || L == 0) return FFQ_OK;
   if (S_max == 0) return fail(FFQ_ERR_ARG, "kv_token_decode: S_max must be >= 1");
   if (int rc = check_sizes_and_buffers("kv_token_decode", c, lens != nullptr)) return rc;
-  for (int i = 12; i < 15; ++i)
-    if (strides[i] < 0 || strides[i] % 4) return fail(FFQ_ERR_ARG, "kv_token_decode: the strides of params must be non-negative multiples of 16 bytes");
+  if (int rc = check_param_strides("kv_token_decode", c, "params")) return rc;
   if (int rc = check_layout_and_workspace("kv_token_decode", c, aligned16(params) && aligned4(lens), " (lens: 4-byte)")) return rc;
+  return enqueue(c, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ffq_kv_paged_token_decode(const void* q, int q_dt, const void* k_pool, const void* v_pool, int dt, const float* q_scale,
+                                         const float* q_offset, const void* param_pool, const void* lens, const void* block_table, int64_t batch,
+                                         int64_t q_heads, int64_t kv_heads, int64_t L, int64_t num_pages, int64_t P, int64_t max_pages,
+                                         int64_t table_stride, int64_t E, const int64_t* strides, int causal, double sqrt_scale,
+                                         const float* out_scale, const float* out_offset, double out_num_bits, int64_t splits, int64_t plan_len,
+                                         void* out, void* workspace, size_t workspace_bytes_given, void* stream) {
+  // the tables of the shared rules, as in ffq_kv_token_decode: the pool in the place of the scales of k and v (it holds them)
+  const float* const deq_scale[3] = {q_scale, static_cast<const float*>(param_pool), static_cast<const float*>(param_pool)};
+  const float* const deq_offset[3] = {q_offset, nullptr, nullptr};
+  DecodeCall c;
+  c.q = q; c.q_dt = q_dt; c.k = k_pool; c.v = v_pool; c.dt = dt; c.deq_scale = deq_scale; c.deq_offset = deq_offset;
+  c.batch = batch; c.q_heads = q_heads; c.kv_heads = kv_heads; c.L = L; c.keys = 0; c.E = E; c.strides = strides;  // (keys: once the geometry is sound)
+  c.lens = static_cast<const int32_t*>(lens); c.mask_kind = causal ? MASK_CAUSAL : MASK_NONE;
+  c.sqrt_scale = sqrt_scale; c.out_scale = out_scale; c.out_offset = out_offset; c.out_num_bits = out_num_bits;
+  c.splits = splits; c.plan_len = plan_len; c.out = out; c.workspace = workspace; c.workspace_bytes = workspace_bytes_given;
+  c.params = static_cast<const float*>(param_pool); c.param_strides = strides ? strides + 12 : nullptr;
+  if (int rc = check_operands("kv_paged_token_decode", c)) return rc;
+  if (const char* why = paging_error(num_pages, P, max_pages, table_stride)) return fail(FFQ_ERR_ARG, "kv_paged_token_decode: %s", why);
+  c.keys = max_pages * P;  // a sequence's capacity, in the place of S_max (below 2^30)
+  if (int rc = check_rows("kv_paged_token_decode", c)) return rc;
+  if (causal != 0 && causal != 1) return fail(FFQ_ERR_ARG, "kv_paged_token_decode: causal is 0 (every key) or 1 (bottom-right)");
+  if (int rc = check_quantizer_and_splits("kv_paged_token_decode", c)) return rc;
+  if (plan_len < 0 || plan_len > c.keys) return fail(FFQ_ERR_ARG, "kv_paged_token_decode: plan_len must be 0 (max_pages * P) or 1..max_pages * P");
+  if (batch == 0 || L == 0) return FFQ_OK;
+  if (int rc = check_sizes_and_buffers("kv_paged_token_decode", c, lens && block_table)) return rc;
+  if (int rc = check_param_strides("kv_paged_token_decode", c, "param_pool")) return rc;
+  if (int rc = check_layout_and_workspace("kv_paged_token_decode", c, aligned16(param_pool) && aligned4(lens) && aligned4(block_table),
+                                          " (lens, block_table: 4-byte)"))
+    return rc;
+  const Paging paging = {static_cast<const int32_t*>(block_table), table_stride, (int32_t)num_pages, page_shift_of(P)};
+  c.paging = &paging;
   return enqueue(c, static_cast<hipStream_t>(stream));
 }

@@ -35,3 +35,4 @@ from fastforward_amd.nn.conv import quantized_conv3d_modules as quantized_conv3d
 from fastforward_amd.nn.kv_cache import QuantizedKVCache as QuantizedKVCache  # isort: skip
 from fastforward_amd.nn.kv_cache import PagedQuantizedKVCache as PagedQuantizedKVCache  # isort: skip
 from fastforward_amd.nn.kv_cache import DynamicQuantizedKVCache as DynamicQuantizedKVCache  # isort: skip
+from fastforward_amd.nn.kv_cache import PagedDynamicQuantizedKVCache as PagedDynamicQuantizedKVCache  # isort: skip

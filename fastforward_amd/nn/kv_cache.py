@@ -20,6 +20,11 @@ outside a captured step; ``composed_paged_append`` / ``composed_paged_attend`` g
 ``(scale, offset)``, computed on the device from the row's min / max and kept in an fp32 store ``[B, H, S_max, 4]`` beside the codes
 (``ops.kv_token_append`` / ``ops.kv_token_decode``, include/ffq_kv_token.h), so nothing is calibrated ahead of serving.
 ``composed_token_append`` / ``composed_token_attend`` are its chain from the quantizer modules themselves.
+
+``PagedDynamicQuantizedKVCache`` is both: the pages and the bookkeeping of ``PagedQuantizedKVCache`` (``_PagedBase`` states them once)
+with two ``DynamicLinearQuantizer``s, every row's ``(scale, offset)`` kept in a third pool ``[num_pages, H, P, 4]`` of the same pages
+(``ops.kv_paged_token_append`` / ``ops.kv_paged_token_decode``, include/ffq_kv_paged_token.h), so a shared prefix page shares its
+parameters. ``composed_paged_token_append`` / ``composed_paged_token_attend`` gather the pages and run the dense per-row chain.
 """
 
 from __future__ import annotations
@@ -237,12 +242,13 @@ PAGED_LAYOUTS = ("phse", "pshe")
 
 def gather_pages(pool: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
     """The dense ``[B, H, max_pages * P, E]`` codes a block table ``[B, max_pages]`` describes in a pool ``[num_pages, H, P, E]``: a
-    host-driven gather (the table is read on the host); the rows of an entry outside ``[0, num_pages)`` are zeros."""
+    host-driven gather (the table is read on the host); the rows of an entry outside ``[0, num_pages)`` are zeros. A parameter pool
+    ``[num_pages, H, P, 4]`` gathers the same way."""
     num_pages, H, P, E = pool.shape
     table = block_table.cpu().long()
     valid = (table >= 0) & (table < num_pages)
     pages = pool[table.clamp(0, num_pages - 1).to(pool.device)]                            # [B, max_pages, H, P, E]
-    pages = pages * valid.to(pool.device)[:, :, None, None, None].to(pool.dtype)
+    pages = torch.where(valid.to(pool.device)[:, :, None, None, None], pages, torch.zeros_like(pages))  # (a float pool may hold NaN)
     return pages.permute(0, 2, 1, 3, 4).reshape(table.shape[0], H, table.shape[1] * P, E)
 
 
@@ -258,22 +264,28 @@ def _in_use(block_table: torch.Tensor, lengths: torch.Tensor, P: int, num_pages:
     return out
 
 
-def composed_paged_append(k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, lengths: torch.Tensor, key: torch.Tensor,
-                          value: torch.Tensor, key_quantizer: LinearQuantizer, value_quantizer: LinearQuantizer, rope: Rope | None = None) -> None:
-    """``ops.kv_paged_append`` from existing pieces: the pages gathered into a dense ``[B, H, C, E]`` view, :func:`composed_append` on
-    it, and the pages the new rows touched scattered back (a row whose page lies outside the pool is dropped). `lengths` already counts
-    the L new rows; it and the table are read on the host."""
-    num_pages, P, L = k_pool.shape[0], k_pool.shape[2], key.shape[2]
-    k_dense, v_dense = gather_pages(k_pool, block_table), gather_pages(v_pool, block_table)
-    composed_append(k_dense, v_dense, lengths, key, value, key_quantizer, value_quantizer, rope)
+def _scatter_touched(pools: Sequence[torch.Tensor], dense: Sequence[torch.Tensor], block_table: torch.Tensor, lengths: torch.Tensor, L: int) -> None:
+    """The pages the L new rows of every sequence touched, copied from the gathered `dense` views back into their `pools` (a page
+    outside the pool is skipped). `lengths` already counts the rows; it and the table are read on the host."""
+    num_pages, P = pools[0].shape[0], pools[0].shape[2]
     rows = block_table.cpu().tolist()
     for b, n in enumerate(lengths.tolist()):
         first, last = max(n - L, 0), min(n, len(rows[b]) * P)
         for slot in range(first // P, -(-last // P) if last > first else 0):
             page = rows[b][slot]
             if 0 <= page < num_pages:
-                k_pool[page].copy_(k_dense[b, :, slot * P:(slot + 1) * P])
-                v_pool[page].copy_(v_dense[b, :, slot * P:(slot + 1) * P])
+                for pool, view in zip(pools, dense):
+                    pool[page].copy_(view[b, :, slot * P:(slot + 1) * P])
+
+
+def composed_paged_append(k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, lengths: torch.Tensor, key: torch.Tensor,
+                          value: torch.Tensor, key_quantizer: LinearQuantizer, value_quantizer: LinearQuantizer, rope: Rope | None = None) -> None:
+    """``ops.kv_paged_append`` from existing pieces: the pages gathered into a dense ``[B, H, C, E]`` view, :func:`composed_append` on
+    it, and the pages the new rows touched scattered back (a row whose page lies outside the pool is dropped). `lengths` already counts
+    the L new rows; it and the table are read on the host."""
+    k_dense, v_dense = gather_pages(k_pool, block_table), gather_pages(v_pool, block_table)
+    composed_append(k_dense, v_dense, lengths, key, value, key_quantizer, value_quantizer, rope)
+    _scatter_touched((k_pool, v_pool), (k_dense, v_dense), block_table, lengths, key.shape[2])
 
 
 def composed_paged_attend(query: Any, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, lengths: torch.Tensor,
@@ -286,24 +298,15 @@ def composed_paged_attend(query: Any, k_pool: torch.Tensor, v_pool: torch.Tensor
                            dtype, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer)
 
 
-class PagedQuantizedKVCache(_CacheBase):
-    """:class:`QuantizedKVCache` with the codes in fixed-size pages: two int8 pools of `num_pages` pages of `page_size` positions
-    shared by `batch` sequences, each of which addresses up to `max_pages_per_seq` of them through its row of ``block_table``
-    (int32 ``[batch, max_pages_per_seq]`` on the device, -1 where no page is assigned). A sequence owns only the pages it uses, a
-    finished sequence's pages go back to the free list without a copy, and two sequences can share the pages of a common prefix.
+class _PagedBase(_CacheBase):
+    """What the two paged caches share: the geometry checks, the two int8 pools (``"phse"`` allocates ``[num_pages, H, P, E]``,
+    ``"pshe"`` ``[num_pages, P, H, E]`` seen through ``transpose(1, 2)``), ``block_table``, ``lengths`` and the host-side page
+    bookkeeping (``reserve``, ``release``, ``share_prefix``, ``pages``, ``free_pages``, reference counts), stated once. Messages carry
+    the subclass's own name."""
 
-    ``layout="phse"`` allocates ``[num_pages, H, P, E]``; ``"pshe"`` allocates ``[num_pages, P, H, E]`` (a position's heads side by
-    side) and works on its ``transpose(1, 2)`` view. ``k_pool`` / ``v_pool`` are always ``[num_pages, H, P, E]`` views.
-
-    ``append`` and ``attend`` are one launch each (``ops.kv_paged_append`` / ``ops.kv_paged_decode``) and read neither a length nor
-    the table on the host, so a step can be captured in a graph and replayed. The page bookkeeping — ``reserve``, ``release``,
-    ``share_prefix`` — is host code that writes the table with one small copy: call it OUTSIDE a captured region, ahead of the step
-    that needs the page. A position whose page was never reserved is dropped by ``append`` and masked by ``attend``."""
-
-    def __init__(self, num_pages: int, page_size: int, kv_heads: int, head_dim: int, key_quantizer: LinearQuantizer,
-                 value_quantizer: LinearQuantizer, batch: int, max_pages_per_seq: int, dtype: torch.dtype = torch.bfloat16,
-                 device: torch.device | str = "cuda", layout: str = "phse") -> None:
-        name = "PagedQuantizedKVCache"
+    def __init__(self, num_pages: int, page_size: int, kv_heads: int, head_dim: int, key_quantizer: Any, value_quantizer: Any, batch: int,
+                 max_pages_per_seq: int, dtype: torch.dtype, device: torch.device | str, layout: str) -> None:
+        name = type(self).__name__
         if layout not in PAGED_LAYOUTS:
             raise ValueError(f"{name}: layout is one of {PAGED_LAYOUTS}, got {layout!r}")
         if not 16 <= page_size <= 256 or page_size & (page_size - 1):
@@ -314,15 +317,19 @@ class PagedQuantizedKVCache(_CacheBase):
         super().__init__(dtype, head_dim, key_quantizer, value_quantizer)
         self.layout, self.page_size, self.num_pages = layout, page_size, num_pages
         self.capacity = max_pages_per_seq * page_size  # positions a sequence can address
-        shape = (num_pages, kv_heads, page_size, head_dim) if layout == "phse" else (num_pages, page_size, kv_heads, head_dim)
-        buffers = [torch.zeros(shape, dtype=torch.int8, device=device) for _ in range(2)]
-        self.k_pool, self.v_pool = (t if layout == "phse" else t.transpose(1, 2) for t in buffers)
+        self.k_pool, self.v_pool = (self._pool(kv_heads, head_dim, torch.int8, device) for _ in range(2))
         self.block_table = torch.full((batch, max_pages_per_seq), -1, dtype=torch.int32, device=device)
         self.lengths = torch.zeros(batch, dtype=torch.int32, device=device)
         # the host's view of the table: the pages of every sequence in order, how many sequences hold each page, and the free pages
         self._pages: list[list[int]] = [[] for _ in range(batch)]
         self._refs = [0] * num_pages
         self._free = list(range(num_pages - 1, -1, -1))  # (a stack: page 0 goes out first)
+
+    def _pool(self, kv_heads: int, width: int, dtype: torch.dtype, device: torch.device | str) -> torch.Tensor:
+        """A zeroed pool ``[num_pages, H, P, width]`` view in the cache's layout."""
+        shape = (self.num_pages, kv_heads, self.page_size, width) if self.layout == "phse" else (self.num_pages, self.page_size, kv_heads, width)
+        t = torch.zeros(shape, dtype=dtype, device=device)
+        return t if self.layout == "phse" else t.transpose(1, 2)
 
     # ---- host-side page bookkeeping (never inside a captured region)
     @property
@@ -340,13 +347,14 @@ class PagedQuantizedKVCache(_CacheBase):
     def reserve(self, seq: int, n_positions: int) -> None:
         """Take pages from the free list until sequence `seq` can hold `n_positions`; RuntimeError (and nothing taken) when the pool
         cannot give them, ValueError beyond the sequence's capacity."""
+        name = type(self).__name__
         if not 0 <= n_positions <= self.capacity:
-            raise ValueError(f"PagedQuantizedKVCache.reserve: a sequence holds 0..{self.capacity} positions, got {n_positions}")
+            raise ValueError(f"{name}.reserve: a sequence holds 0..{self.capacity} positions, got {n_positions}")
         need = -(-n_positions // self.page_size) - len(self._pages[seq])
         if need <= 0:
             return
         if need > len(self._free):
-            raise RuntimeError(f"PagedQuantizedKVCache.reserve: the pool is exhausted ({need} pages wanted, {len(self._free)} free)")
+            raise RuntimeError(f"{name}.reserve: the pool is exhausted ({need} pages wanted, {len(self._free)} free)")
         for _ in range(need):
             page = self._free.pop()
             self._refs[page] = 1
@@ -366,16 +374,37 @@ class PagedQuantizedKVCache(_CacheBase):
     def share_prefix(self, src: int, dst: int, n_positions: int) -> None:
         """Point the first ``n_positions // page_size`` whole pages of `dst` (which holds no page yet) at `src`'s pages, reference
         counted, and set ``lengths[dst]`` to that many positions. A partial last page is not shared: `dst` appends those rows itself."""
+        name = type(self).__name__
         whole = n_positions // self.page_size
         if src == dst or self._pages[dst]:
-            raise ValueError("PagedQuantizedKVCache.share_prefix: the receiving sequence is another one and holds no page yet (release it first)")
+            raise ValueError(f"{name}.share_prefix: the receiving sequence is another one and holds no page yet (release it first)")
         if not 0 <= whole <= len(self._pages[src]):
-            raise ValueError(f"PagedQuantizedKVCache.share_prefix: sequence {src} holds {len(self._pages[src])} pages, {whole} wanted")
+            raise ValueError(f"{name}.share_prefix: sequence {src} holds {len(self._pages[src])} pages, {whole} wanted")
         self._pages[dst] = self._pages[src][:whole]
         for page in self._pages[dst]:
             self._refs[page] += 1
         self._write_row(dst)
         self.lengths[dst:dst + 1].fill_(whole * self.page_size)
+
+
+class PagedQuantizedKVCache(_PagedBase):
+    """:class:`QuantizedKVCache` with the codes in fixed-size pages: two int8 pools of `num_pages` pages of `page_size` positions
+    shared by `batch` sequences, each of which addresses up to `max_pages_per_seq` of them through its row of ``block_table``
+    (int32 ``[batch, max_pages_per_seq]`` on the device, -1 where no page is assigned). A sequence owns only the pages it uses, a
+    finished sequence's pages go back to the free list without a copy, and two sequences can share the pages of a common prefix.
+
+    ``layout="phse"`` allocates ``[num_pages, H, P, E]``; ``"pshe"`` allocates ``[num_pages, P, H, E]`` (a position's heads side by
+    side) and works on its ``transpose(1, 2)`` view. ``k_pool`` / ``v_pool`` are always ``[num_pages, H, P, E]`` views.
+
+    ``append`` and ``attend`` are one launch each (``ops.kv_paged_append`` / ``ops.kv_paged_decode``) and read neither a length nor
+    the table on the host, so a step can be captured in a graph and replayed. The page bookkeeping — ``reserve``, ``release``,
+    ``share_prefix`` — is host code that writes the table with one small copy: call it OUTSIDE a captured region, ahead of the step
+    that needs the page. A position whose page was never reserved is dropped by ``append`` and masked by ``attend``."""
+
+    def __init__(self, num_pages: int, page_size: int, kv_heads: int, head_dim: int, key_quantizer: LinearQuantizer,
+                 value_quantizer: LinearQuantizer, batch: int, max_pages_per_seq: int, dtype: torch.dtype = torch.bfloat16,
+                 device: torch.device | str = "cuda", layout: str = "phse") -> None:
+        super().__init__(num_pages, page_size, kv_heads, head_dim, key_quantizer, value_quantizer, batch, max_pages_per_seq, dtype, device, layout)
 
     # ---- the device side
     _SYMBOLS = ("ffq_kv_paged_append", "ffq_kv_paged_decode")
@@ -407,9 +436,8 @@ class PagedQuantizedKVCache(_CacheBase):
 
 
 # ---- the same cache with a dynamic quantizer per row ---------------------------------------------------------------------------------------
-def _dynamic_spec(quantizer: Any, what: str, head_dim: int) -> tuple[float, bool]:
-    """(bits, symmetric) of a dynamic quantizer the per-row append kernel reproduces, else ValueError."""
-    name = "DynamicQuantizedKVCache"
+def _dynamic_spec(quantizer: Any, what: str, head_dim: int, name: str = "DynamicQuantizedKVCache") -> tuple[float, bool]:
+    """(bits, symmetric) of a dynamic quantizer the per-row append kernels reproduce, else ValueError under the class's `name`."""
     if not isinstance(quantizer, DynamicLinearQuantizer):
         raise ValueError(f"{name}: the {what} quantizer must be a DynamicLinearQuantizer, got {type(quantizer).__name__}")
     bits = quantizer.num_bits
@@ -549,3 +577,73 @@ class DynamicQuantizedKVCache(_CacheBase):
     def values(self, length: int) -> QuantizedTensor:
         rows = self.params[:, :, :length]
         return _wrap_rows(self.v_cache[:, :, :length], rows[..., 2], rows[..., 3], self.value_quantizer, self.dtype)
+
+
+# ---- both: pages and a dynamic quantizer per row -------------------------------------------------------------------------------------------
+def composed_paged_token_append(k_pool: torch.Tensor, v_pool: torch.Tensor, param_pool: torch.Tensor, block_table: torch.Tensor, lengths: torch.Tensor,
+                                key: torch.Tensor, value: torch.Tensor, key_quantizer: DynamicLinearQuantizer, value_quantizer: DynamicLinearQuantizer,
+                                rope: Rope | None = None) -> None:
+    """``ops.kv_paged_token_append`` from existing pieces: the three pools gathered into dense views, :func:`composed_token_append` on
+    them, and the pages the new rows touched scattered back (a row whose page lies outside the pool is dropped, its parameters too).
+    `lengths` already counts the L new rows; it and the table are read on the host."""
+    dense = [gather_pages(pool, block_table) for pool in (k_pool, v_pool, param_pool)]
+    composed_token_append(*dense, lengths, key, value, key_quantizer, value_quantizer, rope)
+    _scatter_touched((k_pool, v_pool, param_pool), dense, block_table, lengths, key.shape[2])
+
+
+def composed_paged_token_attend(query: Any, k_pool: torch.Tensor, v_pool: torch.Tensor, param_pool: torch.Tensor, block_table: torch.Tensor,
+                                lengths: torch.Tensor, key_quantizer: DynamicLinearQuantizer, value_quantizer: DynamicLinearQuantizer,
+                                dtype: torch.dtype, is_causal: bool = True, scale: float | None = None, output_quantizer: Any = None) -> torch.Tensor:
+    """``ops.kv_paged_token_decode`` from existing pieces: :func:`composed_token_attend` on the gathered dense views. It reads the table
+    on the host and refuses (ValueError) a sequence whose length reaches a page outside the pool, which the kernel masks."""
+    _in_use(block_table, lengths, k_pool.shape[2], k_pool.shape[0])
+    return composed_token_attend(query, *(gather_pages(pool, block_table) for pool in (k_pool, v_pool, param_pool)), lengths, key_quantizer,
+                                 value_quantizer, dtype, is_causal=is_causal, scale=scale, output_quantizer=output_quantizer)
+
+
+class PagedDynamicQuantizedKVCache(_PagedBase):
+    """:class:`PagedQuantizedKVCache` with the two ``DynamicLinearQuantizer``s of :class:`DynamicQuantizedKVCache`: int8 K / V codes in
+    pages behind ``block_table``, every (sequence, head, position) row quantized with its own ``(scale, offset)`` when it is appended.
+    ``param_pool`` is the fp32 ``[num_pages, H, P, 4]`` view of ``(k_scale, k_offset, v_scale, v_offset)`` per row of every page
+    (``"pshe"`` allocates ``[num_pages, P, H, 4]``, like the codes): a page shared by two sequences shares its parameters. The quantizer
+    rule is :class:`DynamicQuantizedKVCache`'s, the pages and the bookkeeping (``reserve``, ``release``, ``share_prefix``, outside a
+    captured region) are :class:`PagedQuantizedKVCache`'s. ``append`` and ``attend`` are one launch each
+    (``ops.kv_paged_token_append`` / ``ops.kv_paged_token_decode``) and read nothing on the host."""
+
+    _SYMBOLS = ("ffq_kv_paged_token_append", "ffq_kv_paged_token_decode")
+
+    def __init__(self, num_pages: int, page_size: int, kv_heads: int, head_dim: int, key_quantizer: DynamicLinearQuantizer,
+                 value_quantizer: DynamicLinearQuantizer, batch: int, max_pages_per_seq: int, dtype: torch.dtype = torch.bfloat16,
+                 device: torch.device | str = "cuda", layout: str = "phse") -> None:
+        super().__init__(num_pages, page_size, kv_heads, head_dim, key_quantizer, value_quantizer, batch, max_pages_per_seq, dtype, device, layout)
+        self.param_pool = self._pool(kv_heads, 4, torch.float32, device)
+
+    def _quantizer_rule(self, quantizer: Any, what: str) -> tuple[float, bool]:
+        return _dynamic_spec(quantizer, what, self.head_dim, type(self).__name__)
+
+    def append(self, key: torch.Tensor, value: torch.Tensor, rope: Rope | None = None) -> None:
+        """:meth:`DynamicQuantizedKVCache.append` into pages: ``lengths += L``, then row l of batch b goes to position
+        ``lengths[b] - L + l`` of its sequence with its own codes and ``(scale, offset)``; rows outside ``[0, capacity)`` or on a page
+        never reserved are dropped, their parameters included. The rotary tables need `capacity` rows."""
+        k_spec, v_spec = self._new_rows(key, value, self.k_pool, f"[{self.lengths.shape[0]}, {self.k_pool.shape[1]}, L, {self.k_pool.shape[3]}] rows")
+        if self._native(key, value):
+            ops.kv_paged_token_append(key.detach(), value.detach(), self.k_pool, self.v_pool, self.param_pool, self.lengths, self.block_table, k_spec,
+                                      v_spec, rope=rope)
+        else:
+            composed_paged_token_append(self.k_pool, self.v_pool, self.param_pool, self.block_table, self.lengths, key.detach(), value.detach(),
+                                        self.key_quantizer, self.value_quantizer, rope)
+
+    def _native_attend(self, raw, is_causal, scale, output_quantizer, dequant, splits, plan_len) -> torch.Tensor:
+        return ops.kv_paged_token_decode(raw, self.k_pool, self.v_pool, self.param_pool, self.lengths, self.block_table, is_causal, scale,
+                                         output_quantizer, dequant[0], self.dtype, splits, plan_len)
+
+    def _composed_attend(self, query: Any, **how: Any) -> torch.Tensor:
+        return composed_paged_token_attend(query, self.k_pool, self.v_pool, self.param_pool, self.block_table, self.lengths, self.key_quantizer,
+                                           self.value_quantizer, self.dtype, **how)
+
+    def dense(self, seq: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The K and V codes and the parameters gathered into dense ``[B, H, capacity, E | 4]`` tensors (``[H, capacity, E | 4]`` for one
+        sequence), zeros where no page is assigned: a host-driven gather for tests and debugging, not a fast path."""
+        table = self.block_table if seq is None else self.block_table[seq:seq + 1]
+        k, v, params = (gather_pages(pool, table) for pool in (self.k_pool, self.v_pool, self.param_pool))
+        return (k, v, params) if seq is None else (k[0], v[0], params[0])

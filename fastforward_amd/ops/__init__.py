@@ -58,6 +58,7 @@ from fastforward_amd.ops.unfold import unfold_quantize  # noqa: F401
 from fastforward_amd.ops.sdpa import sdpa_quantize  # noqa: F401
 from fastforward_amd.ops.decode import sdpa_decode, sdpa_decode_plan, sdpa_decode_workspace_bytes  # noqa: F401
 from fastforward_amd.ops.kv_cache import kv_append, kv_decode, kv_paged_append, kv_paged_decode, kv_token_append, kv_token_decode  # noqa: F401
+from fastforward_amd.ops.kv_cache import kv_paged_token_append, kv_paged_token_decode  # noqa: F401
 from fastforward_amd.ops.registry import NATIVE_DISPATCH, TORCH_EXTENSION_PATH, _LIBRARY  # noqa: F401,E402
 
 __all__ = [
@@ -118,6 +119,8 @@ __all__ = [
     "kv_decode",
     "kv_paged_append",
     "kv_paged_decode",
+    "kv_paged_token_append",
+    "kv_paged_token_decode",
     "kv_token_append",
     "kv_token_decode",
     "FLAG_INF",

@@ -13,7 +13,10 @@ and never on the host. The codes and the attention's bits are those of the dense
 ``kv_token_append`` / ``kv_token_decode`` (include/ffq_kv_token.h) are the dense calls with one DYNAMIC ``(scale, offset)`` per
 (sequence, kv head, position) for K and for V, kept in an fp32 store ``[B, H, S_max, 4]`` beside the codes: the append computes them on
 the device from every new row's own min / max (the codes and parameters of ``quantize_dynamic_by_tile`` with the tile ``(1, 1, 1, E)``),
-the decode reads them back per key row."""
+the decode reads them back per key row.
+
+``kv_paged_token_append`` / ``kv_paged_token_decode`` (include/ffq_kv_paged_token.h) are both at once: the codes in pages behind a block
+table and the per-position parameters in a third pool ``[num_pages, H, P, 4]`` of the same pages, so a shared page shares them."""
 
 from __future__ import annotations
 
@@ -345,3 +348,76 @@ def kv_token_decode(
     return _run_decode("ffq_kv_token_decode", query, k_cache, v_cache, (params, lens), dt, (B, H, HKV, L, E, rows), plan_len or S_max, splits, scale,
                        dequant, output_quantizer, (_ptr(params), _ptr(lens), B, H, HKV, L, S_max, E), (int(bool(is_causal)),), (splits, plan_len or 0),
                        row_params=params)
+
+
+def kv_paged_token_append(
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    param_pool: torch.Tensor,
+    lens: torch.Tensor,
+    block_table: torch.Tensor,
+    k_spec: Spec,
+    v_spec: Spec,
+    rope: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> None:
+    """One call of ``ffq_kv_paged_token_append``: :func:`kv_token_append` into pages. The pools and the table are
+    :func:`kv_paged_append`'s; `param_pool` is fp32 ``[num_pages, H, P, 4]`` (the last dimension contiguous, rows 16-byte aligned, any
+    other strides) and receives ``(k_scale, k_offset, v_scale, v_offset)`` of every row written, at row ``pos % P`` of page
+    ``block_table[b, pos // P]`` like the codes. Codes and parameters of a row are :func:`kv_token_append`'s. A row outside ``[0, C)``,
+    or whose table entry lies outside ``[0, num_pages)``, is skipped, its parameters included. Nothing is read on the host."""
+    name = "kv_paged_token_append"
+    if k_new.dim() != 4 or v_new.dim() != 4:
+        raise RuntimeError(f"{name}: the new rows are 4-D [B, H, L, E]")
+    B, HKV, L, E = k_new.shape
+    if tuple(v_new.shape) != (B, HKV, L, E):
+        raise RuntimeError(f"{name}: shapes {tuple(k_new.shape)}, {tuple(v_new.shape)} do not fit")
+    num_pages, P, max_pages = _pools_ok(name, k_pool, v_pool, block_table, B, HKV, E)
+    if not _params_ok(param_pool, num_pages, HKV, P):
+        raise RuntimeError(f"{name}: param_pool is fp32 [{num_pages}, {HKV}, {P}, 4] with 16-byte aligned rows, got {param_pool.dtype} {tuple(param_pool.shape)}")
+    _check_new_rows(name, k_new, v_new, k_pool, v_pool, lens)
+    table_stride = block_table.stride(0) if B > 1 else max_pages
+    _run_append(name, k_new, v_new, k_pool, v_pool, (param_pool, lens, block_table), max_pages * P, k_spec, v_spec, rope,
+                (B, HKV, L, num_pages, P, max_pages, table_stride, E), row_params=param_pool)
+
+
+def kv_paged_token_decode(
+    query: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    param_pool: torch.Tensor,
+    lens: torch.Tensor,
+    block_table: torch.Tensor,
+    is_causal: bool = False,
+    scale: float | None = None,
+    output_quantizer: tuple[torch.Tensor, torch.Tensor | None, float] | None = None,
+    q_dequant: Dequant | None = None,
+    dtype: torch.dtype | None = None,
+    splits: int = 0,
+    plan_len: int | None = None,
+) -> torch.Tensor:
+    """One call of ``ffq_kv_paged_token_decode``: :func:`kv_token_decode` over pools ``[num_pages, H, P, E]`` and the parameter pool
+    ``[num_pages, H, P, 4]`` addressed through `block_table` (:func:`kv_paged_token_append`), with the capacity ``C = max_pages * P`` in
+    the place of ``S_max``. The keys of a table entry outside ``[0, num_pages)`` are masked and their parameters never read. The result
+    is bit-equal to :func:`kv_token_decode` on the same codes and parameters laid out densely at the same split count."""
+    name = "kv_paged_token_decode"
+    if query.dim() != 4:
+        raise RuntimeError(f"{name}: q is 4-D [B, H, L, E]")
+    dequant = (q_dequant, None, None)
+    dt, B, H, L, E, HKV, rows = _check_decode(name, query, k_pool, v_pool, dequant, dtype, k_pool.shape[1] if k_pool.dim() == 4 else 0, splits)
+    if min(B, L) < 1:
+        raise RuntimeError(f"{name}: empty operands {tuple(query.shape)}")
+    num_pages, P, max_pages = _pools_ok(name, k_pool, v_pool, block_table, B, HKV, E)
+    C = max_pages * P
+    if not _params_ok(param_pool, num_pages, HKV, P):
+        raise RuntimeError(f"{name}: param_pool is fp32 [{num_pages}, {HKV}, {P}, 4] with 16-byte aligned rows, got {param_pool.dtype} {tuple(param_pool.shape)}")
+    if not _lens_ok(lens, B):
+        raise RuntimeError(f"{name}: lens is a contiguous int32 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+    if plan_len is not None and not 1 <= plan_len <= C:
+        raise RuntimeError(f"{name}: plan_len is a key count in 1..{C}, got {plan_len}")
+    table_stride = block_table.stride(0) if B > 1 else max_pages
+    return _run_decode("ffq_kv_paged_token_decode", query, k_pool, v_pool, (param_pool, lens, block_table), dt, (B, H, HKV, L, E, rows), plan_len or C,
+                       splits, scale, dequant, output_quantizer,
+                       (_ptr(param_pool), _ptr(lens), _ptr(block_table), B, H, HKV, L, num_pages, P, max_pages, table_stride, E),
+                       (int(bool(is_causal)),), (splits, plan_len or 0), row_params=param_pool)
