@@ -381,6 +381,15 @@ SIGNATURES_PAGED_TOKEN: dict[str, tuple[object, list[object]]] = {
     ),
 }
 
+# name -> (restype, argtypes); mirrors include/lpbq/ffq_lpbq.h one to one: the eleventh header's table (LPBQ weights: scale compression,
+# the fused weight quantizer into int8 per-channel codes, and the expansion of 4-bit codes at rest), bound as SIGNATURES_3D is (None
+# on a library without the symbol).
+SIGNATURES_LPBQ: dict[str, tuple[object, list[object]]] = {
+    "ffq_lpbq_compress_scales": (_i, [_vp, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    "ffq_lpbq_quantize": (_i, [_vp, _i, _i64, _vp, _i64, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "ffq_lpbq_expand": (_i, [_vp, _i, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
+}
+
 SDPA_DECODE_MAX_ROWS = 32  # FFQ_SDPA_DECODE_MAX_ROWS
 SDPA_DECODE_KEY_TILE = 128  # FFQ_SDPA_DECODE_KEY_TILE
 SDPA_DECODE_MAX_SPLITS = 64  # FFQ_SDPA_DECODE_MAX_SPLITS
@@ -414,7 +423,7 @@ class FFQLibrary:
             setattr(self, name, None)
         for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items(),
                                           *SIGNATURES_UNFOLD.items(), *SIGNATURES_DECODE.items(), *SIGNATURES_KV.items(), *SIGNATURES_PAGED.items(),
-                                          *SIGNATURES_KV_TOKEN.items(), *SIGNATURES_PAGED_TOKEN.items()):
+                                          *SIGNATURES_KV_TOKEN.items(), *SIGNATURES_PAGED_TOKEN.items(), *SIGNATURES_LPBQ.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

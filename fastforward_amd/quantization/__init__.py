@@ -7,3 +7,4 @@ from fastforward_amd.quantization.function import QuantizationParameters as Quan
 from fastforward_amd.quantization.fuse import find_weight_quantizers as find_weight_quantizers  # noqa: E402
 from fastforward_amd.quantization.fuse import fuse_qdq_weights as fuse_qdq_weights  # noqa: E402
 from fastforward_amd.quantization.freeze import freeze_parameters as freeze_parameters  # noqa: E402
+from fastforward_amd.quantization import lpbq as lpbq  # noqa: E402
