@@ -49,5 +49,6 @@ import fastforward_amd.fused_index  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_unfold  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_sdpa  # noqa: E402,F401  isort: skip
 import fastforward_amd.fused_sdpa_decode  # noqa: E402,F401  isort: skip
+import fastforward_amd.fused_mx  # noqa: E402,F401  isort: skip
 
 __version__ = "0.1.0"

@@ -390,6 +390,18 @@ SIGNATURES_LPBQ: dict[str, tuple[object, list[object]]] = {
     "ffq_lpbq_expand": (_i, [_vp, _i, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include_mx/ffq_mx.h one to one: the twelfth header's table (OCP microscaling: the MXFP8 / MXFP4
+# quantizer, its inverse, and the linear on the block-scaled matrix cores), bound as SIGNATURES_3D is (None on a library without the symbol).
+SIGNATURES_MX: dict[str, tuple[object, list[object]]] = {
+    "ffq_mx_quantize": (_i, [_vp, _i, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "ffq_mx_dequantize": (_i, [_vp, _i, _vp, _i64, _i64, _i, _vp, _i, _vp]),
+    "ffq_linear_mx_supported": (_i, [_i64, _i64, _i64, _i, _i]),
+    "ffq_linear_mx": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i, _vp, _i, _vp, _i, _i64, _i64, _i64, _vp]),
+}
+
+MX_E4M3 = 0  # FFQ_MX_E4M3
+MX_E2M1 = 1  # FFQ_MX_E2M1
+
 SDPA_DECODE_MAX_ROWS = 32  # FFQ_SDPA_DECODE_MAX_ROWS
 SDPA_DECODE_KEY_TILE = 128  # FFQ_SDPA_DECODE_KEY_TILE
 SDPA_DECODE_MAX_SPLITS = 64  # FFQ_SDPA_DECODE_MAX_SPLITS
@@ -423,7 +435,8 @@ class FFQLibrary:
             setattr(self, name, None)
         for name, (restype, argtypes) in (*SIGNATURES_3D.items(), *SIGNATURES_DEPTHWISE.items(), *SIGNATURES_INDEX.items(),
                                           *SIGNATURES_UNFOLD.items(), *SIGNATURES_DECODE.items(), *SIGNATURES_KV.items(), *SIGNATURES_PAGED.items(),
-                                          *SIGNATURES_KV_TOKEN.items(), *SIGNATURES_PAGED_TOKEN.items(), *SIGNATURES_LPBQ.items()):
+                                          *SIGNATURES_KV_TOKEN.items(), *SIGNATURES_PAGED_TOKEN.items(), *SIGNATURES_LPBQ.items(),
+                                          *SIGNATURES_MX.items()):
             fn = getattr(self._dll, name, None)
             if fn is not None:
                 fn.restype = restype

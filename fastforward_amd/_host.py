@@ -119,3 +119,82 @@ def quantize_dynamic_by_tile(data: torch.Tensor, tile_size: Sequence[int], num_b
     if not can_support_bitwidth(output_dtype, num_bits):
         raise RuntimeError(f"Provided dtype ({output_dtype}) is not enough to store {num_bits} bits quantized values.")
     return out.to(output_dtype), scale, offset
+
+
+# ---- OCP microscaling (MX): the torch restatement of include_mx/ffq_mx.h and docs/numerics.md, on any device ------------------------------
+MX_BLOCK = 32
+MX_FORMATS = ("e4m3", "e2m1")
+_MX_EMAX = {"e4m3": 8, "e2m1": 2}
+_MX_MAX = {"e4m3": 448.0, "e2m1": 6.0}
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx_check_format(element_format: str) -> str:
+    if element_format not in MX_FORMATS:
+        raise ValueError(f"the MX element format is 'e4m3' or 'e2m1', got {element_format!r}")
+    return element_format
+
+
+def mx_quantize(data: torch.Tensor, element_format: str) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(codes uint8 of data's shape, scales uint8 [..., K / 32])``: one code per byte (e2m1: in the low nibble), one E8M0 byte per block
+    of 32 consecutive elements of the last dimension."""
+    fmt = mx_check_format(element_format)
+    if data.dim() < 1 or data.shape[-1] % MX_BLOCK:
+        raise ValueError(f"mx_quantize: the last dimension must be a multiple of {MX_BLOCK}, got shape {tuple(data.shape)}")
+    x = data.detach().to(torch.float32).contiguous()
+    blocks = x.reshape(*x.shape[:-1], x.shape[-1] // MX_BLOCK, MX_BLOCK)
+    magnitude = blocks.view(torch.int32) & 0x7FFFFFFF  # NaN and Inf sort above every finite value
+    e = magnitude.amax(dim=-1) >> 23
+    poisoned = e == 255
+    scale = torch.where(poisoned, torch.full_like(e, 255), (e - _MX_EMAX[fmt]).clamp(min=0))
+    mult = ((254 - torch.where(poisoned, torch.full_like(e, 127), scale)) << 23).to(torch.int32).view(torch.float32)  # 2^(127 - scale)
+    y = (blocks * mult[..., None]).clamp(-_MX_MAX[fmt], _MX_MAX[fmt])
+    y = torch.where(poisoned[..., None], torch.zeros_like(y), y)
+    if fmt == "e4m3":
+        codes = y.to(torch.float8_e4m3fn).view(torch.uint8)
+    else:
+        ay = y.abs()
+        mag = ((ay > 0.25).to(torch.uint8) + (ay >= 0.75) + (ay > 1.25) + (ay >= 1.75) + (ay > 2.5) + (ay >= 3.5) + (ay > 5.0)).to(torch.uint8)
+        codes = mag | (torch.signbit(y).to(torch.uint8) << 3)
+    codes = torch.where(poisoned[..., None], torch.zeros_like(codes), codes)
+    return codes.reshape(x.shape), scale.to(torch.uint8)
+
+
+def mx_scale_values(scales: torch.Tensor) -> torch.Tensor:
+    """2^(code - 127) in fp32: subnormal for code 0, NaN for code 255."""
+    s = scales.to(torch.int32)
+    bits = torch.where(s == 0, torch.full_like(s, 0x00400000), torch.where(s == 255, torch.full_like(s, 0x7FC00000), s << 23))
+    return bits.view(torch.float32)
+
+
+def mx_element_values(codes: torch.Tensor, element_format: str) -> torch.Tensor:
+    """The fp32 value of each element code (one per byte)."""
+    if mx_check_format(element_format) == "e4m3":
+        return codes.view(torch.float8_e4m3fn).to(torch.float32)
+    grid = torch.tensor(_E2M1_GRID, dtype=torch.float32, device=codes.device)
+    value = grid[(codes & 7).long()]
+    return torch.where((codes & 8) != 0, -value, value)
+
+
+def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, element_format: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``value(code) * 2^(scale - 127)`` as one fp32 product, rounded once to `dtype`. `codes` holds one code per byte."""
+    if codes.shape[-1] % MX_BLOCK or tuple(scales.shape) != (*codes.shape[:-1], codes.shape[-1] // MX_BLOCK):
+        raise ValueError(f"mx_dequantize: codes {tuple(codes.shape)} and scales {tuple(scales.shape)} do not match")
+    value = mx_element_values(codes, element_format)
+    blocks = value.reshape(*scales.shape, MX_BLOCK) * mx_scale_values(scales)[..., None]
+    return blocks.reshape(codes.shape).to(dtype)
+
+
+def mx_pack(codes: torch.Tensor) -> torch.Tensor:
+    """e2m1 codes one per byte -> two per byte along the last dimension: element 2i in the low nibble, 2i + 1 in the high one."""
+    if codes.dtype != torch.uint8 or codes.shape[-1] % 2:
+        raise ValueError(f"mx_pack: uint8 codes with an even last dimension, got {codes.dtype} {tuple(codes.shape)}")
+    pairs = codes.reshape(*codes.shape[:-1], codes.shape[-1] // 2, 2)
+    return (pairs[..., 0] & 15) | (pairs[..., 1] << 4)
+
+
+def mx_unpack(packed: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``mx_pack``."""
+    if packed.dtype != torch.uint8:
+        raise ValueError(f"mx_unpack: uint8 bytes, got {packed.dtype}")
+    return torch.stack((packed & 15, packed >> 4), dim=-1).reshape(*packed.shape[:-1], packed.shape[-1] * 2)

@@ -7,6 +7,7 @@ from fastforward_amd.nn.quantizer import default_tags as default_tags
 from fastforward_amd.nn.dynamic_linear_quantizer import DynamicLinearQuantizer as DynamicLinearQuantizer  # isort: skip
 from fastforward_amd.nn.linear_quantizer import LinearQuantizer as LinearQuantizer  # isort: skip
 from fastforward_amd.nn.lpbq_quantizer import LPBQLinearQuantizer as LPBQLinearQuantizer  # isort: skip
+from fastforward_amd.nn.mx_quantizer import MXQuantizer as MXQuantizer  # isort: skip
 from fastforward_amd.nn.quantized_module import QuantizedModule as QuantizedModule  # isort: skip
 from fastforward_amd.nn.quantized_module import SKIP_QUANTIZATION as SKIP_QUANTIZATION  # isort: skip
 from fastforward_amd.nn.quantized_module import named_quantizers as named_quantizers  # isort: skip

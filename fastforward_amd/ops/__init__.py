@@ -14,7 +14,7 @@ forms of A1), ``reductions`` (A4 / A5), ``packing`` (A7, GGUF, GPTQ, the grid es
 quantized weight and a plain input), ``producers`` (RMSNorm / SiLU*up / rotary / attention with A1 fused), ``modules``
 (LayerNorm / Embedding / ReLU / SiLU with A2 and A1 fused), ``conv`` (the W8A8 convolutions, 2-D, transposed and 3-D), ``elementwise`` (add / sub / mul / div,
 softmax, sigmoid, GELU with A2 and A1 fused), ``math`` (rms_norm, pow by a number, exp / sin / cos, sum and cumsum with A2 and A1
-fused), ``pool`` (avg_pool1d / avg_pool2d / avg_pool3d / max_pool2d and nearest interpolate with A2 and A1 fused), ``concat`` (cat and pad with A2 and A1 fused), ``index`` (index_add and permute with A2 and A1 fused), ``unfold`` (im2col with A2 and A1 fused), ``sdpa`` (the quantized scaled_dot_product_attention in one launch), ``decode`` (the same for a short query over int8 K / V codes, split over the keys), ``kv_cache`` (the in-place append of a preallocated int8 KV cache and that attention with device-side lengths, dense, in pages behind a block table, or with one dynamic (scale, offset) per position), ``lpbq`` (W4 block-quantized weights as int8 per-channel codes: scale compression, the fused weight quantizer, the expansion of codes at rest), ``registry`` (the torch operator
+fused), ``pool`` (avg_pool1d / avg_pool2d / avg_pool3d / max_pool2d and nearest interpolate with A2 and A1 fused), ``concat`` (cat and pad with A2 and A1 fused), ``index`` (index_add and permute with A2 and A1 fused), ``unfold`` (im2col with A2 and A1 fused), ``sdpa`` (the quantized scaled_dot_product_attention in one launch), ``decode`` (the same for a short query over int8 K / V codes, split over the keys), ``kv_cache`` (the in-place append of a preallocated int8 KV cache and that attention with device-side lengths, dense, in pages behind a block table, or with one dynamic (scale, offset) per position), ``lpbq`` (W4 block-quantized weights as int8 per-channel codes: scale compression, the fused weight quantizer, the expansion of codes at rest), ``mx`` (OCP microscaling: the MXFP8 / MXFP4 quantizer, its inverse and the linear on the block-scaled matrix cores), ``registry`` (the torch operator
 library and the C++ extension), ``_base`` (device check, tags, scratch). Every public name is re-exported here: ``ops.linear_wq`` etc.
 """
 
@@ -60,6 +60,7 @@ from fastforward_amd.ops.decode import sdpa_decode, sdpa_decode_plan, sdpa_decod
 from fastforward_amd.ops.kv_cache import kv_append, kv_decode, kv_paged_append, kv_paged_decode, kv_token_append, kv_token_decode  # noqa: F401
 from fastforward_amd.ops.kv_cache import kv_paged_token_append, kv_paged_token_decode  # noqa: F401
 from fastforward_amd.ops.lpbq import lpbq_compress_scales, lpbq_expand, lpbq_quantize  # noqa: F401
+from fastforward_amd.ops.mx import linear_mx, linear_mx_supported, mx_dequantize, mx_quantize  # noqa: F401
 from fastforward_amd.ops.registry import NATIVE_DISPATCH, TORCH_EXTENSION_PATH, _LIBRARY  # noqa: F401,E402
 
 __all__ = [
@@ -127,6 +128,10 @@ __all__ = [
     "lpbq_compress_scales",
     "lpbq_quantize",
     "lpbq_expand",
+    "mx_quantize",
+    "mx_dequantize",
+    "linear_mx",
+    "linear_mx_supported",
     "FLAG_INF",
     "FLAG_NAN",
 ]

@@ -8,3 +8,4 @@ from fastforward_amd.quantization.fuse import find_weight_quantizers as find_wei
 from fastforward_amd.quantization.fuse import fuse_qdq_weights as fuse_qdq_weights  # noqa: E402
 from fastforward_amd.quantization.freeze import freeze_parameters as freeze_parameters  # noqa: E402
 from fastforward_amd.quantization import lpbq as lpbq  # noqa: E402
+from fastforward_amd.quantization import mx as mx  # noqa: E402
